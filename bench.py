@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec, TenAnt, 4096 envs per GPU, PPO rollout (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K rollout steps of the headline and prints the JSON line (`value`, `ms_per_step` and the
+configuration).  Everything else below -- the informational series, the step kernel's and the policy layers' rooflines, the layers'
+error against float64, the repeat pass and the CPU baseline -- takes runs of its own and is measured with `--full` only.
+`--dump-outputs DIR` writes what the headline's last timed step computed (rank 0's shard) as DIR/<name>.npy in float32, the inputs
+being seeded, so that two builds can be compared output for output.
 
 One "step" = one PPO rollout step over this rank's 4096 envs: actor + critic inference (the reference's
 ActorCritic, agents/algorithms/rl/ppo/module.py: two MLPs [1024,1024,512], ELU, fp32 -- each hidden layer of both networks one
 launch with bias + ELU fused: mms_linear_group_act_split16, the fp32 product evaluated on the 16-bit matrix pipe from operands carried
 as two fp16 planes under a power-of-two scale per row (operands kept to 2^-22, three plane products, fp32 accumulation; its error
-against float64 is measured in this run next to the exact-fp32 MFMA kernel's and the three-bf16-plane kernel's,
+against float64 is measured with --full next to the exact-fp32 MFMA kernel's and the three-bf16-plane kernel's,
 `policy_layers_error_vs_f64`, and the rollout with each of those two layer kernels is timed beside it:
 `rollout_exact_fp32_layers`, `rollout_bf16x3_layers`), both last layers + Gaussian action sample + log-prob + the
 add_transitions stores (mms_ppo_heads_act, one HIP launch), the fused VecTask
@@ -19,7 +25,7 @@ straight into the rollout slots), and every nsteps=8 steps the GAE scan + advant
 Envs are sharded over ranks with no data-path collective (weak scaling); `value` = all ranks' env-steps
 divided by the slowest rank's time.  Inputs are synthetic and resident in HBM before the timed region.
 
-The JSON line also carries
+With --full the JSON line also carries
   sim_only      the same engine stepped with pre-drawn actions (no policy), the series the step kernel's
                 roofline is computed from,
   roofline      step kernel: algorithmic bytes (4660 B per env-step) / measured launch
@@ -40,6 +46,11 @@ if ROOT not in sys.path:
 ALGO_BYTES_PER_ENV_STEP = 4660
 HBM_PEAK_GBS = 8000.0                   # MI355X_MICROARCH.md: 8 TB/s spec
 NSTEPS = 8                              # cfg/ppo/config.yaml:23
+# Untimed rollout steps in front of the headline's warm-up.  The rollout's step time settles only after ~2 K rollout steps on one
+# engine: timed ~100 steps after the reset-all it runs 0.5-5 % slower per step (engine steps with random actions or a GPU kept
+# busy in front of it do not close that gap; rollout steps do).  The headline was always timed in the settled state: the series
+# that now run with --full only used to run before it.
+HEADLINE_PREWARM = 2048
 GAMMA, LAM = 0.96, 0.95                 # cfg/ppo/config.yaml:30-31
 
 
@@ -75,6 +86,50 @@ def shard_for_rank(rank, world, envs_per_gpu):
     return rank * envs_per_gpu, world * envs_per_gpu
 
 
+DUMP_BUDGET_BYTES = 60 << 20                 # --dump-outputs: 64 MB in all, with room for the .npy headers
+
+
+def last_step_outputs(storage, obs_clipped, read_from_engine=False):
+    """{name: (host array, env axis)} of what the last rollout step handed its caller: the action, log-prob, value, mean and log-std
+    that `act` produced from the observation in slot t, the engine's next observation, reward and done -- and, when that step closed
+    the rollout, the returns and normalised advantages of all its slots.  t is the slot the step filled (the storage cursor is one
+    past it, or 0 once the rollout closed).  The next observation is slot t + 1 inside a rollout, else the engine's clamped row
+    (`read_from_engine`: the unfused path keeps it there at every step)."""
+    T = storage.num_transitions_per_env
+    t = (storage.step - 1) % T
+    nxt = obs_clipped if (read_from_engine or t == T - 1) else storage.observations[t + 1]
+    host = lambda x: x.detach().float().cpu().numpy()
+    out = {"obs": storage.observations[t], "actions": storage.actions[t], "actions_log_prob": storage.actions_log_prob[t],
+           "values": storage.values[t], "mu": storage.mu[t], "sigma": storage.sigma[t], "next_obs": nxt,
+           "rewards": storage.rewards[t], "dones": storage.dones[t]}
+    out = {k: (host(v), 0) for k, v in out.items()}
+    if t == T - 1:
+        out["returns"], out["advantages"] = (host(storage.returns), 1), (host(storage.advantages), 1)
+    return out
+
+
+def write_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Writes {name: (array, env axis)} as out_dir/<name>.npy in float32.  When the arrays would exceed `budget` bytes, the same
+    fixed, seeded sample of env rows is kept in every array and its indices go to env_rows.npy (float64).  Returns the bytes
+    written."""
+    import numpy as np
+    arrays = {k: (np.ascontiguousarray(a, dtype=np.float32), ax) for k, (a, ax) in arrays.items()}
+    rows = {a.shape[ax] for a, ax in arrays.values()}
+    if len(rows) != 1:
+        raise ValueError("arrays disagree on the number of env rows: %s" % sorted(rows))
+    n = rows.pop()
+    total = sum(a.nbytes for a, _ in arrays.values())
+    if total > budget:
+        keep = int(budget // (total / n + 8))
+        idx = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrays = {k: (np.take(a, idx, axis=ax), ax) for k, (a, ax) in arrays.items()}
+        arrays["env_rows"] = (idx.astype(np.float64), 0)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, (a, _) in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sum(a.nbytes for a, _ in arrays.values())
+
+
 POLICY_CFG = {"pi_hid_sizes": [1024, 1024, 512], "vf_hid_sizes": [1024, 1024, 512], "activation": "elu"}   # cfg/ppo/config.yaml:6-9
 INIT_NOISE_STD = 0.8                                                                                        # cfg/ppo/config.yaml:33
 
@@ -107,6 +162,10 @@ def main():
                     help="A/B: the policy's output heads + sampling as their own launch (mms_ppo_heads_act) instead of the step kernel's prologue (mms_bind_policy_head)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=0, help="oracle steps for the CPU baseline (0 = sized for ~15 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the informational series, rooflines, layer errors, repeat pass and CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
 
     import torch
@@ -159,50 +218,50 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- sim-only series: pre-drawn U(-1,1) actions, ring of 16 ---------------------
-    g = torch.Generator(device="cpu").manual_seed(1234)
-    ring = [(torch.rand(N, act_dim, generator=g) * 2 - 1).to(device) for _ in range(16)]
-
-    def sim_step(i):
-        eng.bind_actions(ring[i % 16])              # the engine reads the caller's tensor in place (mms_bind_actions): no copy kernel
-        eng.step()
-
-    for i in range(64):                         # reset-all + settle
-        sim_step(i)
-    barrier()
-    sim_steps = max((args.steps // 64) * 64, 256)
-    sim_graph = None
-    if not args.no_graph:                       # 16 steps (one pass over the ring) per hipGraph replay
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):
-            sim_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(sim_graph, stream=side):
-                for i in range(16):
-                    sim_step(i)
-        torch.cuda.current_stream(device).wait_stream(side)
-        for _ in range(8):                      # the first replays of a fresh graph can carry a one-off runtime stall (tens of ms)
-            sim_graph.replay()
-    barrier()
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    # timed in four equal batches; the series' figure is the MEDIAN batch: early in a process a replay occasionally carries a
-    # one-off runtime stall of tens of ms (seen with every kernel layout, tools/scratch/sim_graph_probe.py), which would otherwise
-    # decide this informational series.  All four batch times are reported.
-    sim_batches = []
-    per_batch = sim_steps // 4
-    for b in range(4):
-        t0 = time.perf_counter()
-        if sim_graph is None:
-            for i in range(per_batch):
-                sim_step(b * per_batch + i)
-        else:
-            for _ in range(per_batch // 16):
+    # ---- sim-only series (--full): pre-drawn U(-1,1) actions, ring of 16 --------------
+    sim_steps, sim_graph, sim_batches, sim_wall, sim_wall_mean = 0, None, [], 0.0, 0.0
+    if args.full:
+        g = torch.Generator(device="cpu").manual_seed(1234)
+        ring = [(torch.rand(N, act_dim, generator=g) * 2 - 1).to(device) for _ in range(16)]
+
+        def sim_step(i):
+            eng.bind_actions(ring[i % 16])              # the engine reads the caller's tensor in place (mms_bind_actions): no copy kernel
+            eng.step()
+
+        for i in range(64):                         # reset-all + settle
+            sim_step(i)
+        barrier()
+        sim_steps = max((args.steps // 64) * 64, 256)
+        if not args.no_graph:                       # 16 steps (one pass over the ring) per hipGraph replay
+            side = torch.cuda.Stream(device)
+            side.wait_stream(torch.cuda.current_stream(device))
+            with torch.cuda.stream(side):
+                sim_graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(sim_graph, stream=side):
+                    for i in range(16):
+                        sim_step(i)
+            torch.cuda.current_stream(device).wait_stream(side)
+            for _ in range(8):                      # the first replays of a fresh graph can carry a one-off runtime stall (tens of ms)
                 sim_graph.replay()
-        torch.cuda.synchronize()
-        sim_batches.append(time.perf_counter() - t0)
-    eng.bind_actions(None)
-    sim_wall = 4.0 * sorted(sim_batches)[1]            # (lower) median batch x 4; the mean and every batch are reported beside it
-    sim_wall_mean = sum(sim_batches)
+        barrier()
+        # timed in four equal batches; the series' figure is the MEDIAN batch: early in a process a replay occasionally carries a
+        # one-off runtime stall of tens of ms (seen with every kernel layout, tools/scratch/sim_graph_probe.py), which would otherwise
+        # decide this informational series.  All four batch times are reported.
+        per_batch = sim_steps // 4
+        for b in range(4):
+            t0 = time.perf_counter()
+            if sim_graph is None:
+                for i in range(per_batch):
+                    sim_step(b * per_batch + i)
+            else:
+                for _ in range(per_batch // 16):
+                    sim_graph.replay()
+            torch.cuda.synchronize()
+            sim_batches.append(time.perf_counter() - t0)
+        eng.bind_actions(None)
+        sim_wall = 4.0 * sorted(sim_batches)[1]            # (lower) median batch x 4; the mean and every batch are reported beside it
+        sim_wall_mean = sum(sim_batches)
     # step-kernel launch duration: back-to-back launches with nothing else on the stream, HIP events around them.
     # Measured twice -- here, after the sim-only series, and again right after the GEMM-heavy rollout series -- because the
     # kernel is VALU-issue bound and so follows the core clock, which the rollout's matrix-core bursts pull down.
@@ -223,7 +282,7 @@ def main():
             times.append(ev0.elapsed_time(ev1) / per)
         step_kernel_batches.append(times)
         return sorted(times)[(batches - 1) // 2]
-    kernel_ms_pre = time_step_kernel()
+    kernel_ms_pre = time_step_kernel() if args.full else 0.0
 
     # ---- PPO rollout series -----------------------------------------------------------------------------------
     PLANES_SCALE = 2048.0                                                   # clip_obs 5 x 2^11 <= 2^14
@@ -231,7 +290,7 @@ def main():
     planes_state = {"used": False}
     head_state = {"fused": False}
 
-    def measure_rollout(pdtype, K_req, W_req, split=True, fmt=None, use_graph=True):
+    def measure_rollout(pdtype, K_req, W_req, split=True, fmt=None, use_graph=True, dump_dir=None, prewarm=64):
         ac_ = ac if pdtype == torch.float32 else ac_bf16
         ac_.split_layers = bool(split)
         ac_.split_format = fmt or args.split_format
@@ -369,7 +428,7 @@ def main():
 
         W = W_req if graph is None else ((W_req + NSTEPS - 1) // NSTEPS) * NSTEPS    # warm-up: whole rollouts, at least W steps
         storage.clear()
-        run_steps(max(64, NSTEPS))                          # always: 64 untimed steps before the W warm-up steps the caller asked for
+        run_steps(max(prewarm, NSTEPS))                     # always: untimed steps before the W warm-up steps the caller asked for
         storage.clear()                                     # (clocks, allocator pools, first replays), outside the timed region
         run_steps(W)
         barrier()
@@ -377,7 +436,11 @@ def main():
         run_steps(K)
         barrier()
         elapsed_ = time.perf_counter() - t0
+        if dump_dir is not None:
+            write_outputs(dump_dir, last_step_outputs(storage, obs_clipped, read_from_engine=args.unfused))
         storage.clear()
+        if not args.full:
+            return elapsed_, K, W, graph is not None
         # a second, untimed-for-the-headline pass over the same K steps: `value` is the FIRST timing, as the contract says; the repeat is
         # reported beside it so that a one-off runtime stall inside either (tens of ms, rare: see sim_only.outlier_batches) can be told
         t1 = time.perf_counter()
@@ -422,7 +485,7 @@ def main():
         torch.cuda.synchronize()
         in_rollout_ms.append(robust_mean())
         # launches of the plain step kernel inside rollout steps of this series: all of them, or -- head fused -- the probe's only
-        rollout_counts.append(4 * NSTEPS if fused_engine is not None else NSTEPS + max(64, NSTEPS) + W + 2 * K + 4 * NSTEPS)
+        rollout_counts.append(4 * NSTEPS if fused_engine is not None else NSTEPS + max(prewarm, NSTEPS) + W + 2 * K + 4 * NSTEPS)
         return elapsed_, K, W, graph is not None
 
     in_rollout_ms, rollout_counts, repeat_ms, in_rollout_head_ms = [], [], [], []
@@ -430,26 +493,29 @@ def main():
     ac_bf16 = None
     bf_elapsed, bf_K = 0.0, 0
     if args.policy_dtype == "fp32":
-        import copy
-        ac_bf16 = copy.deepcopy(ac).to(torch.bfloat16)
-        bf_elapsed, bf_K, _, _ = measure_rollout(torch.bfloat16, min(args.steps, 128), 16)     # informational series
+        if args.full:
+            import copy
+            ac_bf16 = copy.deepcopy(ac).to(torch.bfloat16)
+            bf_elapsed, bf_K, _, _ = measure_rollout(torch.bfloat16, min(args.steps, 128), 16)     # informational series
     else:
         ac_bf16 = ac.to(torch.bfloat16)
     # the same rollout with the hidden layers on the exact-fp32 MFMA kernel (round 2's headline path), beside the split kernel
     ex_elapsed, ex_K, b3_elapsed, b3_K = 0.0, 0, 0.0, 0
-    if args.policy_dtype == "fp32" and not args.exact_fp32_layers and not args.library_gemms:
+    if args.full and args.policy_dtype == "fp32" and not args.exact_fp32_layers and not args.library_gemms:
         ex_elapsed, ex_K, _, _ = measure_rollout(torch.float32, min(args.steps, 128), 16, split=False)
         if args.split_format != "bf16x3":
             b3_elapsed, b3_K, _, _ = measure_rollout(torch.float32, min(args.steps, 128), 16, fmt="bf16x3")
     # the same K steps launched eagerly from Python, the way the reference's loop drives the path (ppo.py:126-161: act -> step ->
     # add_transitions per step) -- what a swapped-import PPO.run obtains without capturing anything
     eg_elapsed, eg_K = 0.0, 0
-    if not args.no_graph:
+    if args.full and not args.no_graph:
         eg_elapsed, eg_K, _, _ = measure_rollout(pdtype, min(args.steps, 512), 16, split=not args.exact_fp32_layers, use_graph=False)
-    elapsed, K, W, graphed = measure_rollout(pdtype, args.steps, args.warmup, split=not args.exact_fp32_layers)
+    elapsed, K, W, graphed = measure_rollout(pdtype, args.steps, args.warmup, split=not args.exact_fp32_layers,
+                                             dump_dir=args.dump_outputs if rank == 0 else None, prewarm=HEADLINE_PREWARM)
     graph = graphed or None
-    refresh_us = None
-    if pdtype == torch.float32 and not args.library_gemms:
+    refresh_us, layer_err, layer_roof = None, None, None
+    kernel_ms, kernel_ms_b2b, kernel_ms_roll = 0.0, 0.0, 0.0
+    if args.full and pdtype == torch.float32 and not args.library_gemms:
         for _ in range(4):
             ac.refresh()
         torch.cuda.synchronize()
@@ -460,20 +526,22 @@ def main():
         torch.cuda.synchronize()
         refresh_us = 1e3 * ev0.elapsed_time(ev1) / 32
     ac.bind_rollout(None, None)                 # (a bound storage at step 0 would make every probe call below refresh the derived buffers first)
-    layer_err = policy_layer_errors(torch, ac, obs_clipped) if (args.policy_dtype == "fp32" and not args.library_gemms) else None
-    layer_roof = policy_layer_roofline(torch, ac, obs_clipped, args) if (args.policy_dtype == "fp32" and not args.library_gemms) else None
+    if args.full and args.policy_dtype == "fp32" and not args.library_gemms:
+        layer_err = policy_layer_errors(torch, ac, obs_clipped)
+        layer_roof = policy_layer_roofline(torch, ac, obs_clipped, args)
     eng.bind_obs_out(None)
     eng.bind_obs_planes(None)
     eng.bind_rollout_out(None, None)
     eng.set_obs_outputs(True, True)
-    kernel_ms_post = time_step_kernel()
-    kernel_ms_b2b = 0.5 * (kernel_ms_pre + kernel_ms_post)
-    kernel_ms_roll = in_rollout_ms[-1]
-    # average over the step-kernel launches of this run (what a kernel trace of the same command averages): back-to-back
-    # launches (sim-only series, its warm-up, the timing loops) and launches inside rollout steps (all series)
-    n_b2b = 64 + 8 * 16 + sim_steps + 2 * 256
-    n_roll = sum(rollout_counts)
-    kernel_ms = (n_b2b * kernel_ms_b2b + n_roll * kernel_ms_roll) / (n_b2b + n_roll)
+    if args.full:
+        kernel_ms_post = time_step_kernel()
+        kernel_ms_b2b = 0.5 * (kernel_ms_pre + kernel_ms_post)
+        kernel_ms_roll = in_rollout_ms[-1]
+        # average over the step-kernel launches of this run (what a kernel trace of the same command averages): back-to-back
+        # launches (sim-only series, its warm-up, the timing loops) and launches inside rollout steps (all series)
+        n_b2b = 64 + 8 * 16 + sim_steps + 2 * 256
+        n_roll = sum(rollout_counts)
+        kernel_ms = (n_b2b * kernel_ms_b2b + n_roll * kernel_ms_roll) / (n_b2b + n_roll)
     tmax = torch.tensor([elapsed, sim_wall, kernel_ms, bf_elapsed, kernel_ms_b2b, kernel_ms_roll, ex_elapsed], dtype=torch.float64, device=device)
     if dist is not None:
         if dist.get_backend() == "gloo":
@@ -484,23 +552,15 @@ def main():
     resets_seen = int(eng.tensor("reset_count").sum().item())
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(N, args.cpu_steps)
 
-    # which packed layout mms_step launches (csrc/step_kernels.hip: launch_step): 16 envs per 768-thread block once every CU gets one
-    force16 = os.environ.get("MMS_STEP_BLOCK16")
-    block16 = (force16[0] != "0") if force16 else N >= 16 * torch.cuda.get_device_properties(device).multi_processor_count
-    step_kernel_name = "mms::ant_step_kernel<TEN_ANT, 768, 16, 10>" if block16 else "mms::ant_step_kernel<TEN_ANT, 192, 4, 10>"
     if rank == 0:
         value = world * N * K / elapsed
-        sim_value = world * N * sim_steps / sim_wall
-        achieved = ALGO_BYTES_PER_ENV_STEP * N / (kernel_ms * 1e-3) / 1e9
-        tr = measured_traffic()
-        traffic = tr["traffic_bytes_per_launch"] if (tr and tr.get("num_envs") == N) else None
         line = {
             "metric": "env-steps/sec (whole node), TenAnt 4096 envs/GPU, PPO rollout",
             "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": args.warmup, "warmup_effective": W,
-            "ms_per_step": 1e3 * elapsed / K, "ms_per_step_repeat": repeat_ms[-1], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "ms_per_step": 1e3 * elapsed / K, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": (("f32 (policy-layer products: fp32 operands as 2 row-scaled fp16 planes (kept to 2^-22), 3 f16 MFMA products, fp32 accumulation; "
                        if args.split_format == "f16x2" else
                        "f32 (policy-layer products: fp32 operands as 3 exact bf16 planes, 6 bf16 MFMA products, fp32 accumulation; ") +
@@ -514,39 +574,51 @@ def main():
                                     "boxgnd_mu": eng.config.model.boxgnd_mu, "antbox_mu": eng.config.model.antbox_mu,
                                     "note": "this build's modelling choice (PhysX default combine rule), not reference-pinned: DESIGN.md section 4"},
                        "critic_deferred": bool(args.defer_critic), "finite": finite, "resets_total": resets_seen,
-                       "distributed": None if dist is None else {"backend": dist.get_backend(), "world_size": dist.get_world_size()}},
-            "sim_only": {"value": sim_value, "unit": "env-steps/s", "steps": sim_steps, "ms_per_step": 1e3 * sim_wall / sim_steps,
-                         "value_mean": world * N * sim_steps / sim_wall_mean, "ms_per_step_mean": 1e3 * sim_wall_mean / sim_steps,
-                         "note": "engine step with pre-drawn actions (ring of 16); four equal batches: `value` from the median batch, "
-                                 "`value_mean` from all four; a batch more than 1.5 x the median is listed in `outlier_batches`",
-                         "batch_ms": [1e3 * b for b in sim_batches],
-                         "outlier_batches": [i for i, b in enumerate(sim_batches) if b > 1.5 * sorted(sim_batches)[1]],
-                         "hipgraph": sim_graph is not None},
-            "roofline": {"bound": "hbm", "kernel": step_kernel_name, "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": (tr or {}).get("source"),
-                         "traffic_note": "launches of the rollout step (one observation row per env-step); the stand-alone engine "
-                                         "configuration of the back-to-back launches also writes its raw + clamped observation "
-                                         "buffers: %s bytes per launch" % ((tr or {}).get("engine_buffers_configuration") or {}).get("traffic_bytes_per_launch"),
-                         "bytes_per_launch": ALGO_BYTES_PER_ENV_STEP * N, "launch_ms": kernel_ms,
-                         "obs_planes_bytes_per_launch": (((obs_dim + 31) // 32) * 128 * N) if planes_state["used"] else 0,
-                         "obs_planes_note": "in the rollout the launch also stores the clamped row as the policy layers' operand planes "
-                                            "(mms_bind_obs_planes16): work moved INTO this kernel from the policy's split pass, not counted in the "
-                                            "algorithmic bytes -- the in-rollout duration includes it",
-                         "launch_ms_back_to_back": kernel_ms_b2b, "launch_ms_in_rollout": kernel_ms_roll,
-                         "launch_ms_in_rollout_with_policy_head": (in_rollout_head_ms[-1] if (in_rollout_head_ms and head_state["fused"]) else None),
-                         "policy_head_note": "with config.policy_head_in_step_kernel the rollout's launches are the <..., false, true> instantiation of the step kernel: "
-                                             "the policy's output heads + sampling tail (mms_ppo_heads_act's arithmetic: ~5.4 KB more algorithmic bytes per env-step) in "
-                                             "its prologue -- launch_ms_in_rollout_with_policy_head; every other figure of this object is the step kernel alone",
-                         "back_to_back_batches_ms": step_kernel_batches,
-                         "launches": {"back_to_back": n_b2b, "in_rollout": n_roll},
-                         "frac_back_to_back": ALGO_BYTES_PER_ENV_STEP * N / (kernel_ms_b2b * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "launch_note": "HIP events on the launch stream: 2 x 256 back-to-back launches (each as eight batches of 32, median batch; all batch times in back_to_back_batches_ms) and 32 launches inside eager rollout steps "
-                                        "(right after the policy GEMMs, when the core clock is lowered: the kernel is VALU-issue bound and follows "
-                                        "it); launch_ms = average over all step-kernel launches of this run, the figure a kernel trace of the same "
-                                        "command averages"},
-            "cpu_baseline": cpu,
+                       "distributed": None if dist is None else {"backend": dist.get_backend(), "world_size": dist.get_world_size()}}
         }
+        if args.full:
+            sim_value = world * N * sim_steps / sim_wall
+            achieved = ALGO_BYTES_PER_ENV_STEP * N / (kernel_ms * 1e-3) / 1e9
+            tr = measured_traffic()
+            traffic = tr["traffic_bytes_per_launch"] if (tr and tr.get("num_envs") == N) else None
+            # which packed layout mms_step launches (csrc/step_kernels.hip: launch_step): 16 envs per 768-thread block once every CU gets one
+            force16 = os.environ.get("MMS_STEP_BLOCK16")
+            block16 = (force16[0] != "0") if force16 else N >= 16 * torch.cuda.get_device_properties(device).multi_processor_count
+            step_kernel_name = "mms::ant_step_kernel<TEN_ANT, 768, 16, 10>" if block16 else "mms::ant_step_kernel<TEN_ANT, 192, 4, 10>"
+            line.update({
+                "ms_per_step_repeat": repeat_ms[-1],
+                "sim_only": {"value": sim_value, "unit": "env-steps/s", "steps": sim_steps, "ms_per_step": 1e3 * sim_wall / sim_steps,
+                             "value_mean": world * N * sim_steps / sim_wall_mean, "ms_per_step_mean": 1e3 * sim_wall_mean / sim_steps,
+                             "note": "engine step with pre-drawn actions (ring of 16); four equal batches: `value` from the median batch, "
+                                     "`value_mean` from all four; a batch more than 1.5 x the median is listed in `outlier_batches`",
+                             "batch_ms": [1e3 * b for b in sim_batches],
+                             "outlier_batches": [i for i, b in enumerate(sim_batches) if b > 1.5 * sorted(sim_batches)[1]],
+                             "hipgraph": sim_graph is not None},
+                "roofline": {"bound": "hbm", "kernel": step_kernel_name, "achieved": achieved, "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                             "traffic_source": (tr or {}).get("source"),
+                             "traffic_note": "launches of the rollout step (one observation row per env-step); the stand-alone engine "
+                                             "configuration of the back-to-back launches also writes its raw + clamped observation "
+                                             "buffers: %s bytes per launch" % ((tr or {}).get("engine_buffers_configuration") or {}).get("traffic_bytes_per_launch"),
+                             "bytes_per_launch": ALGO_BYTES_PER_ENV_STEP * N, "launch_ms": kernel_ms,
+                             "obs_planes_bytes_per_launch": (((obs_dim + 31) // 32) * 128 * N) if planes_state["used"] else 0,
+                             "obs_planes_note": "in the rollout the launch also stores the clamped row as the policy layers' operand planes "
+                                                "(mms_bind_obs_planes16): work moved INTO this kernel from the policy's split pass, not counted in the "
+                                                "algorithmic bytes -- the in-rollout duration includes it",
+                             "launch_ms_back_to_back": kernel_ms_b2b, "launch_ms_in_rollout": kernel_ms_roll,
+                             "launch_ms_in_rollout_with_policy_head": (in_rollout_head_ms[-1] if (in_rollout_head_ms and head_state["fused"]) else None),
+                             "policy_head_note": "with config.policy_head_in_step_kernel the rollout's launches are the <..., false, true> instantiation of the step kernel: "
+                                                 "the policy's output heads + sampling tail (mms_ppo_heads_act's arithmetic: ~5.4 KB more algorithmic bytes per env-step) in "
+                                                 "its prologue -- launch_ms_in_rollout_with_policy_head; every other figure of this object is the step kernel alone",
+                             "back_to_back_batches_ms": step_kernel_batches,
+                             "launches": {"back_to_back": n_b2b, "in_rollout": n_roll},
+                             "frac_back_to_back": ALGO_BYTES_PER_ENV_STEP * N / (kernel_ms_b2b * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "launch_note": "HIP events on the launch stream: 2 x 256 back-to-back launches (each as eight batches of 32, median batch; all batch times in back_to_back_batches_ms) and 32 launches inside eager rollout steps "
+                                            "(right after the policy GEMMs, when the core clock is lowered: the kernel is VALU-issue bound and follows "
+                                            "it); launch_ms = average over all step-kernel launches of this run, the figure a kernel trace of the same "
+                                            "command averages"},
+                "cpu_baseline": cpu,
+            })
         if ex_K:
             line["rollout_exact_fp32_layers"] = {"value": world * N * ex_K / ex_elapsed, "unit": "env-steps/s", "steps": ex_K, "ms_per_step": 1e3 * ex_elapsed / ex_K,
                                                  "note": "the same rollout with the hidden layers on the exact-fp32 MFMA kernel (mms_linear2_act, v_mfma_f32_32x32x2_f32): "

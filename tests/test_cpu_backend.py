@@ -449,25 +449,6 @@ def test_obs_planes_from_the_step_on_cpu_build():
     check_obs_planes("cpu", task="OneAnt")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/agents"), reason="the reference tree is not present on this machine (it does not travel to the GPU box)")
-def test_reference_learners_drop_in_unchanged(tmp_path):
-    """The reference's real learners, imported in place and unmodified, over this build's VecTaskPython / MultiVecTaskPython on the
-    CPU build: PPO.run (agents/algorithms/rl/ppo/ppo.py:99-175), Runner.run (agents/algorithms/marl/runner.py:114-151) as mappo, happo
-    and hatrpo (the sequential update_factor path, :266-316), DDPG.run (rl/ddpg/ddpg.py:116-204) and TD3.run (rl/td3/td3.py) on
-    MultiIngenuity -- each with the reference's own storage / module / buffer classes and with this build's drop-in ones, mappo also
-    with the grouped policy inference as the Runner's collect step.  The committed log of the same script:
-    tests/golden/reference_learners_dropin.log."""
-    log = tmp_path / "dropin.log"
-    env = dict(os.environ, MMS_DROPIN_LOG=str(log), OMP_NUM_THREADS="4")
-    r = subprocess.run([os.sys.executable, os.path.join(ROOT, "tests", "golden", "run_reference_learners.py")], env=env, stdout=subprocess.PIPE,
-                       stderr=subprocess.STDOUT, timeout=900)
-    assert r.returncode == 0, r.stdout.decode()[-3000:]
-    text = log.read_text()
-    assert text.count(": ok") == 13 and "GroupedPolicyInference as Runner.collect: ok" in text
-    for learner, n in (("PPO.run", 2), ("mappo, unmodified", 3), ("happo, unmodified", 2), ("hatrpo, unmodified", 2), ("DDPG.run", 2), ("TD3.run", 2)):
-        assert text.count(learner) == n, (learner, text)
-
-
 def test_refresh_entry_points_and_module_refresh_on_cpu_build():
     """The device-side refresh of the f16x2 layers' weight planes / bound chain (mms_weight_planes16_group, mms_chain_refresh16),
     of the folded-LayerNorm layers' weight side (mms_fold_planes16_group, mms_fold_scales16_group) and ActorCritic.refresh() on the CPU build: tests/refresh_check.py (the HIP build runs the same list)."""

@@ -2,6 +2,7 @@
 agree, the built-in configuration equals the reference YAML, the MJCF-subset compiler reproduces the built-in
 ant description, argument parsing, and the multi-rank logic (gloo, world size 2)."""
 import ctypes
+import json
 import os
 import re
 import subprocess
@@ -10,12 +11,10 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 
 from massive_marl_benchmark_amd import _lib
 from massive_marl_benchmark_amd.model import (ANT_DESCRIPTION, MMS_ABI_VERSION, MmsConfig, default_cfg, load_mjcf_ant, make_config, task_dims)
-
-REF = "/root/reference"
 
 
 def declared_symbols():
@@ -54,26 +53,25 @@ def test_library_loads_without_gpu_and_refuses_cpu():
         Engine("TenAnt", num_envs=4)
 
 
-def test_struct_layout_matches_c():
+def test_struct_layout_matches_c(tmp_path):
     src = '#include "include/mms.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(){printf("%zu %zu %zu %zu\\n", sizeof(mms_config), sizeof(mms_model), offsetof(mms_config, model), offsetof(mms_model, gravity));return 0;}'
-    exe = "/tmp/mms_layout_test"
+    exe = str(tmp_path / "mms_layout_test")
     subprocess.run(["gcc", "-x", "c", "-", "-I", ROOT, "-o", exe], input=src.encode(), check=True, cwd=ROOT)
     a, b, c, d = map(int, subprocess.check_output([exe]).split())
     from massive_marl_benchmark_amd.model import MmsModel
     assert (a, b, c, d) == (ctypes.sizeof(MmsConfig), ctypes.sizeof(MmsModel), MmsConfig.model.offset, MmsModel.gravity.offset)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
 @pytest.mark.parametrize("task", ["TenAnt", "OneAnt", "MultiIngenuity"])
 def test_default_cfg_equals_reference_yaml(task):
-    import yaml
-    ref = yaml.safe_load(open(os.path.join(REF, "cfg", task + ".yaml")))
+    """The reference's cfg/<task>.yaml as parsed values (tests/golden/reference_cfg.json, tests/golden/make_config_fixtures.py)."""
+    with open(os.path.join(GOLDEN, "reference_cfg.json")) as f:
+        ref = json.load(f)[task]
     assert default_cfg(task) == ref
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
 def test_mjcf_compiler_matches_builtin_description():
-    d = load_mjcf_ant(os.path.join(REF, "assets/mjcf/open_ai_assets/ant/nv_ant.xml"))
+    d = load_mjcf_ant(os.path.join(GOLDEN, "nv_ant.xml"))                 # the reference's ant model (tests/golden/make_config_fixtures.py)
     for key in ("armature", "damping", "gear", "density", "limb_radius"):
         assert d[key] == ANT_DESCRIPTION[key], key
     assert d["torso"]["sphere_radius"] == ANT_DESCRIPTION["torso"]["sphere_radius"]
@@ -358,3 +356,57 @@ def test_kernel_resources_of_the_built_library():
         if "linear_split" in k:                                     # 512-thread blocks, two waves per SIMD: 256 registers is all there is
             assert vgpr <= 256, (k, vgpr)
     assert sum(1 for k in kernels if "linear_split16_kernel" in k) >= 12 and sum(1 for k in kernels if "linear_split_kernel" in k) >= 8
+
+
+def test_bench_last_step_outputs_pick_the_filled_slot():
+    """bench.py --dump-outputs: the slot the last step filled (the storage cursor is one past it, or 0 once the rollout closed), its
+    next observation (slot t + 1 inside a rollout, the engine's clamped row at its end or on the unfused path), and the returns /
+    advantages only when that step closed the rollout."""
+    import torch
+    from bench import last_step_outputs
+    from massive_marl_benchmark_amd.algorithms.rl.ppo.storage import RolloutStorage
+    T, N = 8, 6
+    st = RolloutStorage(N, T, (5,), (0,), (3,), device="cpu")
+    g = torch.Generator().manual_seed(3)
+    for name in ("observations", "actions", "actions_log_prob", "values", "mu", "sigma", "rewards", "returns", "advantages"):
+        getattr(st, name).copy_(torch.randn(getattr(st, name).shape, generator=g))
+    st.dones.copy_((torch.rand(st.dones.shape, generator=g) > 0.5).byte())
+    engine_row = torch.randn(N, 5, generator=g)
+    st.step = 3
+    out = last_step_outputs(st, engine_row)
+    assert set(out) == {"obs", "actions", "actions_log_prob", "values", "mu", "sigma", "next_obs", "rewards", "dones"}
+    assert all(ax == 0 and a.dtype == np.float32 and a.shape[0] == N for a, ax in out.values())
+    assert np.array_equal(out["obs"][0], st.observations[2].numpy()) and np.array_equal(out["actions"][0], st.actions[2].numpy())
+    assert np.array_equal(out["next_obs"][0], st.observations[3].numpy()) and np.array_equal(out["dones"][0], st.dones[2].float().numpy())
+    assert np.array_equal(last_step_outputs(st, engine_row, read_from_engine=True)["next_obs"][0], engine_row.numpy())
+    st.step = 0
+    out = last_step_outputs(st, engine_row)
+    assert np.array_equal(out["mu"][0], st.mu[T - 1].numpy()) and np.array_equal(out["next_obs"][0], engine_row.numpy())
+    assert out["returns"][1] == 1 and np.array_equal(out["returns"][0], st.returns.numpy())
+    assert np.array_equal(out["advantages"][0], st.advantages.numpy())
+
+
+def test_bench_write_outputs_float32_and_within_budget(tmp_path):
+    """bench.py --dump-outputs writes float32 .npy files; above the byte budget every array keeps the same fixed, seeded sample of env
+    rows (listed in env_rows.npy), the same from run to run."""
+    from bench import DUMP_BUDGET_BYTES, write_outputs
+    assert DUMP_BUDGET_BYTES + 4096 <= 64 << 20                     # the budget leaves room for the files' headers
+    rng = np.random.default_rng(0)
+    arrays = {"a": (rng.standard_normal((1000, 40)), 0), "b": (rng.integers(0, 2, (1000, 1)).astype(np.uint8), 0),
+              "c": (rng.standard_normal((8, 1000, 1)), 1)}
+    n = write_outputs(str(tmp_path / "all"), arrays)
+    assert n == 1000 * (40 + 1 + 8) * 4 and sorted(os.listdir(tmp_path / "all")) == ["a.npy", "b.npy", "c.npy"]
+    a = np.load(tmp_path / "all" / "a.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, arrays["a"][0].astype(np.float32))
+    budget = 40000
+    sizes = [write_outputs(str(tmp_path / d), arrays, budget=budget) for d in ("s1", "s2")]
+    assert sizes[0] == sizes[1] <= budget
+    rows = np.load(tmp_path / "s1" / "env_rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    idx = rows.astype(np.int64)
+    for name, (src, ax) in arrays.items():
+        got = [np.load(tmp_path / d / (name + ".npy")) for d in ("s1", "s2")]
+        assert got[0].dtype == np.float32 and np.array_equal(got[0], got[1])
+        assert np.array_equal(got[0], np.take(src, idx, axis=ax).astype(np.float32)), name
+    with pytest.raises(ValueError):
+        write_outputs(str(tmp_path / "bad"), {"a": (np.zeros((3, 2)), 0), "b": (np.zeros((4, 2)), 0)})
