@@ -36,6 +36,8 @@
  *                                                                        mms_marl_heads_finish
  *   Actor / Critic forward of every MAPPO / HAPPO agent                  mms_linear_group_act, mms_layernorm_group,
  *     (algorithms/marl/actor_critic.py:43-69, 137-155; runner.py:186-216)  mms_row_stats_group, mms_marl_heads_act
+ *   SquashedGaussianMLPActor heads + rsample + log-probability          mms_sac_heads_act
+ *     (algorithms/rl/sac/module.py:23-61; sac.py:166, 374-376)
  *
  * Ownership: the engine owns every buffer it reports through mms_get_tensor for the lifetime of the
  * handle; callers wrap them as NON-owning views and must keep the handle alive while any view exists.
@@ -293,6 +295,29 @@ typedef struct mms_policy_head {
                                   * One operand load of the head's matrix phase then reads 1 KB of contiguous memory (csrc/head_block.h). */
 } mms_policy_head;
 int mms_bind_policy_head(mms_handle h, const mms_policy_head* head);   /* NULL: unbind */
+
+/* SAC's policy head (algorithms/rl/sac/module.py:23-61, SquashedGaussianMLPActor.forward after `net`) in ONE launch: what torch
+ * evaluates as two GEMMs, clamp, exp, randn, fma, tanh, pow, sub, log, sum and a scale.  SAC calls it on every env step for the
+ * collection (actor_critic.act, sac.py:166) and for the Q target of every update (pi(o2) under no_grad, sac.py:374-376).
+ *   mu_i      = hidden_i @ mu_weight^T + mu_bias;   log_std_i = clamp(hidden_i @ ls_weight^T + ls_bias, -20, 2)   (module.py:31-35)
+ *     on the matrix cores (v_mfma_f32_16x16x4_f32: exact fp32 products and sums); hidden [N,H] f32 is the output of `net`'s last
+ *     activation, the weights [A,H] and biases [A] are torch's mu_layer / log_std_layer parameters, read in place
+ *   u_ij      = mu_ij (deterministic != 0) | mu_ij + exp(log_std_ij) * z_ij (rsample, :41-44)
+ *     z_ij ~ N(0,1): counter-based (seed, global row = row_offset + i, counters[i], j) as in mms_ppo_act; counters[i] += 1 in sample
+ *     mode; deterministic mode draws nothing and leaves counters alone (counters may then be NULL)
+ *   logp_i    = sum_j (-z_ij^2 / 2 - log_std_ij - log(2 pi) / 2 - log(1 - tanh(u_ij)^2 + epsilon))   (:46-52, z = 0 when deterministic)
+ *   action_ij = act_limit * tanh(u_ij)                                                                 (:58-59)
+ * Destinations (any may be NULL: no store): actions_out / act_slot (e.g. a ReplayBuffer row) / u_slot (pre-squash sample) / mu_slot /
+ * log_std_slot (clamped) [N,A], logp_slot [N]; logp_slot == NULL is with_logprob=False and skips the log terms.  H a positive multiple
+ * of 64, 1 <= A <= 128, hidden and both weights 16-byte aligned.  Bad arguments return non-zero with mms_last_error(NULL) and write
+ * nothing. */
+int mms_sac_heads_act(int device, const float* hidden, int32_t H,
+                      const float* mu_weight, const float* mu_bias, const float* ls_weight, const float* ls_bias,
+                      float act_limit, float epsilon, int32_t deterministic,
+                      uint64_t seed, int64_t* counters, int64_t row_offset,
+                      float* actions_out, float* act_slot, float* logp_slot,
+                      float* u_slot, float* mu_slot, float* log_std_slot,
+                      int64_t N, int32_t A, void* hip_stream);
 
 /* One hidden layer of the PPO policy for BOTH networks in one launch (module.py:27-52: nn.Linear + activation, actor and
  * critic of the same shape): y_g = act(x_g @ w_g^T + b_g), g = 0, 1, on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact

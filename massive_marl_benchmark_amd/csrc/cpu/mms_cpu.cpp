@@ -18,6 +18,7 @@
 
 #include "../../../include/mms.h"
 #include "../rollout_lane.h"
+#include "../sac_lane.h"
 #include "lane_step.h"
 
 #define MMS_API extern "C" __attribute__((visibility("default")))
@@ -444,6 +445,55 @@ MMS_API int mms_ppo_heads_act(int device, const float* hidden, const float* weig
         }
         sample_row(mean, v, vhidden != nullptr || value != nullptr, log_std, seed, counters, row_offset, reference_scale, actions_out, act_slot,
                    logp_slot, value_slot, mu_slot, sigma_slot, row, A);
+    }
+    return 0;
+}
+MMS_API int mms_sac_heads_act(int device, const float* hidden, int32_t H, const float* mu_weight, const float* mu_bias, const float* ls_weight,
+                              const float* ls_bias, float act_limit, float epsilon, int32_t deterministic, uint64_t seed, int64_t* counters,
+                              int64_t row_offset, float* actions_out, float* act_slot, float* logp_slot, float* u_slot, float* mu_slot,
+                              float* log_std_slot, int64_t N, int32_t A, void*) {
+    if (cpu_only(device)) return 1;
+    if (!hidden || !mu_weight || !mu_bias || !ls_weight || !ls_bias || (!deterministic && !counters) || N < 0 || A <= 0 || A > 128 || H <= 0 ||
+        (H % 64) != 0) {
+        g_error = "mms_sac_heads_act: bad arguments (A must be in 1..128, H a positive multiple of 64, counters required unless deterministic)";
+        return 1;
+    }
+    if (((uintptr_t)hidden | (uintptr_t)mu_weight | (uintptr_t)ls_weight) & 15) {
+        g_error = "mms_sac_heads_act: hidden and both weight matrices must be 16-byte aligned";
+        return 1;
+    }
+    const bool want_logp = logp_slot != nullptr;
+#pragma omp parallel for schedule(static)
+    for (int64_t row = 0; row < N; row++) {
+        const float* h = hidden + row * (int64_t)H;
+        const int64_t c = deterministic ? 0 : counters[row];
+        float lane[64];                     // the kernel's wave butterfly (lane j holds actions j, j + 64; xor 32, 16, ... 1)
+        for (int l = 0; l < 64; l++) lane[l] = 0.f;
+        for (int j = 0; j < A; j++) {
+            float mu = 0.f, ls = 0.f;
+            for (int k = 0; k < H; k++) mu = fmaf(h[k], mu_weight[(int64_t)j * H + k], mu);
+            for (int k = 0; k < H; k++) ls = fmaf(h[k], ls_weight[(int64_t)j * H + k], ls);
+            mu += mu_bias[j];
+            float u, lsc, term;
+            const float act = mms::sac_sample_one(mu, ls + ls_bias[j], deterministic, seed, (uint64_t)(row_offset + row), (uint64_t)c, (uint32_t)j,
+                                                  act_limit, epsilon, want_logp, u, lsc, term);
+            lane[j & 63] += term;
+            const int64_t at = row * A + j;
+            if (actions_out) actions_out[at] = act;
+            if (act_slot) act_slot[at] = act;
+            if (u_slot) u_slot[at] = u;
+            if (mu_slot) mu_slot[at] = mu;
+            if (log_std_slot) log_std_slot[at] = lsc;
+        }
+        if (want_logp) {
+            for (int m = 32; m >= 1; m >>= 1) {
+                float nxt[64];
+                for (int l = 0; l < 64; l++) nxt[l] = lane[l] + lane[l ^ m];
+                memcpy(lane, nxt, sizeof(lane));
+            }
+            logp_slot[row] = lane[0];
+        }
+        if (!deterministic) counters[row] = c + 1;
     }
     return 0;
 }

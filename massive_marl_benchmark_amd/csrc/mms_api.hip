@@ -26,6 +26,8 @@ hipError_t launch_gae_marl_agents(const float*, const float*, const float*, floa
 hipError_t launch_ppo_act(const float*, const float*, const float*, uint64_t, int64_t*, int64_t, int, float*, float*, float*, float*, float*, float*, int64_t, int, hipStream_t);
 hipError_t launch_ppo_head_act(const float*, const float*, const float*, int, const float*, const float*, const float*, const float*, int, const float*, uint64_t,
                                int64_t*, int64_t, int, float*, float*, float*, float*, float*, float*, int64_t, int, hipStream_t);
+hipError_t launch_sac_head_act(const float*, int, const float*, const float*, const float*, const float*, float, float, int, uint64_t, int64_t*, int64_t,
+                               float*, float*, float*, float*, float*, float*, int64_t, int, hipStream_t);
 }  // namespace mms
 
 struct mms_buffer {
@@ -511,6 +513,26 @@ __attribute__((visibility("default"))) int mms_ppo_heads_act(int device, const f
     }
     MMS_FREE(mms::launch_ppo_head_act(hidden, weight, bias, H, value, vhidden, vweight, vbias, VH, log_std, seed, counters, row_offset, reference_scale,
                                       actions_out, act_slot, logp_slot, value_slot, mu_slot, sigma_slot, N, A, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_sac_heads_act(int device, const float* hidden, int32_t H, const float* mu_weight,
+                                                             const float* mu_bias, const float* ls_weight, const float* ls_bias, float act_limit,
+                                                             float epsilon, int32_t deterministic, uint64_t seed, int64_t* counters,
+                                                             int64_t row_offset, float* actions_out, float* act_slot, float* logp_slot,
+                                                             float* u_slot, float* mu_slot, float* log_std_slot, int64_t N, int32_t A, void* s) {
+    MMS_DEV(device)
+    if (!hidden || !mu_weight || !mu_bias || !ls_weight || !ls_bias || (!deterministic && !counters) || N < 0 || A <= 0 || A > 128 || H <= 0 ||
+        (H % 64) != 0) {
+        g_create_error = "mms_sac_heads_act: bad arguments (A must be in 1..128, H a positive multiple of 64, counters required unless deterministic)";
+        return 1;
+    }
+    if (((uintptr_t)hidden | (uintptr_t)mu_weight | (uintptr_t)ls_weight) & 15) {
+        g_create_error = "mms_sac_heads_act: hidden and both weight matrices must be 16-byte aligned";
+        return 1;
+    }
+    MMS_FREE(mms::launch_sac_head_act(hidden, H, mu_weight, mu_bias, ls_weight, ls_bias, act_limit, epsilon, deterministic, seed, counters, row_offset,
+                                      actions_out, act_slot, logp_slot, u_slot, mu_slot, log_std_slot, N, A, (hipStream_t)s));
     return 0;
 }
 

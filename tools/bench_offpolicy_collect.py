@@ -7,18 +7,26 @@ Two variants of the same loop: `copies` (the wrapper's return values copied into
 `bound` (the step kernel writes next_obs / reward / done into the ring row `ReplayBuffer.slot()` names).  Each is timed
 eagerly and as a replayed hipGraph of one pass over a 16-row window of the ring.
 
-    python tools/bench_offpolicy_collect.py [--num-envs 8192] [--steps 512]
+`--algo sac` runs the same loop with SAC's actor (cfg/sac/config.yaml: 3 x 1024, ELU; stochastic act, sac.py:166: the hidden layers
+as mms_linear2_act launches, the squashed-Gaussian head as one mms_sac_heads_act launch) and also times the Q target's
+pi(o2) under no_grad with logp on an [8, N, W] gather (sac.py:374-376: batch_size 32 / nminibatches 4 = 8 ring rows), fused
+against the library path (torch's Linear / clamp / exp / randn / tanh / log chain) in the same process.
+
+    python tools/bench_offpolicy_collect.py [--algo ddpg|sac] [--num-envs 8192] [--steps 512]
 """
 import argparse
 import json
 import os
 import sys
 
+import numpy as np
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--algo", choices=("ddpg", "sac"), default="ddpg")
     ap.add_argument("--task", default="MultiIngenuity")
     ap.add_argument("--num-envs", type=int, default=8192)
     ap.add_argument("--steps", type=int, default=512)
@@ -33,12 +41,15 @@ def main():
     from massive_marl_benchmark_amd import spaces
     from massive_marl_benchmark_amd.algorithms.rl.ddpg.module import MLPActorCritic
     from massive_marl_benchmark_amd.algorithms.rl.ddpg.storage import ReplayBuffer
+    from massive_marl_benchmark_amd.algorithms.rl.sac.module import MLPActorCritic as SACActorCritic
     from massive_marl_benchmark_amd.engine import Engine
 
     N = args.num_envs
     torch.manual_seed(0)
     out = {"task": args.task, "num_envs": N, "replay_size": args.replay_size, "actor": "library" if args.library_actor else "mms_linear2_act",
            "env_spacing": "reference default" if args.env_spacing is None else args.env_spacing}
+    if args.algo == "sac":
+        out = {"algo": "sac", **out, "actor": "library" if args.library_actor else "mms_linear2_act + mms_sac_heads_act", "hidden": [1024, 1024, 1024]}
     from massive_marl_benchmark_amd.model import default_cfg
     cfg = None
     if args.env_spacing is not None:
@@ -47,10 +58,17 @@ def main():
     for variant in ("copies", "bound"):
         eng = Engine(args.task, cfg=cfg, num_envs=N, device=0, seed=0, clip_obs=5.0)
         W, AD = eng.obs_dim, eng.num_actions
-        ac = MLPActorCritic(spaces.Box(-np.inf * np.ones(W), np.inf * np.ones(W)), spaces.Box(-np.ones(AD), np.ones(AD)), 0.1, "cuda:0",
-                            hidden_sizes=[256, 256, 256]).cuda()                       # cfg/ddpg/config.yaml: hidden_nodes 256 x 3
-        if args.library_actor:
-            ac.pi.forward = lambda obs, _pi=ac.pi: _pi.act_limit * _pi.pi(obs)
+        if args.algo == "sac":
+            ac = SACActorCritic(spaces.Box(-np.inf * np.ones(W), np.inf * np.ones(W)), spaces.Box(-np.ones(AD), np.ones(AD)),
+                                hidden_sizes=[1024, 1024, 1024]).cuda()                # cfg/sac/config.yaml: hidden_nodes 1024 x 3, ELU
+            if args.library_actor:
+                ac.pi.forward = ac.pi.torch_forward
+            ac.pi.reserve_counters(8 * N, torch.device("cuda:0"))     # the graph below pins them; pi(o2) later runs on 8 N rows
+        else:
+            ac = MLPActorCritic(spaces.Box(-np.inf * np.ones(W), np.inf * np.ones(W)), spaces.Box(-np.ones(AD), np.ones(AD)), 0.1, "cuda:0",
+                                hidden_sizes=[256, 256, 256]).cuda()                   # cfg/ddpg/config.yaml: hidden_nodes 256 x 3
+            if args.library_actor:
+                ac.pi.forward = lambda obs, _pi=ac.pi: _pi.act_limit * _pi.pi(obs)
         buf = ReplayBuffer(N, args.replay_size, 64, 8, (W,), (0,), (AD,), "cuda:0")
         states = torch.zeros(N, 0, device="cuda")
         act_buf, rew, done, obs_c = eng.tensor("actions"), eng.tensor("rew"), eng.tensor("reset"), eng.tensor("obs_clipped")
@@ -108,8 +126,40 @@ def main():
                         "graph_ms_per_step": graph_ms, "graph_env_steps_per_s": N / (graph_ms * 1e-3), "finite": finite}
         eng.bind_obs_out(None); eng.bind_rollout_out(None, None)
         del graph
+        if args.algo == "sac" and variant == "bound":
+            out["target_pi"] = time_target_pi(ac, buf, args.steps)
         eng.close()
     print(json.dumps(out), flush=True)
+
+
+def time_target_pi(ac, buf, steps):
+    """pi(o2) under no_grad with logp on an [8, N, W] gather of the ring (sac.py:374-376), fused and library alternating (5 rounds)."""
+    import torch
+    pi = ac.pi
+    o2 = buf.next_observations[torch.arange(8, device=buf.next_observations.device)]
+    paths = {"fused": lambda x: type(pi).forward(pi, x), "library": pi.torch_forward}     # (whatever --library-actor set for the loop)
+    res = {k: [] for k in paths}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    reps = max(8, steps // 8)
+    with torch.no_grad():
+        for f in paths.values():
+            for _ in range(4):
+                a2, logp = f(o2)
+        torch.cuda.synchronize()
+        for _ in range(5):
+            for k, f in paths.items():
+                e0.record()
+                for _ in range(reps):
+                    a2, logp = f(o2)
+                e1.record(); e1.synchronize()
+                res[k].append(e0.elapsed_time(e1) / reps)
+    rows = o2.shape[0] * o2.shape[1]
+    out = {"shape": list(o2.shape), "rows": rows, "calls_per_round": reps, "finite": bool(torch.isfinite(a2).all() and torch.isfinite(logp).all())}
+    for k, v in res.items():
+        out[k + "_ms_per_call"] = float(np.median(v))
+        out[k + "_ms_rounds"] = v
+    out["speedup"] = out["library_ms_per_call"] / out["fused_ms_per_call"]
+    return out
 
 
 if __name__ == "__main__":
