@@ -38,6 +38,10 @@
  *     (algorithms/marl/actor_critic.py:43-69, 137-155; runner.py:186-216)  mms_row_stats_group, mms_marl_heads_act
  *   SquashedGaussianMLPActor heads + rsample + log-probability          mms_sac_heads_act
  *     (algorithms/rl/sac/module.py:23-61; sac.py:166, 374-376)
+ *   TRPO actor backward: torch.autograd.grad of the surrogate loss      mms_mlp_grad
+ *     (algorithms/rl/trpo/trpo.py:290) and the create_graph=True
+ *     gradient of the KL (:427)
+ *   TRPO double backward of the KL's Hessian-vector product (:431)      mms_mlp_grad_rop
  *
  * Ownership: the engine owns every buffer it reports through mms_get_tensor for the lifetime of the
  * handle; callers wrap them as NON-owning views and must keep the handle alive while any view exists.
@@ -496,6 +500,33 @@ int mms_marl_heads_finish(int device, int32_t groups, int64_t M, int32_t slots, 
                           const float* const* hs, const float* const* hc, const int32_t* A, const float* const* std, float* const* out,
                           float* const* logp, const int32_t* out_pitch, int64_t* const* counters, uint64_t seed, int64_t row_offset, float eps,
                           void* hip_stream);
+
+/* ---- TRPO curvature products: backward and R-op of an ELU MLP (csrc/trpo_kernels.hip) ----------------------------------------------
+ * The network: L = layers >= 2 Linear layers, ELU (alpha 1) after every one but the last; dims[0..L] the widths (dims[0] = input,
+ * dims[L] = output), W_l [dims[l], dims[l-1]] in torch's Linear layout; x [M, dims[0]] and the hidden activations h[l-1] = h_l
+ * [M, dims[l]], l = 1..L-1, as the forward left them; all f32, contiguous; 1 <= M <= 2097024.  ELU's derivatives are read from h: f' = f'' = h + 1 where
+ * h <= 0, f' = 1 and f'' = 0 where h > 0.  Every product runs on the split-operand GEMM core (fp32 operands as three bf16 planes,
+ * fp32 accumulation; P32 above), weight gradients as deterministic row-split sums (no atomics: results are bit-identical run to run).
+ * workspace: caller-owned device memory, 256-byte aligned; workspace == NULL stores the bytes needed in *ws_bytes and returns 0
+ * (the CPU build needs none: 0, and runs on any non-NULL workspace).  Otherwise *ws_bytes is the size given and a smaller one is an
+ * error.
+ *
+ * mms_mlp_grad: J^T g of mu = MLP(x) for g [M, dims[L]]: d_L = g, dW_l = d_l^T h_{l-1}, db_l = sum over rows of d_l,
+ *   e_{l-1} = d_l W_l, d_{l-1} = e_{l-1} f'(h_{l-1}).  dw[l-1] [dims[l], dims[l-1]], db[l-1] [dims[l]].  d_out / e_out (NULL: not kept)
+ *   receive d_l and e_l [M, dims[l]] for l = 1..L-1 at index l-1: what mms_mlp_grad_rop reads. */
+int mms_mlp_grad(int device, int32_t layers, int64_t M, const int32_t* dims, const float* x, const float* const* h, const float* const* w,
+                 const float* g, float* const* dw, float* const* db, float* const* d_out, float* const* e_out, void* workspace,
+                 int64_t* ws_bytes, void* hip_stream);
+
+/* mms_mlp_grad_rop: the directional derivative (Pearlmutter's R-op) of mms_mlp_grad along the parameters' direction (V_l, c_l)
+ * (v[l-1], c[l-1] shaped like W_l, b_l) with g held fixed: rmu [M, dims[L]] = J v = R{mu}, and rdw[l-1] / rdb[l-1] = R{dW_l} / R{db_l}
+ * = sum over rows of g . (d2 mu / d theta2) v, the curvature term of a Hessian-vector product (the Gauss-Newton term is the caller's:
+ * J^T of the loss curvature times rmu).  d, e: mms_mlp_grad's d_out / e_out for the same g.
+ *   Ra_l = Rh_{l-1} W_l^T + h_{l-1} V_l^T + c_l, Rh_l = f'(h_l) Ra_l (Rh_0 = 0); Rd_L = 0,
+ *   R{dW_l} = Rd_l^T h_{l-1} + d_l^T Rh_{l-1}, R{db_l} = sum Rd_l, Rd_{l-1} = (Rd_l W_l + d_l V_l) f'(h_{l-1}) + e_{l-1} f''(h_{l-1}) Ra_{l-1} */
+int mms_mlp_grad_rop(int device, int32_t layers, int64_t M, const int32_t* dims, const float* x, const float* const* h, const float* const* w,
+                     const float* const* v, const float* const* c, const float* g, const float* const* d, const float* const* e, float* rmu,
+                     float* const* rdw, float* const* rdb, void* workspace, int64_t* ws_bytes, void* hip_stream);
 
 const char* mms_last_error(mms_handle h);   /* h may be NULL: error of the last failed mms_create */
 int mms_abi_version(void);

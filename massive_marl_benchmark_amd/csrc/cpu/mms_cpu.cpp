@@ -1159,3 +1159,151 @@ MMS_API int mms_marl_heads_act(int device, int32_t groups, int64_t M, int32_t H,
     }
     return 0;
 }
+
+// ---- TRPO curvature products (csrc/trpo_kernels.hip): backward and R-op of an ELU MLP as plain loops -----------------------------------
+// Products accumulate in double and round once (a second opinion for the HIP build, not a bit-equal copy of it).  No workspace.
+static inline double elu_d1(float h) { return h > 0.f ? 1.0 : (double)h + 1.0; }
+static inline double elu_d2(float h) { return h > 0.f ? 0.0 : (double)h + 1.0; }
+
+// out [R, C] = A^T B with A [M, R], B [M, C] (+ out when acc): the contraction over rows
+static void mlp_tn(int64_t M, int R, int C, const float* A, const float* B, float* out, bool acc) {
+#pragma omp parallel for schedule(static)
+    for (int r = 0; r < R; r++)
+        for (int c = 0; c < C; c++) {
+            double s = acc ? out[(int64_t)r * C + c] : 0.0;
+            for (int64_t m = 0; m < M; m++) s += (double)A[m * R + r] * B[m * C + c];
+            out[(int64_t)r * C + c] = (float)s;
+        }
+}
+static void mlp_colsum(int64_t M, int R, const float* A, float* out) {
+    for (int r = 0; r < R; r++) {
+        double s = 0.0;
+        for (int64_t m = 0; m < M; m++) s += A[m * R + r];
+        out[r] = (float)s;
+    }
+}
+// out [M, K] = sum over terms of D_t W_t (D_t [M, N], W_t [N, K]), in double, then rounded
+static void mlp_nn(int64_t M, int N, int K, int terms, const float* const* D, const float* const* W, double* out) {
+#pragma omp parallel for schedule(static)
+    for (int64_t m = 0; m < M; m++)
+        for (int k = 0; k < K; k++) {
+            double s = 0.0;
+            for (int t = 0; t < terms; t++)
+                for (int n = 0; n < N; n++) s += (double)D[t][m * N + n] * W[t][(int64_t)n * K + k];
+            out[m * K + k] = s;
+        }
+}
+
+static int mlp_check(const char* who, int32_t L, int64_t M, const int32_t* dims, int64_t* ws_bytes) {
+    bool ok = dims && ws_bytes && L >= 2 && L <= 8 && M >= 1 && M <= 65535 * 32 / 128 * 128;     // the HIP build's row limit
+    for (int l = 0; ok && l <= L; l++) ok = dims[l] >= 1 && dims[l] <= 65536;
+    if (!ok) {
+        g_error = std::string(who) + ": bad arguments (2 <= layers <= 8, 1 <= M <= 2097024, dims[0..layers] in 1..65536, ws_bytes required)";
+        return 1;
+    }
+    return 0;
+}
+static bool mlp_all(int n, const float* const* p) {
+    if (!p) return false;
+    for (int i = 0; i < n; i++)
+        if (!p[i]) return false;
+    return true;
+}
+
+MMS_API int mms_mlp_grad(int device, int32_t L, int64_t M, const int32_t* dims, const float* x, const float* const* h, const float* const* w,
+                         const float* g, float* const* dw, float* const* db, float* const* d_out, float* const* e_out, void* workspace,
+                         int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    if (mlp_check("mms_mlp_grad", L, M, dims, ws_bytes)) return 1;
+    if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query (callers pass any non-NULL workspace to run)
+    if (!x || !g || !mlp_all(L - 1, h) || !mlp_all(L, w) || !mlp_all(L, dw) || !mlp_all(L, db) || (d_out && !mlp_all(L - 1, d_out)) ||
+        (e_out && !mlp_all(L - 1, e_out))) {
+        g_error = "mms_mlp_grad: null pointer (x, g, h[layers-1], w / dw / db[layers]; d_out / e_out all or none)";
+        return 1;
+    }
+    std::vector<float> dcur(g, g + M * dims[L]), dnext;
+    std::vector<double> e;
+    for (int l = L; l >= 1; l--) {
+        const float* hin = l == 1 ? x : h[l - 2];
+        mlp_tn(M, dims[l], dims[l - 1], dcur.data(), hin, dw[l - 1], false);
+        mlp_colsum(M, dims[l], dcur.data(), db[l - 1]);
+        if (l > 1) {
+            const int K = dims[l - 1];
+            e.assign((size_t)M * K, 0.0);
+            const float* D[1] = {dcur.data()};
+            const float* W[1] = {w[l - 1]};
+            mlp_nn(M, dims[l], K, 1, D, W, e.data());
+            dnext.assign((size_t)M * K, 0.f);
+            for (int64_t i = 0; i < M * K; i++) {
+                const float ev = (float)e[i];
+                if (e_out) e_out[l - 2][i] = ev;
+                dnext[i] = (float)((double)ev * elu_d1(h[l - 2][i]));
+                if (d_out) d_out[l - 2][i] = dnext[i];
+            }
+            dcur.swap(dnext);
+        }
+    }
+    return 0;
+}
+
+MMS_API int mms_mlp_grad_rop(int device, int32_t L, int64_t M, const int32_t* dims, const float* x, const float* const* h, const float* const* w,
+                             const float* const* v, const float* const* c, const float* g, const float* const* d, const float* const* e,
+                             float* rmu, float* const* rdw, float* const* rdb, void* workspace, int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    if (mlp_check("mms_mlp_grad_rop", L, M, dims, ws_bytes)) return 1;
+    if (!workspace) { *ws_bytes = 0; return 0; }
+    if (!x || !g || !rmu || !mlp_all(L - 1, h) || !mlp_all(L, w) || !mlp_all(L, v) || !mlp_all(L, c) || !mlp_all(L - 1, d) ||
+        !mlp_all(L - 1, e) || !mlp_all(L, rdw) || !mlp_all(L, rdb)) {
+        g_error = "mms_mlp_grad_rop: null pointer (x, g, rmu, h / d / e[layers-1], w / v / c / rdw / rdb[layers])";
+        return 1;
+    }
+    // R-forward: Ra_l = Rh_{l-1} W_l^T + h_{l-1} V_l^T + c_l, Rh_l = f'(h_l) Ra_l
+    std::vector<std::vector<float>> Ra(L + 1), Rh(L);
+    for (int l = 1; l <= L; l++) {
+        const int N = dims[l], K = dims[l - 1];
+        const float* hin = l == 1 ? x : h[l - 2];
+        Ra[l].assign((size_t)M * N, 0.f);
+#pragma omp parallel for schedule(static)
+        for (int64_t m = 0; m < M; m++)
+            for (int n = 0; n < N; n++) {
+                double s = c[l - 1][n];
+                for (int k = 0; k < K; k++) {
+                    s += (double)hin[m * K + k] * v[l - 1][(int64_t)n * K + k];
+                    if (l > 1) s += (double)Rh[l - 1][m * K + k] * w[l - 1][(int64_t)n * K + k];
+                }
+                Ra[l][m * N + n] = (float)s;
+            }
+        if (l < L) {
+            Rh[l].assign((size_t)M * N, 0.f);
+            for (int64_t i = 0; i < M * N; i++) Rh[l][i] = (float)(elu_d1(h[l - 1][i]) * Ra[l][i]);
+        }
+    }
+    memcpy(rmu, Ra[L].data(), sizeof(float) * M * dims[L]);
+    // R-backward
+    std::vector<float> Rd;                                        // Rd_l (empty: Rd_L = 0)
+    std::vector<double> T;
+    for (int l = L; l >= 1; l--) {
+        const int N = dims[l], K = dims[l - 1];
+        const float* dl = l == L ? g : d[l - 1];
+        const float* hin = l == 1 ? x : h[l - 2];
+        std::vector<float> acc((size_t)N * K, 0.f);
+        if (l < L) mlp_tn(M, N, K, Rd.data(), hin, acc.data(), false);
+        if (l >= 2) mlp_tn(M, N, K, dl, Rh[l - 1].data(), acc.data(), l < L);
+        memcpy(rdw[l - 1], acc.data(), sizeof(float) * N * K);
+        if (l < L) mlp_colsum(M, N, Rd.data(), rdb[l - 1]);
+        else memset(rdb[l - 1], 0, sizeof(float) * N);
+        if (l >= 2) {
+            T.assign((size_t)M * K, 0.0);
+            const float* D[2] = {dl, Rd.data()};
+            const float* W[2] = {v[l - 1], w[l - 1]};
+            mlp_nn(M, N, K, l < L ? 2 : 1, D, W, T.data());
+            std::vector<float> nd((size_t)M * K);
+            for (int64_t i = 0; i < M * K; i++) {
+                const float hv = h[l - 2][i];
+                nd[i] = (float)(T[i] * elu_d1(hv) + (double)e[l - 2][i] * elu_d2(hv) * Ra[l - 1][i]);
+            }
+            Rd.swap(nd);
+        }
+    }
+    return 0;
+}

@@ -13,6 +13,7 @@
 #include "../../include/mms.h"
 #include "policy_args.h"
 #include "step_args.h"
+#include "trpo_plan.h"
 
 namespace mms {
 hipError_t launch_step(const StepArgs& a, int task, hipStream_t stream);
@@ -28,6 +29,7 @@ hipError_t launch_ppo_head_act(const float*, const float*, const float*, int, co
                                int64_t*, int64_t, int, float*, float*, float*, float*, float*, float*, int64_t, int, hipStream_t);
 hipError_t launch_sac_head_act(const float*, int, const float*, const float*, const float*, const float*, float, float, int, uint64_t, int64_t*, int64_t,
                                float*, float*, float*, float*, float*, float*, int64_t, int, hipStream_t);
+struct MlpPlan;
 }  // namespace mms
 
 struct mms_buffer {
@@ -960,6 +962,68 @@ __attribute__((visibility("default"))) int mms_marl_heads_act(int device, int32_
     }
     a.seed = seed; a.M = M; a.row_offset = row_offset; a.H = H; a.eps = eps;
     MMS_FREE(mms::launch_marl_heads(a, groups, (hipStream_t)s));
+    return 0;
+}
+
+// ---- TRPO curvature products (trpo_kernels.hip) -----------------------------------------------------------------------------------
+
+static bool mlp_ptrs_ok(int n, const float* const* p) {
+    if (!p) return false;
+    for (int i = 0; i < n; i++)
+        if (!p[i]) return false;
+    return true;
+}
+
+// shared checks of both entries: shapes, the workspace query / size; returns 1 (error set), 0 (go on) or 2 (query answered)
+static int mlp_prologue(const char* who, int32_t layers, int64_t M, const int32_t* dims, bool rop, void* workspace, int64_t* ws_bytes,
+                        mms::MlpPlan* P) {
+    if (!dims || !ws_bytes || !mms::mlp_plan(layers, M, dims, rop, P)) {
+        g_create_error = std::string(who) + ": bad arguments (2 <= layers <= 8, 1 <= M <= " + std::to_string(mms::kMlpMaxRows) + ", dims[0..layers] in 1..65536, ws_bytes required)";
+        return 1;
+    }
+    if (!workspace) {
+        *ws_bytes = (int64_t)P->total;
+        return 2;
+    }
+    if (*ws_bytes < (int64_t)P->total) {
+        g_create_error = std::string(who) + ": workspace too small (" + std::to_string(*ws_bytes) + " bytes, needs " + std::to_string(P->total) + ")";
+        return 1;
+    }
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) { g_create_error = std::string(who) + ": workspace must be 256-byte aligned"; return 1; }
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_mlp_grad(int device, int32_t layers, int64_t M, const int32_t* dims, const float* x, const float* const* h,
+                                                        const float* const* w, const float* g, float* const* dw, float* const* db,
+                                                        float* const* d_out, float* const* e_out, void* workspace, int64_t* ws_bytes, void* s) {
+    MMS_DEV(device)
+    mms::MlpPlan P;
+    const int pr = mlp_prologue("mms_mlp_grad", layers, M, dims, false, workspace, ws_bytes, &P);
+    if (pr != 0) return pr == 2 ? 0 : 1;
+    if (!x || !g || !mlp_ptrs_ok(layers - 1, h) || !mlp_ptrs_ok(layers, w) || !mlp_ptrs_ok(layers, dw) || !mlp_ptrs_ok(layers, db) ||
+        (d_out && !mlp_ptrs_ok(layers - 1, d_out)) || (e_out && !mlp_ptrs_ok(layers - 1, e_out))) {
+        g_create_error = "mms_mlp_grad: null pointer (x, g, h[layers-1], w / dw / db[layers]; d_out / e_out all or none)";
+        return 1;
+    }
+    MMS_FREE(mms::mlp_grad(P, x, h, w, g, dw, db, d_out, e_out, static_cast<uint8_t*>(workspace), (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_mlp_grad_rop(int device, int32_t layers, int64_t M, const int32_t* dims, const float* x,
+                                                            const float* const* h, const float* const* w, const float* const* v,
+                                                            const float* const* c, const float* g, const float* const* d, const float* const* e,
+                                                            float* rmu, float* const* rdw, float* const* rdb, void* workspace, int64_t* ws_bytes,
+                                                            void* s) {
+    MMS_DEV(device)
+    mms::MlpPlan P;
+    const int pr = mlp_prologue("mms_mlp_grad_rop", layers, M, dims, true, workspace, ws_bytes, &P);
+    if (pr != 0) return pr == 2 ? 0 : 1;
+    if (!x || !g || !rmu || !mlp_ptrs_ok(layers - 1, h) || !mlp_ptrs_ok(layers, w) || !mlp_ptrs_ok(layers, v) || !mlp_ptrs_ok(layers, c) ||
+        !mlp_ptrs_ok(layers - 1, d) || !mlp_ptrs_ok(layers - 1, e) || !mlp_ptrs_ok(layers, rdw) || !mlp_ptrs_ok(layers, rdb)) {
+        g_create_error = "mms_mlp_grad_rop: null pointer (x, g, rmu, h / d / e[layers-1], w / v / c / rdw / rdb[layers])";
+        return 1;
+    }
+    MMS_FREE(mms::mlp_grad_rop(P, x, h, w, v, c, g, d, e, rmu, rdw, rdb, static_cast<uint8_t*>(workspace), (hipStream_t)s));
     return 0;
 }
 
