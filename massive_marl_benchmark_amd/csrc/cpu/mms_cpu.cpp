@@ -16,63 +16,15 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/mms.h"
+#include "../mms_host.h"
 #include "../rollout_lane.h"
 #include "../sac_lane.h"
 #include "lane_step.h"
 
 #define MMS_API extern "C" __attribute__((visibility("default")))
 
-struct mms_buffer {
-    const char* name;
-    void* ptr;
-    int64_t shape[4];
-    int ndim;
-    int dtype;
-    size_t bytes;
-    int64_t row_bytes;
-};
+struct mms_engine : mms_host_state {};
 
-struct mms_engine {
-    mms_config cfg;
-    int actors = 0, dofs = 0, num_actions = 0, obs_dim = 0, prev_dim = 0;
-    float* obs_out = nullptr;
-    void* obs_planes = nullptr;
-    float obs_planes_scale = 1.f;
-    const float* actions_in = nullptr;
-    int head_on = 0;                        // mms_bind_policy_head: consumed by the next mms_step
-    mms_policy_head head{};
-    int write_raw_obs = 1, write_clipped_obs = 1, dr_enabled = 0;
-    float* rew_out = nullptr;
-    uint8_t* done_out = nullptr;
-    std::vector<mms_buffer> bufs;
-    std::string err;
-};
-
-static std::string g_error;
-static size_t dtype_size(int dt) { return dt == MMS_F32 ? 4 : dt == MMS_I64 ? 8 : dt == MMS_I32 ? 4 : 1; }
-static int fail(mms_engine* e, const std::string& msg) {
-    if (e) e->err = msg; else g_error = msg;
-    return 1;
-}
-static mms_buffer* find(mms_engine* e, const char* name) {
-    for (auto& b : e->bufs)
-        if (!strcmp(b.name, name)) return &b;
-    return nullptr;
-}
-static void add_buffer(mms_engine* e, const char* name, int dtype, std::initializer_list<int64_t> shape) {
-    mms_buffer b{};
-    b.name = name;
-    b.dtype = dtype;
-    b.ndim = (int)shape.size();
-    size_t n = 1;
-    int i = 0;
-    for (int64_t s : shape) { b.shape[i++] = s; n *= (size_t)s; }
-    b.bytes = n * dtype_size(dtype);
-    b.row_bytes = (int64_t)(b.bytes / (size_t)e->cfg.num_envs);
-    b.ptr = calloc(b.bytes ? b.bytes : 16, 1);
-    e->bufs.push_back(b);
-}
 template <typename T> static T* buf(mms_engine* e, const char* name) { return (T*)find(e, name)->ptr; }
 
 MMS_API int mms_abi_version(void) { return MMS_ABI_VERSION; }
@@ -86,107 +38,19 @@ MMS_API int mms_destroy(mms_handle h) {
 }
 
 MMS_API int mms_create(const mms_config* cfg, mms_handle* out) {
-    if (!cfg || !out) return fail(nullptr, "mms_create: null argument");
-    if (cfg->abi_version != MMS_ABI_VERSION) return fail(nullptr, "mms_create: ABI version mismatch");
-    if (cfg->device != -1) return fail(nullptr, "mms_create: this is the CPU build of the engine (libmms_cpu.so); device must be -1");
-    if (cfg->num_envs <= 0 || cfg->num_agents <= 0) return fail(nullptr, "mms_create: num_envs and num_agents must be positive");
-    if (cfg->task == MMS_TASK_MULTI_INGENUITY && cfg->num_agents != 4) return fail(nullptr, "mms_create: MultiIngenuity has 4 helicopters per env");
-    if (cfg->task == MMS_TASK_ONE_ANT && cfg->num_agents != 1) return fail(nullptr, "mms_create: OneAnt has one ant per env");
-    if (cfg->task == MMS_TASK_MULTI_ANT_CIRCLE && cfg->num_agents != 2) return fail(nullptr, "mms_create: MultiAntCircle has two ants per env");
-    if (cfg->task != MMS_TASK_MULTI_INGENUITY && cfg->num_agents > 126) return fail(nullptr, "mms_create: at most 126 ants per env");
     mms_engine* e = new mms_engine();
-    e->cfg = *cfg;
-    const int N = cfg->num_envs, A = cfg->num_agents;
-    if (cfg->task == MMS_TASK_TEN_ANT) { e->actors = A + 1; e->dofs = 8 * A; e->num_actions = 8 * A; e->obs_dim = 38 * A + 8; e->prev_dim = 4 * A + 2; }
-    else if (cfg->task == MMS_TASK_ONE_ANT) { e->actors = 2; e->dofs = 8; e->num_actions = 8; e->obs_dim = 60; e->prev_dim = 6; }
-    else if (cfg->task == MMS_TASK_MULTI_ANT_CIRCLE) { e->actors = A + 1; e->dofs = 8 * A; e->num_actions = 8 * A; e->obs_dim = 38 * A; e->prev_dim = 2 * A; }
-    else if (cfg->task == MMS_TASK_MULTI_INGENUITY) { e->actors = A; e->dofs = 4 * A; e->num_actions = 6 * A; e->obs_dim = 13 * A; e->prev_dim = 3 * A; }
-    else { delete e; return fail(nullptr, "mms_create: unknown task"); }
-    add_buffer(e, "actions", MMS_F32, {N, e->num_actions});
-    add_buffer(e, "obs", MMS_F32, {N, e->obs_dim});
-    add_buffer(e, "obs_clipped", MMS_F32, {N, e->obs_dim});
-    add_buffer(e, "rew", MMS_F32, {N});
-    add_buffer(e, "reset", MMS_I64, {N});
-    add_buffer(e, "progress", MMS_I64, {N});
-    add_buffer(e, "reset_count", MMS_I64, {N});
-    add_buffer(e, "root_states", MMS_F32, {(int64_t)N * e->actors, 13});
-    add_buffer(e, "initial_root_states", MMS_F32, {(int64_t)N * e->actors, 13});
-    add_buffer(e, "dof_state", MMS_F32, {(int64_t)N * e->dofs, 2});
-    add_buffer(e, "env_origin", MMS_F32, {N, 3});
-    add_buffer(e, "prev", MMS_F32, {N, e->prev_dim});
-    add_buffer(e, "reset_noise", MMS_F32, {N, 16});
-    add_buffer(e, "foot_sensors", MMS_F32, {(int64_t)N * A, 24});
-    add_buffer(e, "dr_params", MMS_F32, {(int64_t)N * A, MMS_DR_FLOATS});
-    // construction-time scene: the same as the HIP build's mms_create (ten_ant.py:339-358,494-495; one_ant.py:234;
-    // multi_ingenuity.py:157-164), env grid per SURVEY.md B.2
-    float* init = buf<float>(e, "initial_root_states");
-    float* origin = buf<float>(e, "env_origin");
-    float* prev = buf<float>(e, "prev");
-    int64_t npr = (int64_t)sqrt((double)cfg->total_envs);
-    if (npr < 1) npr = 1;
-    for (int i = 0; i < N; i++) {
-        int64_t gi = cfg->env_offset + i;
-        origin[3 * (size_t)i + 0] = (float)(gi % npr) * 2.f * cfg->env_spacing;
-        origin[3 * (size_t)i + 1] = (float)(gi / npr) * 2.f * cfg->env_spacing;
-        float* r = init + (size_t)i * e->actors * 13;
-        for (int k = 0; k < e->actors; k++) r[13 * k + 6] = 1.f;
-        if (cfg->task != MMS_TASK_MULTI_INGENUITY) {
-            for (int k = 0; k < A; k++) {
-                float off = (A == 1) ? 0.f : (1.5f + 3.f * (float)(k / 2)) * ((k % 2 == 0) ? -1.f : 1.f);
-                r[13 * k + 0] = cfg->ant_start_x; r[13 * k + 1] = off; r[13 * k + 2] = cfg->ant_start_z;
-                if (cfg->task == MMS_TASK_MULTI_ANT_CIRCLE) {                       // multi_ant_circle.py:216-219: (3, 0, 1) and (-3, 0, 1)
-                    r[13 * k + 0] = (k % 2 == 0) ? cfg->ant_start_x : -cfg->ant_start_x; r[13 * k + 1] = 0.f;
-                }
-            }
-            for (int j = 0; j < 3; j++) r[13 * A + j] = cfg->box_start[j];
-        } else {
-            static const float hy[4] = {2.f, -2.f, 6.f, -6.f};
-            for (int k = 0; k < A; k++) { r[13 * k + 0] = 0.f; r[13 * k + 1] = hy[k % 4]; r[13 * k + 2] = 1.f; }
-        }
-        // caches start as the construction-time poses in the global frame (ten_ant.py:870-882, one_ant.py:410-411)
-        const float* o = origin + 3 * (size_t)i;
-        float* pv = prev + (size_t)i * e->prev_dim;
-        if (cfg->task == MMS_TASK_TEN_ANT) {
-            const float* b = r + 13 * A;
-            float bx = b[0] + o[0], by = b[1] + o[1];
-            float ang = atanf((2.f * b[6] * b[5]) / (1.f - 2.f * b[5] * b[5]));
-            float sv = sinf(ang), cv = -cosf(ang);
-            for (int k = 0; k < A; k++) {
-                pv[2 * k] = r[13 * k] + o[0]; pv[2 * k + 1] = r[13 * k + 1] + o[1];
-                float off = 1.5f + 3.0f * (float)(k / 2);
-                pv[2 * A + 2 * k] = (k % 2 == 0) ? bx + off * sv : bx - off * sv;
-                pv[2 * A + 2 * k + 1] = (k % 2 == 0) ? by + off * cv : by - off * cv;
-            }
-            pv[4 * A] = bx; pv[4 * A + 1] = by;
-        } else if (cfg->task == MMS_TASK_ONE_ANT) {
-            pv[0] = r[0] + o[0]; pv[1] = r[1] + o[1]; pv[2] = r[13] + o[0]; pv[3] = r[14] + o[1];
-            pv[4] = -4.f / cfg->dt; pv[5] = -4.f / cfg->dt;
-        } else if (cfg->task == MMS_TASK_MULTI_ANT_CIRCLE) {
-            for (int k = 0; k < A; k++) { pv[2 * k] = r[13 * k] + o[0]; pv[2 * k + 1] = r[13 * k + 1] + o[1]; }   // multi_ant_circle.py:367-368
-        }
-    }
-    memcpy(buf<float>(e, "root_states"), init, find(e, "root_states")->bytes);
-    int64_t* reset = buf<int64_t>(e, "reset");
-    for (int i = 0; i < N; i++) reset[i] = 1;                                     // base_task.py:62-63
-    float* dr = buf<float>(e, "dr_params");
-    for (size_t k = 0; k < (size_t)N * A; k++)
-        for (int j = 0; j < 17; j++) dr[k * MMS_DR_FLOATS + j] = 1.f;            // nominal: scales 1, limit offsets 0
+    std::string bad = engine_init(e, cfg, out);
+    if (bad.empty() && cfg->device != -1) bad = "mms_create: this is the CPU build of the engine (libmms_cpu.so); device must be -1";
+    if (!bad.empty()) { delete e; return fail(nullptr, bad); }
+    e->bufs = buffer_table(*e);
+    for (auto& b : e->bufs) b.ptr = calloc(b.bytes ? b.bytes : 16, 1);
+    fill_scene(*e, buf<float>(e, "initial_root_states"), buf<float>(e, "env_origin"), buf<float>(e, "prev"), buf<int64_t>(e, "reset"), buf<float>(e, "dr_params"));
+    memcpy(buf<float>(e, "root_states"), buf<float>(e, "initial_root_states"), find(e, "root_states")->bytes);
     *out = e;
     return 0;
 }
 
-MMS_API int mms_get_tensor(mms_handle h, const char* name, mms_tensor* out) {
-    if (!h || !name || !out) return fail(h, "mms_get_tensor: null argument");
-    mms_buffer* b = find(h, name);
-    if (!b) return fail(h, std::string("mms_get_tensor: unknown buffer '") + name + "'");
-    memset(out, 0, sizeof(*out));
-    out->ptr = b->ptr;
-    for (int i = 0; i < b->ndim; i++) out->shape[i] = b->shape[i];
-    out->ndim = b->ndim;
-    out->dtype = b->dtype;
-    out->device = -1;
-    return 0;
-}
+MMS_API int mms_get_tensor(mms_handle h, const char* name, mms_tensor* out) { return host_get_tensor(h, name, out); }
 
 MMS_API int mms_ppo_heads_act(int device, const float* hidden, const float* weight, const float* bias, int32_t H, const float* value,
                               const float* vhidden, const float* vweight, const float* vbias, int32_t VH, const float* log_std, uint64_t seed,
@@ -194,14 +58,14 @@ MMS_API int mms_ppo_heads_act(int device, const float* hidden, const float* weig
                               float* logp_slot, float* value_slot, float* mu_slot, float* sigma_slot, int64_t N, int32_t A, void*);
 
 static int do_step(mms_handle h, int physics) {
-    if (!h) return fail(nullptr, "mms_step: null handle");
+    if (null_handle(h, "mms_step")) return 1;
     const float* head_actions = nullptr;
     if (physics && h->head_on) {
         // the fused policy head (mms_bind_policy_head): on the host the heads operator runs in front of the step, into the action tensor
         // the step then reads -- the same values as the two calls made separately
         const mms_policy_head& p = h->head;
         float* dst = p.actions_out ? p.actions_out : buf<float>(h, "actions");
-        h->head_on = 0;
+        h->head_on = false;
         // (with the tiled copy of the actor's last layer bound, THAT is what is read -- as on the device; element
         //  ((ct (H / 4) + k / 4) 16 + i) 4 + k % 4 = weight[16 ct + i][k] -- so a stale or mis-laid copy shows up in the host tests too)
         std::vector<float> untiled;
@@ -235,80 +99,29 @@ MMS_API int mms_step(mms_handle h, void*) { return do_step(h, 1); }
 MMS_API int mms_post_step(mms_handle h, void*) { return do_step(h, 0); }
 
 MMS_API int mms_reset_all(mms_handle h, void*) {
-    if (!h) return fail(nullptr, "mms_reset_all: null handle");
+    if (null_handle(h, "mms_reset_all")) return 1;
     int64_t* r = buf<int64_t>(h, "reset");
     for (int i = 0; i < h->cfg.num_envs; i++) r[i] = 1;
     return 0;
 }
 
 MMS_API int mms_set_state(mms_handle h, const char* name, const void* src, int, const int64_t* env_ids, int64_t n, void*) {
-    if (!h || !name || !src) return fail(h, "mms_set_state: null argument");
-    mms_buffer* b = find(h, name);
-    if (!b) return fail(h, std::string("mms_set_state: unknown buffer '") + name + "'");
+    mms_buffer* b = nullptr;
+    if (host_set_state_check(h, name, src, env_ids, n, &b)) return 1;
     if (!env_ids) { memcpy(b->ptr, src, b->bytes); return 0; }
-    if (b->row_bytes <= 0) return fail(h, "mms_set_state: buffer is not per-env");
-    if (n < 0) return fail(h, "mms_set_state: negative row count");
-    for (int64_t i = 0; i < n; i++)                          // all ids are checked before anything is written
-        if (env_ids[i] < 0 || env_ids[i] >= h->cfg.num_envs) return fail(h, "mms_set_state: env id out of range");
     for (int64_t i = 0; i < n; i++) memcpy((char*)b->ptr + env_ids[i] * b->row_bytes, (const char*)src + i * b->row_bytes, (size_t)b->row_bytes);
     return 0;
 }
 
-MMS_API int mms_bind_obs_out(mms_handle h, void* dst) {
-    if (!h) return fail(nullptr, "mms_bind_obs_out: null handle");
-    h->obs_out = (float*)dst;
-    return 0;
-}
-MMS_API int mms_bind_obs_planes16(mms_handle h, void* planes, float scale) {
-    if (!h) return fail(nullptr, "mms_bind_obs_planes16: null handle");
-    if (!planes) { h->obs_planes = nullptr; return 0; }
-    if (h->cfg.task == MMS_TASK_MULTI_INGENUITY) return fail(h, "mms_bind_obs_planes16: not for the helicopter task (its policies' layers are 256 wide: exact-fp32 kernel)");
-    int e = 0;
-    if (!(scale > 0.f) || frexpf(scale, &e) != 0.5f) return fail(h, "mms_bind_obs_planes16: the scale must be a power of two");
-    if (!(h->cfg.clip_obs * scale <= 16384.f)) return fail(h, "mms_bind_obs_planes16: clip_observations x scale must not exceed 2^14 (fp16 planes)");
-    h->obs_planes = planes;
-    h->obs_planes_scale = scale;
-    return 0;
-}
-MMS_API int mms_bind_actions(mms_handle h, const float* src) {
-    if (!h) return fail(nullptr, "mms_bind_actions: null handle");
-    h->actions_in = src;
-    return 0;
-}
+MMS_API int mms_bind_obs_out(mms_handle h, void* dst) { return host_bind_obs_out(h, dst); }
+MMS_API int mms_bind_obs_planes16(mms_handle h, void* planes, float scale) { return host_bind_obs_planes16(h, planes, scale); }
+MMS_API int mms_bind_actions(mms_handle h, const float* src) { return host_bind_actions(h, src); }
+MMS_API int mms_set_dr(mms_handle h, int32_t enable) { return host_set_dr(h, enable); }
+MMS_API int mms_set_obs_outputs(mms_handle h, int32_t raw, int32_t clipped) { return host_set_obs_outputs(h, raw, clipped); }
+MMS_API int mms_bind_rollout_out(mms_handle h, float* rew_out, uint8_t* done_out) { return host_bind_rollout_out(h, rew_out, done_out); }
 MMS_API int mms_bind_policy_head(mms_handle h, const mms_policy_head* head) {
-    if (!h) return fail(nullptr, "mms_bind_policy_head: null handle");
-    if (!head) { h->head_on = 0; return 0; }
-    if (h->dr_enabled || h->cfg.task != MMS_TASK_TEN_ANT || h->cfg.num_agents != 10 || h->cfg.num_envs % 16 != 0)
-        return fail(h, "mms_bind_policy_head: not available for this engine (needs the 16-envs-per-workgroup TenAnt layout: 10 ants, num_envs a multiple "
-                       "of 16 and >= 16 per CU, no physical DR) -- launch mms_ppo_heads_act instead");
-    if (!head->hidden || !head->weight || !head->bias || !head->vhidden || !head->vweight || !head->vbias || !head->log_std || !head->counters)
-        return fail(h, "mms_bind_policy_head: null pointer (hidden, weight, bias, vhidden, vweight, vbias, log_std, counters are required)");
-    if (head->A != 8 * h->cfg.num_agents || head->H <= 0 || head->H % 512 != 0 || head->VH <= 0 || head->VH % 4 != 0)
-        return fail(h, "mms_bind_policy_head: A must be 8 x num_agents, H a multiple of 512, VH a multiple of 4");
-    uintptr_t bits = reinterpret_cast<uintptr_t>(head->hidden) | reinterpret_cast<uintptr_t>(head->weight) | reinterpret_cast<uintptr_t>(head->vhidden) |
-                     reinterpret_cast<uintptr_t>(head->vweight) | reinterpret_cast<uintptr_t>(head->weight_tiles);
-    if ((bits & 15) != 0) return fail(h, "mms_bind_policy_head: hidden, weight, weight_tiles, vhidden, vweight must be 16-byte aligned");
-    h->head = *head;
-    h->head_on = 1;
-    return 0;
-}
-MMS_API int mms_set_dr(mms_handle h, int32_t enable) {
-    if (!h) return fail(nullptr, "mms_set_dr: null handle");
-    if (enable && h->cfg.task == MMS_TASK_MULTI_INGENUITY) return fail(h, "mms_set_dr: the helicopter task has no randomised physical parameters");
-    h->dr_enabled = enable != 0;
-    return 0;
-}
-MMS_API int mms_set_obs_outputs(mms_handle h, int32_t raw, int32_t clipped) {
-    if (!h) return fail(nullptr, "mms_set_obs_outputs: null handle");
-    h->write_raw_obs = raw != 0;
-    h->write_clipped_obs = clipped != 0;
-    return 0;
-}
-MMS_API int mms_bind_rollout_out(mms_handle h, float* rew_out, uint8_t* done_out) {
-    if (!h) return fail(nullptr, "mms_bind_rollout_out: null handle");
-    h->rew_out = rew_out;
-    h->done_out = done_out;
-    return 0;
+    // the heads operator runs in front of the host step wherever the engine has the shape of the device's fused layout
+    return host_bind_policy_head(h, head, h && h->cfg.task == MMS_TASK_TEN_ANT && h->cfg.num_agents == 10 && h->cfg.num_envs % 16 == 0);
 }
 
 // ---- rollout functions (device argument: -1) ---------------------------------------------------------------------------------
@@ -342,18 +155,14 @@ MMS_API int mms_adv_normalize(int device, float* advantages, const double* stats
 }
 MMS_API int mms_layer_clock_probe(int device, uint64_t* out, int32_t slots) {
     (void)device;
-    if (out && slots < 1) { g_error = "mms_layer_clock_probe: slots must be >= 1 with an output buffer"; return 1; }
-    if (out && (reinterpret_cast<uintptr_t>(out) & 7) != 0) { g_error = "mms_layer_clock_probe: the buffer must be 8-byte aligned"; return 1; }
+    if (refused(check_layer_clock_probe(out, slots))) return 1;
     return 0;                                     // (no shader clock on this build: nothing is stored)
 }
 
 MMS_API int mms_gae_ppo_normalized(int device, const float* rewards, const uint8_t* dones, const float* values, const float* last_values, float* returns,
                                    float* advantages, double* stats, int32_t T, int64_t N, float gamma, float lam, void*) {
     if (cpu_only(device)) return 1;
-    if (!rewards || !dones || !values || !last_values || !returns || !advantages || !stats || T < 1 || N < 1) {
-        g_error = "mms_gae_ppo_normalized: bad arguments (null pointer, T < 1 or N < 1)";
-        return 1;
-    }
+    if (refused(check_gae_ppo_normalized(rewards, dones, values, last_values, returns, advantages, stats, T, N))) return 1;
     if (mms_gae_ppo(device, rewards, dones, values, last_values, returns, advantages, stats, T, N, gamma, lam, nullptr)) return 1;
     return mms_adv_normalize(device, advantages, stats, (int64_t)T * N, nullptr);
 }
@@ -409,7 +218,7 @@ MMS_API int mms_ppo_act(int device, const float* mean, const float* value, const
                         int64_t row_offset, int32_t reference_scale, float* actions_out, float* act_slot, float* logp_slot, float* value_slot,
                         float* mu_slot, float* sigma_slot, int64_t N, int32_t A, void*) {
     if (cpu_only(device)) return 1;
-    if (!mean || !log_std || !counters || N < 0 || A <= 0 || A > 128) { g_error = "mms_ppo_act: bad arguments (A must be in 1..128)"; return 1; }
+    if (refused(check_ppo_act(mean, log_std, counters, N, A))) return 1;
 #pragma omp parallel for schedule(static)
     for (int64_t row = 0; row < N; row++)
         sample_row(mean + row * A, value ? value[row] : 0.f, value != nullptr, log_std, seed, counters, row_offset, reference_scale, actions_out,
@@ -421,14 +230,7 @@ MMS_API int mms_ppo_heads_act(int device, const float* hidden, const float* weig
                               int64_t* counters, int64_t row_offset, int32_t reference_scale, float* actions_out, float* act_slot,
                               float* logp_slot, float* value_slot, float* mu_slot, float* sigma_slot, int64_t N, int32_t A, void*) {
     if (cpu_only(device)) return 1;
-    if (!hidden || !weight || !bias || !log_std || !counters || N < 0 || A <= 0 || A > 128 || H <= 0 || (H % 64) != 0) {
-        g_error = "mms_ppo_heads_act: bad arguments (A must be in 1..128, H a positive multiple of 64)";
-        return 1;
-    }
-    if (vhidden && (!vweight || !vbias || VH <= 0 || (VH % 4) != 0)) {
-        g_error = "mms_ppo_heads_act: the value head needs weight, bias and a hidden width that is a multiple of 4";
-        return 1;
-    }
+    if (refused(check_ppo_heads_act(hidden, weight, bias, H, vhidden, vweight, vbias, VH, log_std, counters, N, A))) return 1;
 #pragma omp parallel for schedule(static)
     for (int64_t row = 0; row < N; row++) {
         float mean[128];
@@ -453,15 +255,7 @@ MMS_API int mms_sac_heads_act(int device, const float* hidden, int32_t H, const 
                               int64_t row_offset, float* actions_out, float* act_slot, float* logp_slot, float* u_slot, float* mu_slot,
                               float* log_std_slot, int64_t N, int32_t A, void*) {
     if (cpu_only(device)) return 1;
-    if (!hidden || !mu_weight || !mu_bias || !ls_weight || !ls_bias || (!deterministic && !counters) || N < 0 || A <= 0 || A > 128 || H <= 0 ||
-        (H % 64) != 0) {
-        g_error = "mms_sac_heads_act: bad arguments (A must be in 1..128, H a positive multiple of 64, counters required unless deterministic)";
-        return 1;
-    }
-    if (((uintptr_t)hidden | (uintptr_t)mu_weight | (uintptr_t)ls_weight) & 15) {
-        g_error = "mms_sac_heads_act: hidden and both weight matrices must be 16-byte aligned";
-        return 1;
-    }
+    if (refused(check_sac_heads_act(hidden, H, mu_weight, mu_bias, ls_weight, ls_bias, deterministic, counters, N, A))) return 1;
     const bool want_logp = logp_slot != nullptr;
 #pragma omp parallel for schedule(static)
     for (int64_t row = 0; row < N; row++) {
@@ -506,12 +300,8 @@ static float act_fn(float v, int act) {
 MMS_API int mms_linear2_act(int device, int64_t M, int32_t N, int32_t K, const float* x0, const float* w0, const float* b0, float* y0,
                             const float* x1, const float* w1, const float* b1, float* y1, int32_t act, void*) {
     if (cpu_only(device)) return 1;
-    if (!x0 || !w0 || !b0 || !y0 || M < 0 || N <= 0 || K <= 0 || (K % 4) != 0 || act < 0 || act > 3) {
-        g_error = "mms_linear2_act: bad arguments (K must be a positive multiple of 4, act 0..3)";
-        return 1;
-    }
-    const bool two = x1 || w1 || b1 || y1;
-    if (two && !(x1 && w1 && b1 && y1)) { g_error = "mms_linear2_act: the second problem needs all four pointers"; return 1; }
+    if (refused(check_linear2_act(M, N, K, x0, w0, b0, y0, x1, w1, b1, y1, act))) return 1;
+    const bool two = x1 != nullptr;
     const float* xs[2] = {x0, x1};
     const float* ws[2] = {w0, w1};
     const float* bs[2] = {b0, b1};
@@ -549,10 +339,7 @@ static inline void split3(float v, uint16_t* p0, uint16_t* p1, uint16_t* p2) {
 }
 static inline float join3(const uint16_t* chunk, int j) { return (bf2f(chunk[j]) + bf2f(chunk[32 + j])) + bf2f(chunk[64 + j]); }
 
-MMS_API int mms_split_planes(int device, int64_t rows, int32_t K, int32_t x_pitch, const float* x, void* planes, void*) {
-    if (cpu_only(device)) return 1;
-    if (x_pitch == 0) x_pitch = K;
-    if (!x || !planes || rows < 0 || K <= 0 || x_pitch < K) { g_error = "mms_split_planes: bad arguments"; return 1; }
+static void split_planes_rows(int64_t rows, int32_t K, int32_t x_pitch, const float* x, void* planes) {
     const int KC = (K + 31) / 32;
     uint16_t* out = (uint16_t*)planes;
 #pragma omp parallel for schedule(static)
@@ -564,17 +351,21 @@ MMS_API int mms_split_planes(int device, int64_t rows, int32_t K, int32_t x_pitc
                 split3(k < K ? x[r * x_pitch + k] : 0.f, c + j, c + 32 + j, c + 64 + j);
             }
         }
+}
+
+MMS_API int mms_split_planes(int device, int64_t rows, int32_t K, int32_t x_pitch, const float* x, void* planes, void*) {
+    if (cpu_only(device)) return 1;
+    if (x_pitch == 0) x_pitch = K;
+    if (refused(check_split_planes(rows, K, x_pitch, x, planes))) return 1;
+    split_planes_rows(rows, K, x_pitch, x, planes);
     return 0;
 }
 
 MMS_API int mms_split_planes_group(int device, int32_t groups, int64_t rows, int32_t K, int32_t x_pitch, const float* const* x, void* const* planes, void*) {
     if (cpu_only(device)) return 1;
-    if (groups < 1 || groups > MMS_MAX_GROUPS) { g_error = "mms_split_planes_group: groups must be 1.." + std::to_string(MMS_MAX_GROUPS); return 1; }
-    if (!x || !planes) { g_error = "mms_split_planes_group: bad arguments (x_pitch >= K)"; return 1; }
-    for (int g = 0; g < groups; g++) {
-        if (!x[g] || !planes[g]) { g_error = "mms_split_planes_group: null or misaligned pointer in a group (planes 16-byte aligned)"; return 1; }
-        if (mms_split_planes(device, rows, K, x_pitch, x[g], planes[g], nullptr)) return 1;
-    }
+    if (x_pitch == 0) x_pitch = K;
+    if (refused(check_split_planes_group(groups, rows, K, x_pitch, x, planes))) return 1;
+    for (int g = 0; g < groups; g++) split_planes_rows(rows, K, x_pitch, x[g], planes[g]);
     return 0;
 }
 
@@ -621,44 +412,15 @@ static void split_layer_rows(int64_t M, int32_t N, int KC, const std::vector<flo
     }
 }
 
-static int split_layer_check(const char* fn, int32_t groups, const void* x, const void* w, const void* b, int64_t M, int32_t N, int32_t K, int32_t act,
-                             int32_t out_mode, const void* y, const void* ln_s, const void* ln_stat_in, const void* ln_part_out, const void* head_w,
-                             const void* head_part, const int32_t* head_dims) {
-    const std::string f(fn);
-    if (groups < 1 || groups > MMS_MAX_GROUPS) { g_error = f + ": groups must be 1.." + std::to_string(MMS_MAX_GROUPS); return 1; }
-    if (!x || !w || !b || M < 0 || (M % 128) != 0 || N <= 0 || (N % 128) != 0 || K <= 0 || act < 0 || act > 3 || out_mode < 0 || out_mode > 2 || (out_mode != 2 && !y)) {
-        g_error = f + ": bad arguments (M and N multiples of 128, act 0..3, out_mode 0..2)";
-        return 1;
-    }
-    const bool ln = ln_s || ln_stat_in || ln_part_out;
-    if (ln && (!ln_s || !ln_stat_in || !ln_part_out || act != 1 || out_mode == 0)) {
-        g_error = f + ": the LayerNorm folds come together (ln_s, ln_stat_in, ln_part_out), with act = ELU and out_mode 1 or 2";
-        return 1;
-    }
-    if (out_mode == 2 && (!ln || !head_w || !head_part || !head_dims)) {
-        g_error = f + ": out_mode 2 needs the LayerNorm folds, head_w, head_part and head_dims";
-        return 1;
-    }
-    if (out_mode == 2)
-        for (int g = 0; g < groups; g++)
-            if (head_dims[g] < 1 || head_dims[g] > 16) { g_error = "split layer, out_mode 2: 1 <= head_dims[g] <= 16"; return 1; }
-    return 0;
-}
-
 MMS_API int mms_linear_group_act_split(int device, int32_t groups, int64_t M, int32_t N, int32_t K, const void* const* x, const void* const* w,
                                        const float* const* b, void* const* y, int32_t act, int32_t out_mode, const float* const* ln_s,
                                        const float* const* ln_stat_in, float* const* ln_part_out, const float* const* head_w, float* const* head_part,
                                        const int32_t* head_dims, void*) {
     if (cpu_only(device)) return 1;
-    if (split_layer_check("mms_linear_group_act_split", groups, x, w, b, M, N, K, act, out_mode, y, ln_s, ln_stat_in, ln_part_out, head_w, head_part, head_dims)) return 1;
+    if (refused(check_split_layer(false, groups, M, N, K, x, w, b, y, nullptr, nullptr, nullptr, act, out_mode, ln_s, ln_stat_in, ln_part_out, head_w, head_part, head_dims))) return 1;
     const bool ln = ln_s != nullptr;
     const int KC = (K + 31) / 32, NC = N / 32;
     for (int g = 0; g < groups; g++) {
-        if (!x[g] || !w[g] || !b[g] || (out_mode != 2 && !y[g]) || (ln && (!ln_s[g] || !ln_stat_in[g] || !ln_part_out[g])) ||
-            (out_mode == 2 && (!head_w[g] || !head_part[g]))) {
-            g_error = "mms_linear_group_act_split: null pointer in a group";
-            return 1;
-        }
         const uint16_t* xp = (const uint16_t*)x[g];
         const uint16_t* wp = (const uint16_t*)w[g];
         std::vector<float> wf((size_t)N * KC * 32);
@@ -700,23 +462,11 @@ static inline void split2(float t, uint16_t* hi, uint16_t* lo) {
 }
 static inline float join2(const uint16_t* chunk, int j) { return h2f(chunk[j]) + h2f(chunk[32 + j]) * (1.f / 2048.f); }
 
-MMS_API int mms_split_planes16_group(int device, int32_t groups, int64_t rows, int32_t K, int32_t x_pitch, const float* const* x, void* const* planes,
-                                     float* const* scale, float* const* inv, int32_t nchains, int32_t L, const float* const* chain,
-                                     float* const* chain_scale, float* const* chain_inv, float* const* stat, float eps, void*) {
-    if (cpu_only(device)) return 1;
-    if (groups < 1 || groups > MMS_MAX_GROUPS) { g_error = "mms_split_planes16_group: groups must be 1.." + std::to_string(MMS_MAX_GROUPS); return 1; }
-    if (x_pitch == 0) x_pitch = K;
-    if (!x || !planes || !scale || !inv || rows < 0 || K <= 0 || x_pitch < K || nchains < 0 || L < 0 || (nchains > 0 && (L < 1 || !chain || !chain_scale || !chain_inv))) {
-        g_error = "mms_split_planes16_group: bad arguments (x_pitch >= K; nchains > 0 needs L >= 1, chain, chain_scale, chain_inv)";
-        return 1;
-    }
+static void split_planes16_rows(int32_t groups, int64_t rows, int32_t K, int32_t x_pitch, const float* const* x, void* const* planes, float* const* scale,
+                                float* const* inv, int32_t nchains, int32_t L, const float* const* chain, float* const* chain_scale,
+                                float* const* chain_inv, float* const* stat, float eps) {
     const int KC = (K + 31) / 32;
     for (int g = 0; g < groups; g++) {
-        if (!x[g] || !planes[g] || (nchains > 0 && (!chain[g] || !chain_scale[g] || !chain_inv[g]))) {
-            g_error = "mms_split_planes16_group: null or misaligned pointer in a group (planes 16-byte aligned)";
-            return 1;
-        }
-        if (stat && !stat[g]) { g_error = "mms_split_planes16_group: null or misaligned stat pointer in a group"; return 1; }
         uint16_t* out = (uint16_t*)planes[g];
         const float* xg = x[g];
 #pragma omp parallel for schedule(static)
@@ -754,6 +504,15 @@ MMS_API int mms_split_planes16_group(int device, int32_t groups, int64_t rows, i
             }
         }
     }
+}
+
+MMS_API int mms_split_planes16_group(int device, int32_t groups, int64_t rows, int32_t K, int32_t x_pitch, const float* const* x, void* const* planes,
+                                     float* const* scale, float* const* inv, int32_t nchains, int32_t L, const float* const* chain,
+                                     float* const* chain_scale, float* const* chain_inv, float* const* stat, float eps, void*) {
+    if (cpu_only(device)) return 1;
+    if (x_pitch == 0) x_pitch = K;
+    if (refused(check_split_planes16_group(groups, rows, K, x_pitch, x, planes, scale, inv, nchains, L, chain, chain_scale, chain_inv, stat))) return 1;
+    split_planes16_rows(groups, rows, K, x_pitch, x, planes, scale, inv, nchains, L, chain, chain_scale, chain_inv, stat, eps);
     return 0;
 }
 
@@ -763,15 +522,10 @@ MMS_API int mms_split_planes16_group(int device, int32_t groups, int64_t rows, i
 MMS_API int mms_weight_planes16_group(int device, int32_t groups, const int64_t* N, const int32_t* K, const float* const* w, void* const* planes,
                                       float* const* scale, float* const* inv, float* const* l1, void*) {
     if (cpu_only(device)) return 1;
-    if (groups < 1 || groups > MMS_MAX_GROUPS) { g_error = "mms_weight_planes16_group: groups must be 1.." + std::to_string(MMS_MAX_GROUPS); return 1; }
-    if (!N || !K || !w || !planes || !scale || !inv) { g_error = "mms_weight_planes16_group: bad arguments (null array)"; return 1; }
-    for (int g = 0; g < groups; g++) {
-        if (N[g] < 0 || K[g] <= 0) { g_error = "mms_weight_planes16_group: bad shape in a group (N >= 0, K > 0)"; return 1; }
-        if (!w[g] || !planes[g] || !scale[g] || !inv[g]) { g_error = "mms_weight_planes16_group: null or misaligned pointer in a group (planes and inv 16-byte aligned)"; return 1; }
-    }
+    if (refused(check_weight_planes16_group(groups, N, K, w, planes, scale, inv))) return 1;
     for (int g = 0; g < groups; g++) {
         if (N[g] == 0) continue;
-        if (mms_split_planes16_group(device, 1, N[g], K[g], K[g], w + g, planes + g, scale + g, inv + g, 0, 0, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr)) return 1;
+        split_planes16_rows(1, N[g], K[g], K[g], w + g, planes + g, scale + g, inv + g, 0, 0, nullptr, nullptr, nullptr, nullptr, 0.f);
         if (!l1 || !l1[g]) continue;
         const int Kg = K[g], KC = (Kg + 31) / 32, pieces = KC * 4;
         int P = 1;
@@ -799,12 +553,7 @@ MMS_API int mms_weight_planes16_group(int device, int32_t groups, const int64_t*
 MMS_API int mms_chain_refresh16(int device, int32_t nchains, int32_t L, const float* const* l1, const float* const* bias, const int32_t* n, float* chain,
                                 float bound0, int64_t rows, float* chain_scale, float* chain_inv, void*) {
     if (cpu_only(device)) return 1;
-    if (nchains < 1 || L < 1 || (int64_t)nchains * L > MMS_MAX_GROUPS || !l1 || !n || !chain || rows < 0 || (rows > 0 && (!chain_scale || !chain_inv || !(bound0 >= 0.f)))) {
-        g_error = "mms_chain_refresh16: bad arguments (nchains, L >= 1, nchains * L <= " + std::to_string(MMS_MAX_GROUPS) + "; rows > 0 needs chain_scale, chain_inv, bound0 >= 0)";
-        return 1;
-    }
-    for (int e = 0; e < nchains * L; e++)
-        if (!l1[e] || n[e] < 0) { g_error = "mms_chain_refresh16: null pointer or negative count in an entry"; return 1; }
+    if (refused(check_chain_refresh16(nchains, L, l1, n, chain, bound0, rows, chain_scale, chain_inv))) return 1;
     for (int e = 0; e < nchains * L; e++) {
         float m = 0.f, b = 0.f;
         for (int i = 0; i < n[e]; i++) {
@@ -834,15 +583,7 @@ MMS_API int mms_fold_planes16_group(int device, int32_t groups, const int64_t* N
                                     const float* const* beta, const float* const* bias, void* const* planes, float* const* inv, float* const* s_out,
                                     float* const* c_out, float* const* rb, float* const* wt, void*) {
     if (cpu_only(device)) return 1;
-    if (groups < 1 || groups > MMS_MAX_GROUPS) { g_error = "mms_fold_planes16_group: groups must be 1.." + std::to_string(MMS_MAX_GROUPS); return 1; }
-    if (!N || !K || !w) { g_error = "mms_fold_planes16_group: bad arguments (null array)"; return 1; }
-    for (int g = 0; g < groups; g++) {
-        if (N[g] < 0 || K[g] <= 0) { g_error = "mms_fold_planes16_group: bad shape in a group (N >= 0, K > 0)"; return 1; }
-        if (!w[g] || (planes && planes[g] && (!inv || !inv[g]))) {
-            g_error = "mms_fold_planes16_group: null or misaligned pointer in a group (planes 16-byte aligned and with inv)";
-            return 1;
-        }
-    }
+    if (refused(check_fold_planes16_group(groups, N, K, w, planes, inv))) return 1;
     for (int g = 0; g < groups; g++) {
         const int Kg = K[g], KC = (Kg + 31) / 32;
         const float* gm = gamma ? gamma[g] : nullptr;
@@ -883,10 +624,7 @@ MMS_API int mms_fold_planes16_group(int device, int32_t groups, const int64_t* N
 MMS_API int mms_fold_scales16_group(int device, int32_t groups, const float* const* rb, const int32_t* n, int64_t M, float* const* scale1,
                                     float* const* ysc, float* const* yinv, void*) {
     if (cpu_only(device)) return 1;
-    if (groups < 1 || groups > MMS_MAX_GROUPS) { g_error = "mms_fold_scales16_group: groups must be 1.." + std::to_string(MMS_MAX_GROUPS); return 1; }
-    if (!rb || !n || M < 0) { g_error = "mms_fold_scales16_group: bad arguments"; return 1; }
-    for (int g = 0; g < groups; g++)
-        if (!rb[g] || n[g] < 0) { g_error = "mms_fold_scales16_group: null pointer or negative count in a group"; return 1; }
+    if (refused(check_fold_scales16_group(groups, rb, n, M))) return 1;
     for (int g = 0; g < groups; g++) {
         float m = 0.f;
         for (int i = 0; i < n[g]; i++) m = fmaxf(m, rb[g][i]);
@@ -909,16 +647,10 @@ MMS_API int mms_linear_group_act_split16(int device, int32_t groups, int64_t M, 
                                          const float* const* ln_stat_in, float* const* ln_part_out, const float* const* head_w, float* const* head_part,
                                          const int32_t* head_dims, void*) {
     if (cpu_only(device)) return 1;
-    if (split_layer_check("mms_linear_group_act_split16", groups, x, w, b, M, N, K, act, out_mode, y, ln_s, ln_stat_in, ln_part_out, head_w, head_part, head_dims)) return 1;
-    if (!x_inv || !w_inv || (out_mode == 1 && !y_scale)) { g_error = "mms_linear_group_act_split16: bad arguments (x_inv, w_inv, y_scale with out_mode 1)"; return 1; }
+    if (refused(check_split_layer(true, groups, M, N, K, x, w, b, y, x_inv, w_inv, y_scale, act, out_mode, ln_s, ln_stat_in, ln_part_out, head_w, head_part, head_dims))) return 1;
     const bool ln = ln_s != nullptr;
     const int KC = (K + 31) / 32, NC = N / 32;
     for (int g = 0; g < groups; g++) {
-        if (!x[g] || !w[g] || !b[g] || !x_inv[g] || !w_inv[g] || (out_mode != 2 && !y[g]) || (out_mode == 1 && !y_scale[g]) ||
-            (ln && (!ln_s[g] || !ln_stat_in[g] || !ln_part_out[g])) || (out_mode == 2 && (!head_w[g] || !head_part[g]))) {
-            g_error = "mms_linear_group_act_split16: null pointer in a group";
-            return 1;
-        }
         const uint16_t* xp = (const uint16_t*)x[g];
         const uint16_t* wp = (const uint16_t*)w[g];
         std::vector<float> wf((size_t)N * KC * 32);
@@ -959,10 +691,8 @@ static void chan_combine(const float* part, int64_t M, int64_t row, int slots, f
 
 MMS_API int mms_row_stats_chan_group(int device, int32_t groups, int64_t M, int32_t slots, const float* const* part, float* const* stat, float eps, void*) {
     if (cpu_only(device)) return 1;
-    if (groups < 1 || groups > MMS_MAX_GROUPS) { g_error = "mms_row_stats_chan_group: groups must be 1.." + std::to_string(MMS_MAX_GROUPS); return 1; }
-    if (!part || !stat || M < 0 || slots < 1) { g_error = "mms_row_stats_chan_group: bad arguments"; return 1; }
+    if (refused(check_row_stats_chan_group(groups, M, slots, part, stat))) return 1;
     for (int g = 0; g < groups; g++) {
-        if (!part[g] || !stat[g]) { g_error = "mms_row_stats_chan_group: null pointer in a group"; return 1; }
         for (int64_t r = 0; r < M; r++) {
             float mean, m2;
             chan_combine(part[g], M, r, slots, mean, m2);
@@ -977,15 +707,9 @@ MMS_API int mms_marl_heads_finish(int device, int32_t groups, int64_t M, int32_t
                                   const float* const* hs, const float* const* hc, const int32_t* A, const float* const* std, float* const* out,
                                   float* const* logp, const int32_t* out_pitch, int64_t* const* counters, uint64_t seed, int64_t row_offset, float eps, void*) {
     if (cpu_only(device)) return 1;
-    if (groups < 1 || groups > MMS_MAX_GROUPS) { g_error = "mms_marl_heads_finish: groups must be 1.." + std::to_string(MMS_MAX_GROUPS); return 1; }
-    if (!part || !head_part || !hs || !hc || !A || !out || M < 0 || slots < 1) { g_error = "mms_marl_heads_finish: bad arguments"; return 1; }
+    if (refused(check_marl_heads_finish(groups, M, slots, part, head_part, hs, hc, A, out, out_pitch))) return 1;
     for (int g = 0; g < groups; g++) {
-        if (!part[g] || !head_part[g] || !hs[g] || !hc[g] || !out[g] || A[g] < 1 || A[g] > 16) {
-            g_error = "mms_marl_heads_finish: null pointer or output width outside 1..16 in a group";
-            return 1;
-        }
         const int pitch = out_pitch ? out_pitch[g] : A[g];
-        if (pitch < A[g]) { g_error = "mms_marl_heads_finish: out_pitch below the output width"; return 1; }
         const float* sd = std ? std[g] : nullptr;
         int64_t* cnt = (sd && counters) ? counters[g] : nullptr;
         for (int64_t r = 0; r < M; r++) {
@@ -1008,31 +732,13 @@ MMS_API int mms_marl_heads_finish(int device, int32_t groups, int64_t M, int32_t
     return 0;
 }
 
-// ---- grouped policy inference (the same three operators as the HIP build; plain loops) -------------------------------------------
-static bool bad_groups(int32_t groups, const char* what) {
-    if (groups >= 1 && groups <= MMS_MAX_GROUPS) return false;
-    g_error = std::string(what) + ": groups must be 1.." + std::to_string(MMS_MAX_GROUPS);
-    return true;
-}
+// ---- grouped policy inference (plain loops) -------------------------------------------------------------------------------------
 MMS_API int mms_linear_group_act(int device, int32_t groups, int64_t M, int32_t N, int32_t K, const float* const* x, const float* const* w,
                                  const float* const* b, float* const* y, int32_t act, const float* const* ln_s, const float* const* ln_stat_in,
                                  float* const* ln_part_out, void*) {
     if (cpu_only(device)) return 1;
-    if (bad_groups(groups, "mms_linear_group_act")) return 1;
-    if (!x || !w || !b || !y || M < 0 || N <= 0 || K <= 0 || (K % 4) != 0 || act < 0 || act > 3) {
-        g_error = "mms_linear_group_act: bad arguments (K must be a positive multiple of 4, act 0..3)";
-        return 1;
-    }
-    if ((ln_stat_in != nullptr) != (ln_s != nullptr)) { g_error = "mms_linear_group_act: ln_stat_in and ln_s come together"; return 1; }
-    if ((ln_stat_in || ln_part_out) && (act != 1 || M % 128 != 0 || N % 128 != 0 || K < 8)) {
-        g_error = "mms_linear_group_act: the LayerNorm folds need act = ELU, M and N multiples of 128";
-        return 1;
-    }
+    if (refused(check_linear_group_act(groups, M, N, K, x, w, b, y, act, ln_s, ln_stat_in, ln_part_out))) return 1;
     for (int g = 0; g < groups; g++) {
-        if (!x[g] || !w[g] || !b[g] || !y[g] || (ln_s && (!ln_s[g] || !ln_stat_in[g])) || (ln_part_out && !ln_part_out[g])) {
-            g_error = "mms_linear_group_act: null pointer in a group";
-            return 1;
-        }
 #pragma omp parallel for schedule(static)
         for (int64_t m = 0; m < M; m++) {
             for (int n = 0; n < N; n++) {
@@ -1055,10 +761,8 @@ MMS_API int mms_linear_group_act(int device, int32_t groups, int64_t M, int32_t 
 MMS_API int mms_row_stats_group(int device, int32_t groups, int64_t M, int32_t slots, int32_t width, const float* const* part, float* const* stat,
                                 float eps, void*) {
     if (cpu_only(device)) return 1;
-    if (bad_groups(groups, "mms_row_stats_group")) return 1;
-    if (!part || !stat || M < 0 || slots < 1 || width < 1) { g_error = "mms_row_stats_group: bad arguments"; return 1; }
+    if (refused(check_row_stats_group(groups, M, slots, width, part, stat))) return 1;
     for (int g = 0; g < groups; g++) {
-        if (!part[g] || !stat[g]) { g_error = "mms_row_stats_group: null pointer in a group"; return 1; }
         for (int64_t m = 0; m < M; m++) {
             float sum = 0.f, sq = 0.f;
             for (int k = 0; k < slots; k++) { sum += part[g][((int64_t)k * M + m) * 2]; sq += part[g][((int64_t)k * M + m) * 2 + 1]; }
@@ -1081,11 +785,9 @@ static void ln_row(const float* x, int K, float eps, float& mean, float& rstd) {
 MMS_API int mms_row_moments_group(int device, int32_t groups, int64_t M, int32_t K, int32_t x_pitch, const float* const* x, float* const* stat,
                                   float eps, void*) {
     if (cpu_only(device)) return 1;
-    if (bad_groups(groups, "mms_row_moments_group")) return 1;
     if (x_pitch == 0) x_pitch = K;
-    if (!x || !stat || M < 0 || K <= 0 || K > 4096 || x_pitch < K) { g_error = "mms_row_moments_group: bad arguments (1 <= K <= 4096)"; return 1; }
+    if (refused(check_row_moments_group(groups, M, K, x_pitch, x, stat))) return 1;
     for (int g = 0; g < groups; g++) {
-        if (!x[g] || !stat[g]) { g_error = "mms_row_moments_group: null pointer in a group"; return 1; }
 #pragma omp parallel for schedule(static)
         for (int64_t m = 0; m < M; m++) ln_row(x[g] + m * x_pitch, K, eps, stat[g][2 * m], stat[g][2 * m + 1]);
     }
@@ -1094,15 +796,9 @@ MMS_API int mms_row_moments_group(int device, int32_t groups, int64_t M, int32_t
 MMS_API int mms_layernorm_group(int device, int32_t groups, int64_t M, int32_t K, int32_t Kp, int32_t x_pitch, const float* const* x,
                                 const float* const* gamma, const float* const* beta, float* const* y, float eps, void*) {
     if (cpu_only(device)) return 1;
-    if (bad_groups(groups, "mms_layernorm_group")) return 1;
     if (x_pitch == 0) x_pitch = K;
-    if (!x || !gamma || !beta || !y || M < 0 || K <= 0 || K > 4096 || Kp < K || x_pitch < K) {
-        g_error = "mms_layernorm_group: bad arguments (1 <= K <= 4096, Kp >= K, x_pitch >= K or 0)";
-        return 1;
-    }
+    if (refused(check_layernorm_group(groups, M, K, Kp, x_pitch, x, gamma, beta, y))) return 1;
     for (int g = 0; g < groups; g++) {
-        if (!x[g] || !gamma[g] || !beta[g] || !y[g]) { g_error = "mms_layernorm_group: null pointer in a group"; return 1; }
-        if ((Kp != K || x_pitch != K) && x[g] == y[g]) { g_error = "mms_layernorm_group: in place needs Kp == x_pitch == K"; return 1; }
 #pragma omp parallel for schedule(static)
         for (int64_t m = 0; m < M; m++) {
             float mean, rstd;
@@ -1118,18 +814,9 @@ MMS_API int mms_marl_heads_act(int device, int32_t groups, int64_t M, int32_t H,
                                float* const* out, float* const* logp, const int32_t* out_pitch, int64_t* const* counters, uint64_t seed,
                                int64_t row_offset, float eps, void*) {
     if (cpu_only(device)) return 1;
-    if (bad_groups(groups, "mms_marl_heads_act")) return 1;
-    if (!h || !gamma || !beta || !w || !b || !A || !out || M < 0 || H <= 0 || H > 1024) {
-        g_error = "mms_marl_heads_act: bad arguments (1 <= H <= 1024)";
-        return 1;
-    }
+    if (refused(check_marl_heads_act(groups, M, H, h, gamma, beta, w, b, A, out, out_pitch))) return 1;
     for (int g = 0; g < groups; g++) {
-        if (!h[g] || !gamma[g] || !beta[g] || !w[g] || !b[g] || !out[g] || A[g] < 1 || A[g] > 16) {
-            g_error = "mms_marl_heads_act: null pointer in a group, or outputs outside 1..16";
-            return 1;
-        }
         const int op = out_pitch ? out_pitch[g] : A[g];
-        if (op < A[g]) { g_error = "mms_marl_heads_act: out_pitch below the number of outputs"; return 1; }
         const float* sd = std ? std[g] : nullptr;
         float* lp = logp ? logp[g] : nullptr;
         int64_t* cnt = counters ? counters[g] : nullptr;
@@ -1194,33 +881,12 @@ static void mlp_nn(int64_t M, int N, int K, int terms, const float* const* D, co
         }
 }
 
-static int mlp_check(const char* who, int32_t L, int64_t M, const int32_t* dims, int64_t* ws_bytes) {
-    bool ok = dims && ws_bytes && L >= 2 && L <= 8 && M >= 1 && M <= 65535 * 32 / 128 * 128;     // the HIP build's row limit
-    for (int l = 0; ok && l <= L; l++) ok = dims[l] >= 1 && dims[l] <= 65536;
-    if (!ok) {
-        g_error = std::string(who) + ": bad arguments (2 <= layers <= 8, 1 <= M <= 2097024, dims[0..layers] in 1..65536, ws_bytes required)";
-        return 1;
-    }
-    return 0;
-}
-static bool mlp_all(int n, const float* const* p) {
-    if (!p) return false;
-    for (int i = 0; i < n; i++)
-        if (!p[i]) return false;
-    return true;
-}
-
 MMS_API int mms_mlp_grad(int device, int32_t L, int64_t M, const int32_t* dims, const float* x, const float* const* h, const float* const* w,
                          const float* g, float* const* dw, float* const* db, float* const* d_out, float* const* e_out, void* workspace,
                          int64_t* ws_bytes, void*) {
     if (cpu_only(device)) return 1;
-    if (mlp_check("mms_mlp_grad", L, M, dims, ws_bytes)) return 1;
+    if (refused(check_mlp_grad(L, M, dims, x, h, w, g, dw, db, d_out, e_out, workspace, ws_bytes))) return 1;
     if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query (callers pass any non-NULL workspace to run)
-    if (!x || !g || !mlp_all(L - 1, h) || !mlp_all(L, w) || !mlp_all(L, dw) || !mlp_all(L, db) || (d_out && !mlp_all(L - 1, d_out)) ||
-        (e_out && !mlp_all(L - 1, e_out))) {
-        g_error = "mms_mlp_grad: null pointer (x, g, h[layers-1], w / dw / db[layers]; d_out / e_out all or none)";
-        return 1;
-    }
     std::vector<float> dcur(g, g + M * dims[L]), dnext;
     std::vector<double> e;
     for (int l = L; l >= 1; l--) {
@@ -1250,13 +916,8 @@ MMS_API int mms_mlp_grad_rop(int device, int32_t L, int64_t M, const int32_t* di
                              const float* const* v, const float* const* c, const float* g, const float* const* d, const float* const* e,
                              float* rmu, float* const* rdw, float* const* rdb, void* workspace, int64_t* ws_bytes, void*) {
     if (cpu_only(device)) return 1;
-    if (mlp_check("mms_mlp_grad_rop", L, M, dims, ws_bytes)) return 1;
+    if (refused(check_mlp_grad_rop(L, M, dims, x, h, w, v, c, g, d, e, rmu, rdw, rdb, workspace, ws_bytes))) return 1;
     if (!workspace) { *ws_bytes = 0; return 0; }
-    if (!x || !g || !rmu || !mlp_all(L - 1, h) || !mlp_all(L, w) || !mlp_all(L, v) || !mlp_all(L, c) || !mlp_all(L - 1, d) ||
-        !mlp_all(L - 1, e) || !mlp_all(L, rdw) || !mlp_all(L, rdb)) {
-        g_error = "mms_mlp_grad_rop: null pointer (x, g, rmu, h / d / e[layers-1], w / v / c / rdw / rdb[layers])";
-        return 1;
-    }
     // R-forward: Ra_l = Rh_{l-1} W_l^T + h_{l-1} V_l^T + c_l, Rh_l = f'(h_l) Ra_l
     std::vector<std::vector<float>> Ra(L + 1), Rh(L);
     for (int l = 1; l <= L; l++) {

@@ -1,0 +1,558 @@
+// mms_host.h -- the rules of the C ABI (include/mms.h) that do not touch a device, written once for both builds of the engine:
+// mms_api.hip (libmms.so) and cpu/mms_cpu.cpp (libmms_cpu.so).  The engine state both keep, the host half of mms_create (config
+// check, task dimensions, buffer table, construction-time scene), the entry points that only change that state, and the argument
+// check of every operator entry.  Plain C++17, no HIP include.  A check returns the message for mms_last_error, or an empty string;
+// what the HIP build refuses the CPU build refuses in the same words (the CPU build is the stand-in for the HIP boundary on
+// machines without a GPU).  What stays different between the builds on purpose is listed in DESIGN.md section 1.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/mms.h"
+
+namespace mms {
+constexpr int kMlpMaxLayers = 8;
+constexpr int64_t kMlpMaxRows = 65535 * 32 / 128 * 128;   // rows: the 32-row chunks of the padded batch index a grid dimension
+}  // namespace mms
+
+struct mms_buffer {
+    const char* name;
+    void* ptr;
+    int64_t shape[4];
+    int ndim;
+    int dtype;
+    size_t bytes;
+    int64_t row_bytes;   // bytes per env (for indexed set_state)
+};
+
+// The engine state both builds keep; each build's mms_engine adds only what is its own.
+struct mms_host_state {
+    mms_config cfg;
+    int actors = 0, dofs = 0, num_actions = 0, obs_dim = 0, prev_dim = 0;
+    float* obs_out = nullptr;
+    void* obs_planes = nullptr;
+    float obs_planes_scale = 1.f;
+    const float* actions_in = nullptr;      // mms_bind_actions
+    bool head_on = false;                   // mms_bind_policy_head: consumed (and cleared) by the next mms_step
+    mms_policy_head head{};
+    int write_raw_obs = 1, write_clipped_obs = 1;
+    int dr_enabled = 0;
+    float* rew_out = nullptr;
+    uint8_t* done_out = nullptr;
+    std::vector<mms_buffer> bufs;
+    std::string err;
+};
+
+// the message of a call without a handle: mms_last_error(NULL)
+inline std::string g_error;
+
+static inline int fail(mms_host_state* e, const std::string& msg) {
+    if (e) e->err = msg; else g_error = msg;
+    return 1;
+}
+// an operator entry's check: 0 to go on, 1 with the message stored
+static inline int refused(const std::string& msg) { return msg.empty() ? 0 : fail(nullptr, msg); }
+static inline int null_handle(const mms_host_state* h, const char* entry) { return h ? 0 : fail(nullptr, std::string(entry) + ": null handle"); }
+
+static inline size_t dtype_size(int dt) { return dt == MMS_F32 ? 4 : dt == MMS_I64 ? 8 : dt == MMS_I32 ? 4 : 1; }
+
+static inline mms_buffer* find(mms_host_state* e, const char* name) {
+    for (auto& b : e->bufs)
+        if (!strcmp(b.name, name)) return &b;
+    return nullptr;
+}
+
+static inline uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+
+// ---- mms_create, host half ----------------------------------------------------------------------------------------------------
+
+// The config check and the per-task dimensions (into e, with the config).  The device field is the build's own check.
+static inline std::string engine_init(mms_host_state* e, const mms_config* cfg, const mms_handle* out) {
+    if (!cfg || !out) return "mms_create: null argument";
+    if (cfg->abi_version != MMS_ABI_VERSION) return "mms_create: ABI version mismatch";
+    if (cfg->num_envs <= 0 || cfg->num_agents <= 0) return "mms_create: num_envs and num_agents must be positive";
+    const int A = cfg->num_agents;
+    if (cfg->task == MMS_TASK_TEN_ANT) { e->actors = A + 1; e->dofs = 8 * A; e->num_actions = 8 * A; e->obs_dim = 38 * A + 8; e->prev_dim = 4 * A + 2; }
+    else if (cfg->task == MMS_TASK_ONE_ANT) { e->actors = 2; e->dofs = 8; e->num_actions = 8; e->obs_dim = 60; e->prev_dim = 6; }
+    else if (cfg->task == MMS_TASK_MULTI_ANT_CIRCLE) { e->actors = A + 1; e->dofs = 8 * A; e->num_actions = 8 * A; e->obs_dim = 38 * A; e->prev_dim = 2 * A; }
+    else if (cfg->task == MMS_TASK_MULTI_INGENUITY) { e->actors = A; e->dofs = 4 * A; e->num_actions = 6 * A; e->obs_dim = 13 * A; e->prev_dim = 3 * A; }
+    else return "mms_create: unknown task";
+    if (cfg->task == MMS_TASK_MULTI_INGENUITY && A != 4) return "mms_create: MultiIngenuity has 4 helicopters per env";
+    if (cfg->task == MMS_TASK_ONE_ANT && A != 1) return "mms_create: OneAnt has one ant per env";
+    if (cfg->task == MMS_TASK_MULTI_ANT_CIRCLE && A != 2) return "mms_create: MultiAntCircle has two ants per env";
+    // one env is one workgroup of at most 512 lanes: 4 per ant, rounded up to 8, and 8 for the box
+    if (cfg->task != MMS_TASK_MULTI_INGENUITY && ((4 * A + 7) & ~7) + 8 > 512) return "mms_create: at most 126 ants per env";
+    e->cfg = *cfg;
+    return {};
+}
+
+// The named buffers of an engine (name, dtype, shape, sizes; ptr NULL): each build allocates them zero-filled where its step reads them.
+static inline std::vector<mms_buffer> buffer_table(const mms_host_state& e) {
+    const int64_t N = e.cfg.num_envs, A = e.cfg.num_agents;
+    const struct { const char* name; int dtype; int64_t rows, cols; } table[] = {       // cols 0: one dimension
+        {"actions", MMS_F32, N, e.num_actions},
+        {"obs", MMS_F32, N, e.obs_dim},
+        {"obs_clipped", MMS_F32, N, e.obs_dim},
+        {"rew", MMS_F32, N, 0},
+        {"reset", MMS_I64, N, 0},
+        {"progress", MMS_I64, N, 0},
+        {"reset_count", MMS_I64, N, 0},
+        {"root_states", MMS_F32, N * e.actors, 13},
+        {"initial_root_states", MMS_F32, N * e.actors, 13},
+        {"dof_state", MMS_F32, N * e.dofs, 2},
+        {"env_origin", MMS_F32, N, 3},
+        {"prev", MMS_F32, N, e.prev_dim},
+        {"reset_noise", MMS_F32, N, 16},
+        {"foot_sensors", MMS_F32, N * A, 24},
+        {"dr_params", MMS_F32, N * A, MMS_DR_FLOATS},
+    };
+    std::vector<mms_buffer> out;
+    for (const auto& t : table) {
+        mms_buffer b{};
+        b.name = t.name;
+        b.dtype = t.dtype;
+        b.ndim = t.cols ? 2 : 1;
+        b.shape[0] = t.rows;
+        b.shape[1] = t.cols;
+        b.bytes = (size_t)t.rows * (size_t)(t.cols ? t.cols : 1) * dtype_size(t.dtype);
+        b.row_bytes = (int64_t)(b.bytes / (size_t)N);
+        out.push_back(b);
+    }
+    return out;
+}
+
+// The construction-time scene (what create_sim .. prepare_sim leave in the reference, agents/tasks/ten_ant.py:205-633) into the
+// caller's zero-filled host arrays, shaped as the buffers of the same names.  root_states starts as a copy of initial_root_states.
+static inline void fill_scene(const mms_host_state& e, float* initial_root_states, float* env_origin, float* prev, int64_t* reset, float* dr_params) {
+    const mms_config* cfg = &e.cfg;
+    const int N = cfg->num_envs, A = cfg->num_agents;
+    int64_t npr = (int64_t)sqrt((double)cfg->total_envs);
+    if (npr < 1) npr = 1;
+    for (int i = 0; i < N; i++) {
+        int64_t gi = cfg->env_offset + i;
+        float* o = env_origin + 3 * (size_t)i;
+        o[0] = (float)(gi % npr) * 2.f * cfg->env_spacing;                       // env grid: SURVEY.md B.2 convention
+        o[1] = (float)(gi / npr) * 2.f * cfg->env_spacing;
+        float* r = initial_root_states + (size_t)i * e.actors * 13;
+        for (int k = 0; k < e.actors; k++) r[13 * k + 6] = 1.f;
+        if (cfg->task != MMS_TASK_MULTI_INGENUITY) {
+            for (int k = 0; k < A; k++) {                                        // ten_ant.py:339-358 / one_ant.py:234
+                float off = (A == 1) ? 0.f : (1.5f + 3.f * (float)(k / 2)) * ((k % 2 == 0) ? -1.f : 1.f);
+                r[13 * k + 0] = cfg->ant_start_x; r[13 * k + 1] = off; r[13 * k + 2] = cfg->ant_start_z;
+                if (cfg->task == MMS_TASK_MULTI_ANT_CIRCLE) {                       // multi_ant_circle.py:216-219: (3, 0, 1) and (-3, 0, 1)
+                    r[13 * k + 0] = (k % 2 == 0) ? cfg->ant_start_x : -cfg->ant_start_x; r[13 * k + 1] = 0.f;
+                }
+            }
+            for (int j = 0; j < 3; j++) r[13 * A + j] = cfg->box_start[j];       // ten_ant.py:494-495
+        } else {
+            static const float hy[4] = {2.f, -2.f, 6.f, -6.f};                   // multi_ingenuity.py:157-164
+            for (int k = 0; k < A; k++) { r[13 * k + 0] = 0.f; r[13 * k + 1] = hy[k % 4]; r[13 * k + 2] = 1.f; }
+        }
+        // caches start as the construction-time poses: what reset_idx reads from the not-yet-refreshed tensors on the
+        // first step (ten_ant.py:870-882, one_ant.py:410-411), in the global frame
+        float* pv = prev + (size_t)i * e.prev_dim;
+        if (cfg->task == MMS_TASK_TEN_ANT) {
+            const float* b = r + 13 * A;
+            float bx = b[0] + o[0], by = b[1] + o[1];
+            float ang = atanf((2.f * b[6] * b[5]) / (1.f - 2.f * b[5] * b[5]));   // ten_ant.py:935-947
+            float sv = sinf(ang), cv = -cosf(ang);
+            for (int k = 0; k < A; k++) {
+                pv[2 * k] = r[13 * k] + o[0]; pv[2 * k + 1] = r[13 * k + 1] + o[1];
+                float off = 1.5f + 3.0f * (float)(k / 2);
+                pv[2 * A + 2 * k] = (k % 2 == 0) ? bx + off * sv : bx - off * sv;
+                pv[2 * A + 2 * k + 1] = (k % 2 == 0) ? by + off * cv : by - off * cv;
+            }
+            pv[4 * A] = bx; pv[4 * A + 1] = by;
+        } else if (cfg->task == MMS_TASK_ONE_ANT) {
+            pv[0] = r[0] + o[0]; pv[1] = r[1] + o[1]; pv[2] = r[13] + o[0]; pv[3] = r[14] + o[1];
+            pv[4] = -4.f / cfg->dt; pv[5] = -4.f / cfg->dt;                       // one_ant.py:143-144
+        } else if (cfg->task == MMS_TASK_MULTI_ANT_CIRCLE) {
+            for (int k = 0; k < A; k++) { pv[2 * k] = r[13 * k] + o[0]; pv[2 * k + 1] = r[13 * k + 1] + o[1]; }   // multi_ant_circle.py:367-368
+        }
+        reset[i] = 1;                                                            // base_task.py:62-63
+    }
+    for (size_t k = 0; k < (size_t)N * A; k++)                                   // nominal: scales 1, limit offsets 0
+        for (int j = 0; j < 17; j++) dr_params[k * MMS_DR_FLOATS + j] = 1.f;
+}
+
+// ---- the entry points that only read or change host state -----------------------------------------------------------------------
+
+static inline int host_get_tensor(mms_host_state* h, const char* name, mms_tensor* out) {
+    if (!h || !name || !out) return fail(h, "mms_get_tensor: null argument");
+    mms_buffer* b = find(h, name);
+    if (!b) return fail(h, std::string("mms_get_tensor: unknown buffer '") + name + "'");
+    memset(out, 0, sizeof(*out));
+    out->ptr = b->ptr;
+    for (int i = 0; i < b->ndim; i++) out->shape[i] = b->shape[i];
+    out->ndim = b->ndim;
+    out->dtype = b->dtype;
+    out->device = h->cfg.device;
+    return 0;
+}
+
+// the checks of mms_set_state (all ids are checked before anything is written); *buffer is the destination
+static inline int host_set_state_check(mms_host_state* h, const char* name, const void* src, const int64_t* env_ids, int64_t n, mms_buffer** buffer) {
+    if (!h || !name || !src) return fail(h, "mms_set_state: null argument");
+    mms_buffer* b = find(h, name);
+    if (!b) return fail(h, std::string("mms_set_state: unknown buffer '") + name + "'");
+    *buffer = b;
+    if (!env_ids) return 0;
+    if (b->row_bytes <= 0) return fail(h, "mms_set_state: buffer is not per-env");
+    if (n < 0) return fail(h, "mms_set_state: negative row count");
+    for (int64_t i = 0; i < n; i++)
+        if (env_ids[i] < 0 || env_ids[i] >= h->cfg.num_envs) return fail(h, "mms_set_state: env id out of range");
+    return 0;
+}
+
+static inline int host_bind_obs_out(mms_host_state* h, void* dst) {
+    if (null_handle(h, "mms_bind_obs_out")) return 1;
+    h->obs_out = (float*)dst;
+    return 0;
+}
+
+static inline int host_bind_obs_planes16(mms_host_state* h, void* planes, float scale) {
+    if (null_handle(h, "mms_bind_obs_planes16")) return 1;
+    if (!planes) { h->obs_planes = nullptr; return 0; }
+    if (h->cfg.task == MMS_TASK_MULTI_INGENUITY) return fail(h, "mms_bind_obs_planes16: not for the helicopter task (its policies' layers are 256 wide: exact-fp32 kernel)");
+    int e = 0;
+    if (!(scale > 0.f) || frexpf(scale, &e) != 0.5f) return fail(h, "mms_bind_obs_planes16: the scale must be a power of two");
+    if (!(h->cfg.clip_obs * scale <= 16384.f)) return fail(h, "mms_bind_obs_planes16: clip_observations x scale must not exceed 2^14 (fp16 planes)");
+    if ((addr(planes) & 15) != 0) return fail(h, "mms_bind_obs_planes16: the planes must be 16-byte aligned");
+    h->obs_planes = planes;
+    h->obs_planes_scale = scale;
+    return 0;
+}
+
+static inline int host_bind_actions(mms_host_state* h, const float* src) {
+    if (null_handle(h, "mms_bind_actions")) return 1;
+    if (src && (addr(src) & 7) != 0) return fail(h, "mms_bind_actions: the action tensor must be 8-byte aligned");
+    h->actions_in = src;
+    return 0;
+}
+
+// step_takes_head: the build's own answer to "this engine's step takes a head" (asked only with a handle and a head)
+static inline int host_bind_policy_head(mms_host_state* h, const mms_policy_head* head, bool step_takes_head) {
+    if (null_handle(h, "mms_bind_policy_head")) return 1;
+    if (!head) { h->head_on = false; return 0; }
+    if (h->dr_enabled || !step_takes_head)
+        return fail(h, "mms_bind_policy_head: not available for this engine (needs the 16-envs-per-workgroup TenAnt layout: 10 ants, num_envs a multiple "
+                       "of 16 and >= 16 per CU, no physical DR) -- launch mms_ppo_heads_act instead");
+    if (!head->hidden || !head->weight || !head->bias || !head->vhidden || !head->vweight || !head->vbias || !head->log_std || !head->counters)
+        return fail(h, "mms_bind_policy_head: null pointer (hidden, weight, bias, vhidden, vweight, vbias, log_std, counters are required)");
+    if (head->A != 8 * h->cfg.num_agents || head->H <= 0 || head->H % 512 != 0 || head->VH <= 0 || head->VH % 4 != 0)
+        return fail(h, "mms_bind_policy_head: A must be 8 x num_agents, H a multiple of 512, VH a multiple of 4");
+    if (((addr(head->hidden) | addr(head->weight) | addr(head->vhidden) | addr(head->vweight) | addr(head->weight_tiles)) & 15) != 0)
+        return fail(h, "mms_bind_policy_head: hidden, weight, weight_tiles, vhidden, vweight must be 16-byte aligned");
+    h->head = *head;
+    h->head_on = true;
+    return 0;
+}
+
+static inline int host_set_dr(mms_host_state* h, int32_t enable) {
+    if (null_handle(h, "mms_set_dr")) return 1;
+    if (enable && h->cfg.task == MMS_TASK_MULTI_INGENUITY) return fail(h, "mms_set_dr: the helicopter task has no randomised physical parameters");
+    h->dr_enabled = enable != 0;
+    return 0;
+}
+
+static inline int host_set_obs_outputs(mms_host_state* h, int32_t raw, int32_t clipped) {
+    if (null_handle(h, "mms_set_obs_outputs")) return 1;
+    h->write_raw_obs = raw != 0;
+    h->write_clipped_obs = clipped != 0;
+    return 0;
+}
+
+static inline int host_bind_rollout_out(mms_host_state* h, float* rew_out, uint8_t* done_out) {
+    if (null_handle(h, "mms_bind_rollout_out")) return 1;
+    h->rew_out = rew_out;
+    h->done_out = done_out;
+    return 0;
+}
+
+// ---- the operator entries' argument checks (after the build's device-argument check) -----------------------------------------------
+// x_pitch arguments are the effective pitch (the caller has replaced 0 by K).
+
+static inline std::string check_groups(const char* entry, int32_t groups) {
+    if (groups >= 1 && groups <= MMS_MAX_GROUPS) return {};
+    return std::string(entry) + ": groups must be 1.." + std::to_string(MMS_MAX_GROUPS);
+}
+
+static inline bool all_set(int n, const float* const* p) {
+    if (!p) return false;
+    for (int i = 0; i < n; i++)
+        if (!p[i]) return false;
+    return true;
+}
+
+static inline std::string check_gae_ppo_normalized(const float* rewards, const uint8_t* dones, const float* values, const float* last_values,
+                                                   const float* returns, const float* advantages, const double* stats, int32_t T, int64_t N) {
+    if (!rewards || !dones || !values || !last_values || !returns || !advantages || !stats || T < 1 || N < 1)
+        return "mms_gae_ppo_normalized: bad arguments (null pointer, T < 1 or N < 1)";
+    return {};
+}
+
+static inline std::string check_ppo_act(const float* mean, const float* log_std, const int64_t* counters, int64_t N, int32_t A) {
+    if (!mean || !log_std || !counters || N < 0 || A <= 0 || A > 128) return "mms_ppo_act: bad arguments (A must be in 1..128)";
+    return {};
+}
+
+static inline std::string check_ppo_heads_act(const float* hidden, const float* weight, const float* bias, int32_t H, const float* vhidden,
+                                              const float* vweight, const float* vbias, int32_t VH, const float* log_std, const int64_t* counters,
+                                              int64_t N, int32_t A) {
+    if (!hidden || !weight || !bias || !log_std || !counters || N < 0 || A <= 0 || A > 128 || H <= 0 || (H % 64) != 0)
+        return "mms_ppo_heads_act: bad arguments (A must be in 1..128, H a positive multiple of 64)";
+    if (vhidden && (!vweight || !vbias || VH <= 0 || (VH % 4) != 0))
+        return "mms_ppo_heads_act: the value head needs weight, bias and a hidden width that is a multiple of 4";
+    return {};
+}
+
+static inline std::string check_sac_heads_act(const float* hidden, int32_t H, const float* mu_weight, const float* mu_bias, const float* ls_weight,
+                                              const float* ls_bias, int32_t deterministic, const int64_t* counters, int64_t N, int32_t A) {
+    if (!hidden || !mu_weight || !mu_bias || !ls_weight || !ls_bias || (!deterministic && !counters) || N < 0 || A <= 0 || A > 128 || H <= 0 ||
+        (H % 64) != 0)
+        return "mms_sac_heads_act: bad arguments (A must be in 1..128, H a positive multiple of 64, counters required unless deterministic)";
+    if ((addr(hidden) | addr(mu_weight) | addr(ls_weight)) & 15) return "mms_sac_heads_act: hidden and both weight matrices must be 16-byte aligned";
+    return {};
+}
+
+static inline std::string check_linear2_act(int64_t M, int32_t N, int32_t K, const float* x0, const float* w0, const float* b0, const float* y0,
+                                            const float* x1, const float* w1, const float* b1, const float* y1, int32_t act) {
+    if (!x0 || !w0 || !b0 || !y0 || M < 0 || M > 0x7fffffff || N <= 0 || K <= 0 || (K % 4) != 0 || act < 0 || act > 3)
+        return "mms_linear2_act: bad arguments (K must be a positive multiple of 4, act 0..3)";
+    if ((x1 || w1 || b1 || y1) && !(x1 && w1 && b1 && y1)) return "mms_linear2_act: the second problem needs all four pointers";
+    return {};
+}
+
+static inline std::string check_split_planes(int64_t rows, int32_t K, int32_t x_pitch, const float* x, const void* planes) {
+    if (!x || !planes || rows < 0 || K <= 0 || x_pitch < K || (x_pitch % 4) != 0 || (addr(x) & 15) != 0 || (addr(planes) & 15) != 0)
+        return "mms_split_planes: bad arguments (x and planes 16-byte aligned, x_pitch >= K and a multiple of 4)";
+    return {};
+}
+
+static inline std::string check_split_planes_group(int32_t groups, int64_t rows, int32_t K, int32_t x_pitch, const float* const* x, void* const* planes) {
+    std::string bad = check_groups("mms_split_planes_group", groups);
+    if (!bad.empty()) return bad;
+    if (!x || !planes || rows < 0 || K <= 0 || x_pitch < K) return "mms_split_planes_group: bad arguments (x_pitch >= K)";
+    for (int g = 0; g < groups; g++)
+        if (!x[g] || !planes[g] || (addr(planes[g]) & 15) != 0 || (addr(x[g]) & 3) != 0)
+            return "mms_split_planes_group: null or misaligned pointer in a group (planes 16-byte aligned)";
+    return {};
+}
+
+// mms_linear_group_act_split (x_inv, w_inv, y_scale unused: scaled = false) and mms_linear_group_act_split16 (scaled = true)
+static inline std::string check_split_layer(bool scaled, int32_t groups, int64_t M, int32_t N, int32_t K, const void* const* x, const void* const* w,
+                                            const float* const* b, void* const* y, const float* const* x_inv, const float* const* w_inv,
+                                            const float* const* y_scale, int32_t act, int32_t out_mode, const float* const* ln_s,
+                                            const float* const* ln_stat_in, float* const* ln_part_out, const float* const* head_w,
+                                            float* const* head_part, const int32_t* head_dims) {
+    const char* fn = scaled ? "mms_linear_group_act_split16" : "mms_linear_group_act_split";
+    std::string bad = check_groups(fn, groups);
+    if (!bad.empty()) return bad;
+    if (!x || !w || !b || (scaled && (!x_inv || !w_inv)) || M < 0 || M > 0x7fffffff || (M % 128) != 0 || N <= 0 || (N % 128) != 0 || K <= 0 || act < 0 ||
+        act > 3 || out_mode < 0 || out_mode > 2 || (out_mode != 2 && !y) || (scaled && out_mode == 1 && !y_scale))
+        return std::string(fn) + ": bad arguments (M and N multiples of 128, act 0..3, out_mode 0..2" + (scaled ? ", x_inv, w_inv, y_scale with out_mode 1)" : ")");
+    const bool ln = ln_s || ln_stat_in || ln_part_out;
+    if (ln && (!ln_s || !ln_stat_in || !ln_part_out || act != 1 || out_mode == 0))
+        return std::string(fn) + ": the LayerNorm folds come together (ln_s, ln_stat_in, ln_part_out), with act = ELU and out_mode 1 or 2";
+    if (out_mode == 2 && (!ln || !head_w || !head_part || !head_dims)) return std::string(fn) + ": out_mode 2 needs the LayerNorm folds, head_w, head_part and head_dims";
+    for (int g = 0; g < groups; g++) {
+        if (!x[g] || !w[g] || !b[g] || (scaled && (!x_inv[g] || !w_inv[g])) || (out_mode != 2 && !y[g]) || (scaled && out_mode == 1 && !y_scale[g]) ||
+            (ln && (!ln_s[g] || !ln_stat_in[g] || !ln_part_out[g])) || (out_mode == 2 && (!head_w[g] || !head_part[g])))
+            return std::string(fn) + ": null pointer in a group";
+        uintptr_t bits = addr(x[g]) | addr(w[g]) | addr(b[g]);                   // 16 bytes; the (mean, rstd) pairs and slot partials 8
+        if (scaled) bits |= addr(w_inv[g]);
+        if (out_mode != 2) bits |= addr(y[g]);
+        if (ln) bits |= addr(ln_s[g]) | (addr(ln_stat_in[g]) << 1) | (addr(ln_part_out[g]) << 1);
+        if ((bits & 15) != 0) return std::string(fn) + ": operands must be 16-byte aligned";
+        if (out_mode == 2 && (head_dims[g] < 1 || head_dims[g] > 16)) return "split layer, out_mode 2: 1 <= head_dims[g] <= 16";
+    }
+    return {};
+}
+
+static inline std::string check_split_planes16_group(int32_t groups, int64_t rows, int32_t K, int32_t x_pitch, const float* const* x, void* const* planes,
+                                                     float* const* scale, float* const* inv, int32_t nchains, int32_t L, const float* const* chain,
+                                                     float* const* chain_scale, float* const* chain_inv, float* const* stat) {
+    std::string bad = check_groups("mms_split_planes16_group", groups);
+    if (!bad.empty()) return bad;
+    if (!x || !planes || !scale || !inv || rows < 0 || K <= 0 || x_pitch < K || nchains < 0 || L < 0 || (nchains > 0 && (L < 1 || !chain || !chain_scale || !chain_inv)))
+        return "mms_split_planes16_group: bad arguments (x_pitch >= K; nchains > 0 needs L >= 1, chain, chain_scale, chain_inv)";
+    for (int g = 0; g < groups; g++) {
+        if (!x[g] || !planes[g] || (addr(planes[g]) & 15) != 0 || (addr(x[g]) & 3) != 0 || (nchains > 0 && (!chain[g] || !chain_scale[g] || !chain_inv[g])))
+            return "mms_split_planes16_group: null or misaligned pointer in a group (planes 16-byte aligned)";
+        if (stat && (!stat[g] || (addr(stat[g]) & 7) != 0)) return "mms_split_planes16_group: null or misaligned stat pointer in a group";
+    }
+    return {};
+}
+
+static inline std::string check_weight_planes16_group(int32_t groups, const int64_t* N, const int32_t* K, const float* const* w, void* const* planes,
+                                                      float* const* scale, float* const* inv) {
+    std::string bad = check_groups("mms_weight_planes16_group", groups);
+    if (!bad.empty()) return bad;
+    if (!N || !K || !w || !planes || !scale || !inv) return "mms_weight_planes16_group: bad arguments (null array)";
+    for (int g = 0; g < groups; g++) {
+        if (N[g] < 0 || K[g] <= 0) return "mms_weight_planes16_group: bad shape in a group (N >= 0, K > 0)";
+        if (!w[g] || !planes[g] || !scale[g] || !inv[g] || (addr(planes[g]) & 15) != 0 || (addr(w[g]) & 3) != 0 || (addr(inv[g]) & 15) != 0)
+            return "mms_weight_planes16_group: null or misaligned pointer in a group (planes and inv 16-byte aligned)";
+    }
+    return {};
+}
+
+static inline std::string check_chain_refresh16(int32_t nchains, int32_t L, const float* const* l1, const int32_t* n, const float* chain, float bound0,
+                                                int64_t rows, const float* chain_scale, const float* chain_inv) {
+    if (nchains < 1 || L < 1 || (int64_t)nchains * L > MMS_MAX_GROUPS || !l1 || !n || !chain || rows < 0 || (rows > 0 && (!chain_scale || !chain_inv || !(bound0 >= 0.f))))
+        return "mms_chain_refresh16: bad arguments (nchains, L >= 1, nchains * L <= " + std::to_string(MMS_MAX_GROUPS) + "; rows > 0 needs chain_scale, chain_inv, bound0 >= 0)";
+    for (int e = 0; e < nchains * L; e++)
+        if (!l1[e] || n[e] < 0) return "mms_chain_refresh16: null pointer or negative count in an entry";
+    return {};
+}
+
+static inline std::string check_fold_planes16_group(int32_t groups, const int64_t* N, const int32_t* K, const float* const* w, void* const* planes,
+                                                    float* const* inv) {
+    std::string bad = check_groups("mms_fold_planes16_group", groups);
+    if (!bad.empty()) return bad;
+    if (!N || !K || !w) return "mms_fold_planes16_group: bad arguments (null array)";
+    for (int g = 0; g < groups; g++) {
+        if (N[g] < 0 || K[g] <= 0) return "mms_fold_planes16_group: bad shape in a group (N >= 0, K > 0)";
+        if (!w[g] || (planes && planes[g] && (!inv || !inv[g])) || (planes && (addr(planes[g]) & 15) != 0))
+            return "mms_fold_planes16_group: null or misaligned pointer in a group (planes 16-byte aligned and with inv)";
+    }
+    return {};
+}
+
+static inline std::string check_fold_scales16_group(int32_t groups, const float* const* rb, const int32_t* n, int64_t M) {
+    std::string bad = check_groups("mms_fold_scales16_group", groups);
+    if (!bad.empty()) return bad;
+    if (!rb || !n || M < 0) return "mms_fold_scales16_group: bad arguments";
+    for (int g = 0; g < groups; g++)
+        if (!rb[g] || n[g] < 0) return "mms_fold_scales16_group: null pointer or negative count in a group";
+    return {};
+}
+
+static inline std::string check_layer_clock_probe(const uint64_t* out, int32_t slots) {
+    if (out && slots < 1) return "mms_layer_clock_probe: slots must be >= 1 with an output buffer";
+    if (out && (addr(out) & 7) != 0) return "mms_layer_clock_probe: the buffer must be 8-byte aligned";
+    return {};
+}
+
+static inline std::string check_row_stats_chan_group(int32_t groups, int64_t M, int32_t slots, const float* const* part, float* const* stat) {
+    std::string bad = check_groups("mms_row_stats_chan_group", groups);
+    if (!bad.empty()) return bad;
+    if (!part || !stat || M < 0 || slots < 1) return "mms_row_stats_chan_group: bad arguments";
+    for (int g = 0; g < groups; g++)
+        if (!part[g] || !stat[g]) return "mms_row_stats_chan_group: null pointer in a group";
+    return {};
+}
+
+static inline std::string check_marl_heads_finish(int32_t groups, int64_t M, int32_t slots, const float* const* part, const float* const* head_part,
+                                                  const float* const* hs, const float* const* hc, const int32_t* A, float* const* out,
+                                                  const int32_t* out_pitch) {
+    std::string bad = check_groups("mms_marl_heads_finish", groups);
+    if (!bad.empty()) return bad;
+    if (!part || !head_part || !hs || !hc || !A || !out || M < 0 || slots < 1) return "mms_marl_heads_finish: bad arguments";
+    for (int g = 0; g < groups; g++) {
+        if (!part[g] || !head_part[g] || !hs[g] || !hc[g] || !out[g] || A[g] < 1 || A[g] > 16)
+            return "mms_marl_heads_finish: null pointer or output width outside 1..16 in a group";
+        if ((addr(head_part[g]) & 15) != 0 || (addr(part[g]) & 7) != 0)
+            return "mms_marl_heads_finish: head_part must be 16-byte aligned and part 8-byte aligned (read as float4 / float2)";
+        if (out_pitch && out_pitch[g] < A[g]) return "mms_marl_heads_finish: out_pitch below the output width";
+    }
+    return {};
+}
+
+static inline std::string check_linear_group_act(int32_t groups, int64_t M, int32_t N, int32_t K, const float* const* x, const float* const* w,
+                                                 const float* const* b, float* const* y, int32_t act, const float* const* ln_s,
+                                                 const float* const* ln_stat_in, float* const* ln_part_out) {
+    std::string bad = check_groups("mms_linear_group_act", groups);
+    if (!bad.empty()) return bad;
+    if (!x || !w || !b || !y || M < 0 || M > 0x7fffffff || N <= 0 || K <= 0 || (K % 4) != 0 || act < 0 || act > 3)
+        return "mms_linear_group_act: bad arguments (K must be a positive multiple of 4, act 0..3)";
+    if ((ln_stat_in != nullptr) != (ln_s != nullptr)) return "mms_linear_group_act: ln_stat_in and ln_s come together";
+    if ((ln_stat_in || ln_part_out) && (act != 1 || M % 128 != 0 || N % 128 != 0 || K < 8))
+        return "mms_linear_group_act: the LayerNorm folds need act = ELU, M and N multiples of 128";
+    for (int g = 0; g < groups; g++)
+        if (!x[g] || !w[g] || !b[g] || !y[g] || (ln_s && (!ln_s[g] || !ln_stat_in[g])) || (ln_part_out && !ln_part_out[g]))
+            return "mms_linear_group_act: null pointer in a group";
+    return {};
+}
+
+static inline std::string check_row_stats_group(int32_t groups, int64_t M, int32_t slots, int32_t width, const float* const* part, float* const* stat) {
+    std::string bad = check_groups("mms_row_stats_group", groups);
+    if (!bad.empty()) return bad;
+    if (!part || !stat || M < 0 || slots < 1 || width < 1) return "mms_row_stats_group: bad arguments";
+    for (int g = 0; g < groups; g++)
+        if (!part[g] || !stat[g]) return "mms_row_stats_group: null pointer in a group";
+    return {};
+}
+
+static inline std::string check_row_moments_group(int32_t groups, int64_t M, int32_t K, int32_t x_pitch, const float* const* x, float* const* stat) {
+    std::string bad = check_groups("mms_row_moments_group", groups);
+    if (!bad.empty()) return bad;
+    if (!x || !stat || M < 0 || K <= 0 || K > 4096 || x_pitch < K) return "mms_row_moments_group: bad arguments (1 <= K <= 4096)";
+    for (int g = 0; g < groups; g++)
+        if (!x[g] || !stat[g]) return "mms_row_moments_group: null pointer in a group";
+    return {};
+}
+
+static inline std::string check_layernorm_group(int32_t groups, int64_t M, int32_t K, int32_t Kp, int32_t x_pitch, const float* const* x,
+                                                const float* const* gamma, const float* const* beta, float* const* y) {
+    std::string bad = check_groups("mms_layernorm_group", groups);
+    if (!bad.empty()) return bad;
+    if (!x || !gamma || !beta || !y || M < 0 || K <= 0 || K > 4096 || Kp < K || x_pitch < K)
+        return "mms_layernorm_group: bad arguments (1 <= K <= 4096, Kp >= K, x_pitch >= K or 0)";
+    for (int g = 0; g < groups; g++) {
+        if (!x[g] || !gamma[g] || !beta[g] || !y[g]) return "mms_layernorm_group: null pointer in a group";
+        if ((Kp != K || x_pitch != K) && x[g] == y[g]) return "mms_layernorm_group: in place needs Kp == x_pitch == K";
+    }
+    return {};
+}
+
+static inline std::string check_marl_heads_act(int32_t groups, int64_t M, int32_t H, const float* const* h, const float* const* gamma,
+                                               const float* const* beta, const float* const* w, const float* const* b, const int32_t* A,
+                                               float* const* out, const int32_t* out_pitch) {
+    std::string bad = check_groups("mms_marl_heads_act", groups);
+    if (!bad.empty()) return bad;
+    if (!h || !gamma || !beta || !w || !b || !A || !out || M < 0 || H <= 0 || H > 1024) return "mms_marl_heads_act: bad arguments (1 <= H <= 1024)";
+    for (int g = 0; g < groups; g++) {
+        if (!h[g] || !gamma[g] || !beta[g] || !w[g] || !b[g] || !out[g] || A[g] < 1 || A[g] > 16)
+            return "mms_marl_heads_act: null pointer in a group, or outputs outside 1..16";
+        if (out_pitch && out_pitch[g] < A[g]) return "mms_marl_heads_act: out_pitch below the number of outputs";
+    }
+    return {};
+}
+
+// mms_mlp_grad and mms_mlp_grad_rop: the shapes, then (workspace NULL is the size query: nothing else is read) the operands.  The
+// workspace's size and alignment are the HIP build's own; the CPU build needs none.
+static inline std::string check_mlp_shapes(const char* entry, int32_t layers, int64_t M, const int32_t* dims, const int64_t* ws_bytes) {
+    bool ok = dims && ws_bytes && layers >= 2 && layers <= mms::kMlpMaxLayers && M >= 1 && M <= mms::kMlpMaxRows;
+    for (int l = 0; ok && l <= layers; l++) ok = dims[l] >= 1 && dims[l] <= 65536;
+    if (ok) return {};
+    return std::string(entry) + ": bad arguments (2 <= layers <= " + std::to_string(mms::kMlpMaxLayers) + ", 1 <= M <= " + std::to_string(mms::kMlpMaxRows) +
+           ", dims[0..layers] in 1..65536, ws_bytes required)";
+}
+
+static inline std::string check_mlp_grad(int32_t layers, int64_t M, const int32_t* dims, const float* x, const float* const* h, const float* const* w,
+                                         const float* g, float* const* dw, float* const* db, float* const* d_out, float* const* e_out,
+                                         const void* workspace, const int64_t* ws_bytes) {
+    std::string bad = check_mlp_shapes("mms_mlp_grad", layers, M, dims, ws_bytes);
+    if (!bad.empty() || !workspace) return bad;
+    if (!x || !g || !all_set(layers - 1, h) || !all_set(layers, w) || !all_set(layers, dw) || !all_set(layers, db) ||
+        (d_out && !all_set(layers - 1, d_out)) || (e_out && !all_set(layers - 1, e_out)))
+        return "mms_mlp_grad: null pointer (x, g, h[layers-1], w / dw / db[layers]; d_out / e_out all or none)";
+    return {};
+}
+
+static inline std::string check_mlp_grad_rop(int32_t layers, int64_t M, const int32_t* dims, const float* x, const float* const* h, const float* const* w,
+                                             const float* const* v, const float* const* c, const float* g, const float* const* d,
+                                             const float* const* e, const float* rmu, float* const* rdw, float* const* rdb, const void* workspace,
+                                             const int64_t* ws_bytes) {
+    std::string bad = check_mlp_shapes("mms_mlp_grad_rop", layers, M, dims, ws_bytes);
+    if (!bad.empty() || !workspace) return bad;
+    if (!x || !g || !rmu || !all_set(layers - 1, h) || !all_set(layers, w) || !all_set(layers, v) || !all_set(layers, c) || !all_set(layers - 1, d) ||
+        !all_set(layers - 1, e) || !all_set(layers, rdw) || !all_set(layers, rdb))
+        return "mms_mlp_grad_rop: null pointer (x, g, rmu, h / d / e[layers-1], w / v / c / rdw / rdb[layers])";
+    return {};
+}

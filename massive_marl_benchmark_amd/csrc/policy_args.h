@@ -3,9 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/mms.h"
+
 namespace mms {
 
-constexpr int kMaxGroups = 32;      // networks per grouped launch (MMS_MAX_GROUPS in include/mms.h)
+constexpr int kMaxGroups = MMS_MAX_GROUPS;      // networks per grouped launch
 
 // y_g = act(x_g w_g^T + b_g) for g < groups: one launch for all of them (same M, N, K)
 struct LinearArgs {

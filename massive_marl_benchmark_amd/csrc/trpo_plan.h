@@ -4,10 +4,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
-namespace mms {
+#include "mms_host.h"   // kMlpMaxLayers, kMlpMaxRows: the limits the C ABI checks on both builds
 
-constexpr int kMlpMaxLayers = 8;
-constexpr int64_t kMlpMaxRows = 65535 * 32 / 128 * 128;   // rows: the 32-row chunks of the padded batch index a grid dimension
+namespace mms {
 
 struct MlpPlan {
     int L, MC;                   // layers; 32-row chunks of the padded batch

@@ -1941,6 +1941,50 @@ def test_abi_error_paths_and_indexed_set_state(torch_cuda):
     eng.close()
 
 
+# the calls of tests/abi_errors.py whose failure IS the device argument: each build names its own device rule, in its own words
+DEVICE_ARGUMENT_CALLS = ["mms_create, the other library's device", "mms_create, device out of range", "mms_gae_ppo, the other library's device"]
+
+
+def test_both_builds_refuse_in_the_same_words(torch_cuda):
+    """The CPU build stands in for the HIP build's boundary on machines without a GPU, so a call one of them refuses the other refuses with
+    the same message (csrc/mms_host.h holds each rule once): the list of tests/abi_errors.py on both builds, message against message.
+    The exceptions are the calls that fail on the device argument itself, and the one call only the HIP build can make (an ordinal
+    past the last device)."""
+    import abi_errors
+    from massive_marl_benchmark_amd import _lib
+    hip, cpu = [], []
+    assert abi_errors.check_abi_error_paths(_lib.lib(), 0, hip) >= 40
+    assert abi_errors.check_abi_error_paths(_lib.lib_cpu(), -1, cpu) >= 40
+    hip, cpu = dict(hip), dict(cpu)
+    assert set(hip) - set(cpu) == {"mms_create, device out of range"} and not set(cpu) - set(hip)
+    assert set(DEVICE_ARGUMENT_CALLS) <= set(hip)
+    compared = [k for k in cpu if k not in DEVICE_ARGUMENT_CALLS]
+    assert len(compared) >= 40
+    for k in compared:
+        assert hip[k] == cpu[k], (k, hip[k], cpu[k])
+
+
+@pytest.mark.parametrize("task,kw", [("TenAnt", {}), ("OneAnt", {}), ("MultiAntCircle", {}), ("MultiIngenuity", {}), ("TenAnt", {"num_agents": 100})])
+def test_both_builds_construct_the_same_scene(torch_cuda, task, kw):
+    """Right after mms_create every named buffer is bit-identical between the builds (one scene function, csrc/mms_host.h), for a shard in
+    the middle of a larger grid: non-zero env_offset, total_envs above num_envs."""
+    from massive_marl_benchmark_amd.engine import Engine
+    names = ["actions", "obs", "obs_clipped", "rew", "reset", "progress", "reset_count", "root_states", "initial_root_states", "dof_state",
+             "env_origin", "prev", "reset_noise", "foot_sensors", "dr_params"]
+    args = dict(num_envs=24, seed=5, env_offset=37, total_envs=200, **kw)
+    hip, cpu = Engine(task, device=0, **args), Engine(task, device="cpu", **args)
+    try:
+        origin = hip.tensor("env_origin").cpu()
+        assert float(origin[:, 0].max()) > 0 and float(origin[:, 1].min()) > 0       # (a shard away from the grid's first row)
+        for name in names:
+            a, b = hip.tensor(name).cpu(), cpu.tensor(name)
+            assert a.dtype == b.dtype and a.shape == b.shape, name
+            assert torch_cuda.equal(a.view(torch_cuda.uint8), b.view(torch_cuda.uint8)), name
+    finally:
+        hip.close()
+        cpu.close()
+
+
 def test_bench_under_torchrun_single_rank(torch_cuda):
     """bench.py launched the way the driver launches the multi-GPU runs -- `python -m torch.distributed.run --nproc-per-node 1
     --master-addr 127.0.0.1 ... bench.py --gpus 1` as a fresh child process -- takes the RCCL path (init_process_group("nccl"),
