@@ -38,6 +38,8 @@
  *     (algorithms/marl/actor_critic.py:43-69, 137-155; runner.py:186-216)  mms_row_stats_group, mms_marl_heads_act
  *   SquashedGaussianMLPActor heads + rsample + log-probability          mms_sac_heads_act
  *     (algorithms/rl/sac/module.py:23-61; sac.py:166, 374-376)
+ *   MLPQFunction last layer + min + Bellman backup (Q target)           mms_q_heads_backup
+ *     (rl/sac/sac.py:379-382; td3/td3.py:370-373; ddpg/ddpg.py:368-369)
  *   TRPO actor backward: torch.autograd.grad of the surrogate loss      mms_mlp_grad
  *     (algorithms/rl/trpo/trpo.py:290) and the create_graph=True
  *     gradient of the KL (:427)
@@ -322,6 +324,31 @@ int mms_sac_heads_act(int device, const float* hidden, int32_t H,
                       float* actions_out, float* act_slot, float* logp_slot,
                       float* u_slot, float* mu_slot, float* log_std_slot,
                       int64_t N, int32_t A, void* hip_stream);
+
+/* The tail of the off-policy Q target in ONE launch: the last layer of one or two critics (MLPQFunction's Linear(H, 1),
+ * algorithms/rl/{ddpg,td3,sac}/module.py `q.q.<last>`), the min of the two and the Bellman backup -- what sac.py:379-382,
+ * td3.py:370-373 and ddpg.py:368-369 evaluate under no_grad as two [M,H] x [H,1] products, two bias adds, a min and five
+ * element-wise launches.
+ *   q_g[i]    = dot(h_g[i, :], w_g) + b_g[0]                            g < G (G = 2 when h1 is given)
+ *   qmin[i]   = G == 2 ? min(q_0[i], q_1[i]) : q_0[i]
+ *   backup[i] = reward[i] + gamma * (1 - done[i]) * (qmin[i] - alpha * logp[i])     (logp == NULL: no alpha term -- TD3, DDPG)
+ * h_g [M,H] f32 is the output of the critic's last hidden activation; w_g [1,H] and b_g [1] are torch's parameters, read in place
+ * on every call (the polyak update rewrites the target's after every minibatch, sac.py:354-359).  reward [M] f32, done [M] uint8
+ * (ReplayBuffer.dones; non-zero = done), logp [M] f32.  Destinations, any of which may be NULL (no store), at least one given:
+ * q0_out, q1_out, backup [M].  backup == NULL is the forward alone: reward, done and logp are not read.  backup needs reward and done.
+ * h1 = w1 = b1 = q1_out = NULL runs one network; the second network needs h1, w1 and b1 together.
+ * The sum over k has a fixed order that depends on H alone and there are no atomics: q_g[i] is a function of row i and the
+ * parameters, not of M or of where the row sits in the call; a done row's backup is reward[i] exactly.  Inputs are taken to be
+ * finite: the min is fminf in finite-math code, so a NaN in one critic's output does not propagate as torch.min's would.  Rows past
+ * M are neither read nor written.  H a positive multiple of 64 up to MMS_Q_MAX_H (both weight rows are staged in LDS), h_g and w_g
+ * 16-byte aligned, M >= 0 (M == 0 succeeds and writes nothing).  Bad arguments return non-zero with mms_last_error(NULL) and
+ * write nothing. */
+#define MMS_Q_MAX_H 4096
+int mms_q_heads_backup(int device, int64_t M, int32_t H,
+                       const float* h0, const float* w0, const float* b0, float* q0_out,
+                       const float* h1, const float* w1, const float* b1, float* q1_out,      /* all NULL: one network */
+                       const float* reward, const uint8_t* done, const float* logp, float gamma, float alpha,
+                       float* backup, void* hip_stream);
 
 /* One hidden layer of the PPO policy for BOTH networks in one launch (module.py:27-52: nn.Linear + activation, actor and
  * critic of the same shape): y_g = act(x_g @ w_g^T + b_g), g = 0, 1, on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact

@@ -7,7 +7,8 @@ When no gradient is wanted on the HIP device (the collection's `act`, sac.py:166
 sac.py:374-376), the actor runs as launches of this build: the hidden layers through `mms_linear2_act` (ddpg.module.fused_mlp_forward)
 and the head -- mu_layer, log_std_layer, clamp, rsample, the tanh-corrected log-probability and the scaled action -- as ONE
 `mms_sac_heads_act` launch.  Anything else (autograd for compute_loss_pi, the CPU, other dtypes, shapes the kernels do not take)
-is plain torch with the same formulae.
+is plain torch with the same formulae.  The critics under no_grad run fused as well (`MLPQFunction.forward`, `q_backup`: see
+ddpg.module); `fused_q=False` keeps them on torch.
 
 The noise of the fused path is this build's counter-based generator (seed, global row = row_offset + row, per-row draw counter),
 not torch's Philox: sampled actions differ from the reference's draw for the same torch seed, their distribution and
@@ -25,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from .... import _lib
-from ..ddpg.module import fused_mlp_forward, mlp
+from ..ddpg.module import fused_mlp_forward, fused_q_backup, fused_q_forward, mlp
 
 LOG_STD_MAX = 2
 LOG_STD_MIN = -20
@@ -127,23 +128,33 @@ class SquashedGaussianMLPActor(nn.Module):
 
 
 class MLPQFunction(nn.Module):
-    def __init__(self, obs_dim, act_dim, hidden_sizes, activation):
+    def __init__(self, obs_dim, act_dim, hidden_sizes, activation, fused_q=True):
         super().__init__()
         self.q = mlp([obs_dim + act_dim] + list(hidden_sizes) + [1], activation)
+        self.fused_q = bool(fused_q)       # False: torch always
 
     def forward(self, obs, act):
+        out = fused_q_forward([self], obs, act) if self.fused_q else None      # no gradient wanted on the HIP device: ddpg.module
+        if out is not None:
+            return out[0]
         return self.q(torch.cat([obs, act], dim=-1))      # [..., 1], as the reference returns it
 
 
 class MLPActorCritic(nn.Module):
-    def __init__(self, observation_space, action_space, hidden_sizes=(256, 256), activation=nn.ELU, seed=None, row_offset=0):
+    def __init__(self, observation_space, action_space, hidden_sizes=(256, 256), activation=nn.ELU, seed=None, row_offset=0, fused_q=True):
         super().__init__()
         obs_dim, act_dim = observation_space.shape[0], action_space.shape[0]
         act_limit = action_space.high[0]
         self.pi = SquashedGaussianMLPActor(obs_dim, act_dim, hidden_sizes, activation, act_limit, seed=0, row_offset=row_offset)
-        self.q1 = MLPQFunction(obs_dim, act_dim, hidden_sizes, activation)
-        self.q2 = MLPQFunction(obs_dim, act_dim, hidden_sizes, activation)
+        self.fused_q = bool(fused_q)
+        self.q1 = MLPQFunction(obs_dim, act_dim, hidden_sizes, activation, self.fused_q)
+        self.q2 = MLPQFunction(obs_dim, act_dim, hidden_sizes, activation, self.fused_q)
         self.pi.seed = _draw_seed() if seed is None else int(seed)  # after every layer: initialisation identical to the reference's
+
+    def q_backup(self, o2, a2, r, d, gamma, alpha=None, logp=None):
+        """r + gamma * (1 - d) * (min(q1(o2, a2), q2(o2, a2)) - alpha * logp), no gradient: called on the target copy it is
+        sac.py:379-382 in one line -- both critics per launch, the min and the backup inside the last one (ddpg.module.fused_q_backup)."""
+        return fused_q_backup([self.q1, self.q2], o2, a2, r, d, gamma, alpha, logp)
 
     def act(self, obs, deterministic=False):
         with torch.no_grad():

@@ -18,6 +18,7 @@
 
 #include "../mms_host.h"
 #include "../rollout_lane.h"
+#include "../q_lane.h"
 #include "../sac_lane.h"
 #include "lane_step.h"
 
@@ -288,6 +289,32 @@ MMS_API int mms_sac_heads_act(int device, const float* hidden, int32_t H, const 
             logp_slot[row] = lane[0];
         }
         if (!deterministic) counters[row] = c + 1;
+    }
+    return 0;
+}
+MMS_API int mms_q_heads_backup(int device, int64_t M, int32_t H, const float* h0, const float* w0, const float* b0, float* q0_out, const float* h1,
+                               const float* w1, const float* b1, float* q1_out, const float* reward, const uint8_t* done, const float* logp,
+                               float gamma, float alpha, float* backup, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_q_heads_backup(M, H, h0, w0, b0, q0_out, h1, w1, b1, q1_out, reward, done, backup))) return 1;
+    const int G = h1 ? 2 : 1;
+    const float* hs[2] = {h0, h1};
+    const float* ws[2] = {w0, w1};
+    const float* bs[2] = {b0, b1};
+    float* qs[2] = {q0_out, q1_out};
+#pragma omp parallel for schedule(static)
+    for (int64_t row = 0; row < M; row++) {
+        float q[2] = {0.f, 0.f};
+        for (int g = 0; g < G; g++) {
+            float s = 0.f;
+            for (int k = 0; k < H; k++) s = fmaf(hs[g][row * (int64_t)H + k], ws[g][k], s);
+            q[g] = mms::q_value(s, bs[g][0]);
+            if (qs[g]) qs[g][row] = q[g];
+        }
+        if (backup) {
+            const float qm = G == 2 ? mms::q_min(q[0], q[1]) : q[0];
+            backup[row] = mms::q_backup(reward[row], done[row], qm, logp != nullptr, logp ? logp[row] : 0.f, gamma, alpha);
+        }
     }
     return 0;
 }

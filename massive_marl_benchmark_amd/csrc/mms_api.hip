@@ -24,6 +24,8 @@ hipError_t launch_ppo_head_act(const float*, const float*, const float*, int, co
                                int64_t*, int64_t, int, float*, float*, float*, float*, float*, float*, int64_t, int, hipStream_t);
 hipError_t launch_sac_head_act(const float*, int, const float*, const float*, const float*, const float*, float, float, int, uint64_t, int64_t*, int64_t,
                                float*, float*, float*, float*, float*, float*, int64_t, int, hipStream_t);
+hipError_t launch_q_heads_backup(int, int64_t, int, const float* const*, const float* const*, const float* const*, float* const*, const float*,
+                                 const uint8_t*, const float*, float, float, float*, hipStream_t);
 struct MlpPlan;
 }  // namespace mms
 
@@ -320,6 +322,20 @@ __attribute__((visibility("default"))) int mms_sac_heads_act(int device, const f
     if (refused(check_sac_heads_act(hidden, H, mu_weight, mu_bias, ls_weight, ls_bias, deterministic, counters, N, A))) return 1;
     MMS_FREE(mms::launch_sac_head_act(hidden, H, mu_weight, mu_bias, ls_weight, ls_bias, act_limit, epsilon, deterministic, seed, counters, row_offset,
                                       actions_out, act_slot, logp_slot, u_slot, mu_slot, log_std_slot, N, A, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_q_heads_backup(int device, int64_t M, int32_t H, const float* h0, const float* w0, const float* b0,
+                                                              float* q0_out, const float* h1, const float* w1, const float* b1, float* q1_out,
+                                                              const float* reward, const uint8_t* done, const float* logp, float gamma,
+                                                              float alpha, float* backup, void* s) {
+    MMS_DEV(device)
+    if (refused(check_q_heads_backup(M, H, h0, w0, b0, q0_out, h1, w1, b1, q1_out, reward, done, backup))) return 1;
+    const float* h[2] = {h0, h1};
+    const float* w[2] = {w0, w1};
+    const float* b[2] = {b0, b1};
+    float* q[2] = {q0_out, q1_out};
+    MMS_FREE(mms::launch_q_heads_backup(h1 ? 2 : 1, M, H, h, w, b, q, reward, done, backup ? logp : nullptr, gamma, alpha, backup, (hipStream_t)s));
     return 0;
 }
 

@@ -319,6 +319,19 @@ static inline std::string check_sac_heads_act(const float* hidden, int32_t H, co
     return {};
 }
 
+// all checks before any work; G is 2 when the second network is given
+static inline std::string check_q_heads_backup(int64_t M, int32_t H, const float* h0, const float* w0, const float* b0, const float* q0_out,
+                                               const float* h1, const float* w1, const float* b1, const float* q1_out, const float* reward,
+                                               const uint8_t* done, const float* backup) {
+    if (!h0 || !w0 || !b0 || M < 0 || H <= 0 || (H % 64) != 0 || H > MMS_Q_MAX_H)
+        return "mms_q_heads_backup: bad arguments (h0, w0, b0 required, M >= 0, H a positive multiple of 64 up to " + std::to_string(MMS_Q_MAX_H) + ")";
+    if ((h1 || w1 || b1 || q1_out) && !(h1 && w1 && b1)) return "mms_q_heads_backup: the second network needs h1, w1 and b1 (or all four NULL: one network)";
+    if ((addr(h0) | addr(w0) | addr(h1) | addr(w1)) & 15) return "mms_q_heads_backup: hidden activations and weights must be 16-byte aligned";
+    if (!q0_out && !q1_out && !backup) return "mms_q_heads_backup: no destination (q0_out, q1_out, backup all NULL)";
+    if (backup && (!reward || !done)) return "mms_q_heads_backup: the backup needs reward and done";
+    return {};
+}
+
 static inline std::string check_linear2_act(int64_t M, int32_t N, int32_t K, const float* x0, const float* w0, const float* b0, const float* y0,
                                             const float* x1, const float* w1, const float* b1, const float* y1, int32_t act) {
     if (!x0 || !w0 || !b0 || !y0 || M < 0 || M > 0x7fffffff || N <= 0 || K <= 0 || (K % 4) != 0 || act < 0 || act > 3)

@@ -1,0 +1,157 @@
+"""Checks of mms_q_heads_backup (include/mms.h) shared by the CPU-build tests (test_q_target.py) and the GPU tests
+(test_q_target_gpu.py): seeded problems, the launch through ctypes, the float64 statement and the gates.
+
+Gates.  q against float64: |q - q64| <= 1e-6 s on the CPU build (s_i = sum_k |h_ik w_k| + |b|, the gate of
+test_sac_actor.py::test_cpu_build_against_float64 for the same kind of chain), e <= 2 e_torch + 1e-6 on the device with
+e = max |q - q64| / s and e_torch the same for torch.nn.functional.linear in fp32 (test_sac_actor_gpu.py::test_kernel_against_float64).
+The backup is compared with the float64 evaluation of the formula FROM THE CALL'S OWN q_out, so that the dot product's error is
+out of it: |backup - backup64| <= 1e-6 (|r| + gamma (|qmin| + alpha |logp|)) -- five roundings of at most 2^-24 each on terms
+bounded by that scale give 3e-7.  gamma and alpha cross the ABI as fp32: the float64 statement uses the fp32-rounded values."""
+import ctypes
+
+import numpy as np
+import torch
+
+from massive_marl_benchmark_amd import _lib
+
+SENTINEL = 7.0
+
+
+def problem(M, H, G, seed=0, device="cpu"):
+    """h_g [M,H] (ELU outputs of N(0,1)), w_g [1,H] ~ N(0, 1/H), b_g [1]: the row scale s_i = sum_k |h_ik w_k| + |b| is O(1).
+    r [M] ~ N(0,1), d [M] uint8 with both values present (from M = 2 on), logp [M] ~ N(-3, 2)."""
+    g = torch.Generator().manual_seed(1000 * seed + 7 * H + M + G)
+    hs = [torch.nn.functional.elu(torch.randn(M, H, generator=g)) for _ in range(G)]
+    ws = [torch.randn(1, H, generator=g) * H ** -0.5 for _ in range(G)]
+    bs = [torch.randn(1, generator=g) * 0.1 for _ in range(G)]
+    r = torch.randn(M, generator=g)
+    d = (torch.rand(M, generator=g) < 0.3).to(torch.uint8)
+    if M >= 2:
+        d[0], d[1] = 1, 0
+    logp = torch.randn(M, generator=g) * 2 - 3
+    to = lambda t: t.to(device)
+    return dict(h=[to(t) for t in hs], w=[to(t) for t in ws], b=[to(t) for t in bs], r=to(r), d=to(d), logp=to(logp))
+
+
+def p(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def call(L, device, stream, M, H, h, w, b, q_out, r, d, logp, gamma, alpha, backup):
+    """The raw entry: lists of one or two tensors (or None) for h, w, b, q_out; returns the return code."""
+    two = len(h) == 2
+    g1 = lambda xs: p(xs[1]) if two else None
+    return L.mms_q_heads_backup(device, M, H, p(h[0]), p(w[0]), p(b[0]), p(q_out[0]), g1(h), g1(w), g1(b), g1(q_out), p(r), p(d), p(logp),
+                                float(gamma), float(alpha), p(backup), stream)
+
+
+def run(L, device, stream, pr, *, G=None, with_q=True, with_backup=True, with_logp=True, gamma=0.99, alpha=0.2, rows=None):
+    """One call on the first `rows` rows of problem `pr`; destinations pre-filled with SENTINEL.  Returns (q list, backup)."""
+    G = len(pr["h"]) if G is None else G
+    M, H = pr["h"][0].shape
+    M = M if rows is None else rows
+    dev = pr["h"][0].device
+    q = [torch.full((M,), SENTINEL, device=dev) if with_q else None for _ in range(G)]
+    backup = torch.full((M,), SENTINEL, device=dev) if with_backup else None
+    use = with_backup
+    rc = call(L, device, stream, M, H, pr["h"][:G], pr["w"][:G], pr["b"][:G], q, pr["r"] if use else None, pr["d"] if use else None,
+              pr["logp"] if use and with_logp else None, gamma, alpha, backup)
+    _lib.check(rc, None, "mms_q_heads_backup", L)
+    return q, backup
+
+
+def f64_q(pr, g):
+    """q_g in float64 and the row scale s."""
+    h, w, b = (t.detach().double() for t in (pr["h"][g], pr["w"][g], pr["b"][g]))           # (on the tensors' own device: [65536, 1024] rows)
+    return (h @ w[0] + b[0]).cpu().numpy(), (h.abs() @ w[0].abs() + b[0].abs()).cpu().numpy()
+
+
+def f64_backup(q, pr, with_logp, gamma, alpha, rows=None):
+    """The backup in float64 from the call's own (fp32) q outputs, and its gate."""
+    n = q[0].numel() if rows is None else rows
+    q64 = [np.asarray(t.detach().cpu(), np.float64) for t in q]
+    qmin = np.minimum(q64[0], q64[1]) if len(q64) == 2 else q64[0]
+    r, d, logp = (np.asarray(pr[k].detach().cpu(), np.float64)[:n] for k in ("r", "d", "logp"))
+    gamma, alpha = float(np.float32(gamma)), float(np.float32(alpha))
+    if not with_logp:
+        alpha, logp = 0.0, np.zeros_like(r)
+    ref = r + gamma * (1.0 - d) * (qmin - alpha * logp)
+    gate = 1e-6 * (np.abs(r) + gamma * (np.abs(qmin) + alpha * np.abs(logp)))
+    return ref, gate
+
+
+def check_backup(q, backup, pr, with_logp, gamma, alpha, what="", extra=0.0):
+    ref, gate = f64_backup(q, pr, with_logp, gamma, alpha, rows=backup.numel())
+    got = np.asarray(backup.detach().cpu(), np.float64)
+    err = np.abs(got - ref)
+    print("%s backup: max err / gate = %.3g" % (what, float((err / (gate + extra + 1e-30)).max())))
+    assert (err <= gate + extra).all(), (what, float((err / (gate + extra + 1e-30)).max()))
+    done = np.asarray(pr["d"].cpu())[:backup.numel()] != 0
+    assert torch.equal(backup.cpu()[done], pr["r"].cpu()[:backup.numel()][done]), what       # r + gamma * 0 * x
+
+
+def exact_properties(L, device, stream, pr1000):
+    """The exact properties of the entry on a G = 2 problem of 1000 rows (finite inputs)."""
+    q, backup = run(L, device, stream, pr1000)
+    # a G = 2 call's q_out equals the two G = 1 calls bit for bit
+    for g in range(2):
+        one = dict(pr1000, h=[pr1000["h"][g]], w=[pr1000["w"][g]], b=[pr1000["b"][g]])
+        q1, _ = run(L, device, stream, one, with_backup=False)
+        assert torch.equal(q1[0], q[g]), g
+    # the first 64 rows of the 1000-row call equal a 64-row call bit for bit
+    q64, b64 = run(L, device, stream, pr1000, rows=64)
+    assert torch.equal(q64[0], q[0][:64]) and torch.equal(q64[1], q[1][:64]) and torch.equal(b64, backup[:64])
+    # backup == NULL leaves r / d / logp unread (NULL is passed), and gives the same q
+    qf, none = run(L, device, stream, pr1000, with_backup=False)
+    assert none is None and torch.equal(qf[0], q[0]) and torch.equal(qf[1], q[1])
+    # any destination may be NULL; the others do not depend on it
+    M, H = pr1000["h"][0].shape
+    dev = pr1000["h"][0].device
+    only = torch.full((M,), SENTINEL, device=dev)
+    _lib.check(call(L, device, stream, M, H, pr1000["h"], pr1000["w"], pr1000["b"], [None, only], pr1000["r"], pr1000["d"], pr1000["logp"], 0.99, 0.2,
+                    None), None, "mms_q_heads_backup", L)
+    assert torch.equal(only, q[1])
+    _, b_only = run(L, device, stream, pr1000, with_q=False)
+    assert torch.equal(b_only, backup)
+    # rows past M are not written: a 37-row call into 1000-row destinations
+    q37 = [torch.full((M,), SENTINEL, device=dev) for _ in range(2)]
+    b37 = torch.full((M,), SENTINEL, device=dev)
+    _lib.check(call(L, device, stream, 37, H, pr1000["h"], pr1000["w"], pr1000["b"], q37, pr1000["r"], pr1000["d"], pr1000["logp"], 0.99, 0.2, b37),
+               None, "mms_q_heads_backup", L)
+    for t, full in ((q37[0], q[0]), (q37[1], q[1]), (b37, backup)):
+        assert torch.equal(t[:37], full[:37]) and (t[37:] == SENTINEL).all()
+    return q, backup
+
+
+def check_error_paths(L, device, stream, other_device):
+    """Every refused call returns non-zero with a message and writes nothing (destinations pre-filled with SENTINEL); M = 0 succeeds.
+    device: the library's own device argument; other_device: one it must refuse."""
+    M, H = 8, 64
+    dev = "cpu" if device < 0 else "cuda:%d" % device
+    pr = problem(M, H, 2, seed=5, device=dev)
+    dst = [torch.full((M,), SENTINEL, device=dev) for _ in range(3)]
+    pad = torch.zeros(M * H + 1, device=dev)[1:].view(M, H)        # 4 bytes past a 16-byte boundary
+
+    def go(M=M, H=H, h=pr["h"], w=pr["w"], b=pr["b"], q=(dst[0], dst[1]), r=pr["r"], d=pr["d"], backup=dst[2], device=device):
+        return L.mms_q_heads_backup(device, M, H, p(h[0]), p(w[0]), p(b[0]), p(q[0]), p(h[1]), p(w[1]), p(b[1]), p(q[1]), p(r), p(d), p(pr["logp"]),
+                                    0.99, 0.2, p(backup), stream)
+
+    N = None
+    bad = [("H = 96", dict(H=96), "multiple of 64"), ("H = 0", dict(H=0), "multiple of 64"), ("H above MMS_Q_MAX_H", dict(H=4160), "up to 4096"), ("h1 without w1", dict(w=[pr["w"][0], N]), "second network"),
+           ("w1 without h1", dict(h=[pr["h"][0], N]), "second network"), ("M = -1", dict(M=-1), "M >= 0"), ("misaligned h0", dict(h=[pad, pr["h"][1]]), "aligned"),
+           ("NULL w0", dict(w=[N, pr["w"][1]]), "required"), ("no destination", dict(q=(N, N), backup=N), "destination"),
+           ("backup without reward", dict(r=N), "reward and done"), ("backup without done", dict(d=N), "reward and done"),
+           ("wrong device", dict(device=other_device), None)]
+    for label, kw, contains in bad:
+        rc = go(**kw)
+        msg = _lib.last_error(None, L)
+        assert rc != 0 and msg, (label, rc, msg)
+        assert contains is None or contains in msg, (label, msg)
+        if dev != "cpu":
+            torch.cuda.synchronize()
+        assert all((t == SENTINEL).all() for t in dst), label
+    assert go(M=0) == 0 and all((t == SENTINEL).all() for t in dst)
+    assert go() == 0
+    if dev != "cpu":
+        torch.cuda.synchronize()
+    assert not any((t == SENTINEL).any() for t in dst)

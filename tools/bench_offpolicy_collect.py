@@ -10,9 +10,13 @@ eagerly and as a replayed hipGraph of one pass over a 16-row window of the ring.
 `--algo sac` runs the same loop with SAC's actor (cfg/sac/config.yaml: 3 x 1024, ELU; stochastic act, sac.py:166: the hidden layers
 as mms_linear2_act launches, the squashed-Gaussian head as one mms_sac_heads_act launch) and also times the Q target's
 pi(o2) under no_grad with logp on an [8, N, W] gather (sac.py:374-376: batch_size 32 / nminibatches 4 = 8 ring rows), fused
-against the library path (torch's Linear / clamp / exp / randn / tanh / log chain) in the same process.
+against the library path (torch's Linear / clamp / exp / randn / tanh / log chain) in the same process, and `target_q`: the three
+lines behind it (sac.py:379-382: both target critics, the min, the Bellman backup) on the same gather by the same protocol, as
+`library` (the torch modules), `fused_separate` (the reference's four lines over the fused MLPQFunction.forward: what an unmodified
+sac.py gets) and `fused_backup` (actor_critic_targ.q_backup).  `--target-only` skips the timed collection loops (the ring is filled by
+the warm-up steps alone): the run to put under a kernel trace.
 
-    python tools/bench_offpolicy_collect.py [--algo ddpg|sac] [--num-envs 8192] [--steps 512]
+    python tools/bench_offpolicy_collect.py [--algo ddpg|sac] [--num-envs 8192] [--steps 512] [--target-only]
 """
 import argparse
 import json
@@ -35,6 +39,7 @@ def main():
     ap.add_argument("--env-spacing", type=float, default=None,
                     help="override env.envSpacing (0: every env at the origin, the helicopters fly; default: the reference's grid, where every env away "
                          "from the origin resets on every step -- positions and goals are global-frame, multi_ingenuity.py:381-453)")
+    ap.add_argument("--target-only", action="store_true", help="--algo sac: only the target_pi / target_q series (no timed collection loop, no graph)")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -55,7 +60,7 @@ def main():
     if args.env_spacing is not None:
         cfg = default_cfg(args.task)
         cfg["env"]["envSpacing"] = float(args.env_spacing)
-    for variant in ("copies", "bound"):
+    for variant in (("bound",) if args.target_only else ("copies", "bound")):
         eng = Engine(args.task, cfg=cfg, num_envs=N, device=0, seed=0, clip_obs=5.0)
         W, AD = eng.obs_dim, eng.num_actions
         if args.algo == "sac":
@@ -99,6 +104,14 @@ def main():
             for _ in range(64):
                 step()
             s.synchronize()
+        if args.target_only:
+            torch.cuda.current_stream().wait_stream(s)
+            out["target_pi"] = time_target_pi(ac, buf, args.steps)
+            out["target_q"] = time_target_q(ac, buf, args.steps)
+            eng.bind_obs_out(None); eng.bind_rollout_out(None, None)
+            eng.close()
+            break
+        with torch.cuda.stream(s):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(s)
             for _ in range(args.steps):
@@ -128,6 +141,7 @@ def main():
         del graph
         if args.algo == "sac" and variant == "bound":
             out["target_pi"] = time_target_pi(ac, buf, args.steps)
+            out["target_q"] = time_target_q(ac, buf, args.steps)
         eng.close()
     print(json.dumps(out), flush=True)
 
@@ -159,6 +173,64 @@ def time_target_pi(ac, buf, steps):
         out[k + "_ms_per_call"] = float(np.median(v))
         out[k + "_ms_rounds"] = v
     out["speedup"] = out["library_ms_per_call"] / out["fused_ms_per_call"]
+    return out
+
+
+def time_target_q(ac, buf, steps, gamma=0.99, alpha=0.2):
+    """The Q target behind pi(o2) (sac.py:379-382) on the same [8, N, .] gather, a2 and logp from one pi(o2) call: the torch modules,
+    the reference's four lines over the fused MLPQFunction.forward, and q_backup -- warm-up of every path, then five rounds alternating
+    the paths, medians and all rounds kept."""
+    import copy
+
+    import torch
+    idx = torch.arange(8, device=buf.next_observations.device)
+    o2, r, d = buf.next_observations[idx], buf.rewards[idx], buf.dones[idx]
+    targ = copy.deepcopy(ac)                                       # sac.py:104: actor_critic_targ
+    for m in (targ, targ.q1, targ.q2):
+        m.fused_q = True
+    lib = copy.deepcopy(targ)
+    for m in (lib, lib.q1, lib.q2):
+        m.fused_q = False
+
+    def four_lines(t):
+        def f():
+            q1_pi_targ = t.q1(o2, a2)
+            q2_pi_targ = t.q2(o2, a2)
+            q_pi_targ = torch.min(q1_pi_targ, q2_pi_targ)
+            return r + gamma * (1 - d) * (q_pi_targ - alpha * logp_a2)
+        return f
+
+    paths = {"library": four_lines(lib), "fused_separate": four_lines(targ), "fused_backup": lambda: targ.q_backup(o2, a2, r, d, gamma, alpha, logp_a2)}
+    res = {k: [] for k in paths}
+    last = {}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    reps = max(8, steps // 8)
+    with torch.no_grad():
+        a2, logp_a2 = ac.pi(o2)
+        for f in paths.values():
+            for _ in range(4):
+                f()
+        torch.cuda.synchronize()
+        for _ in range(5):
+            for k, f in paths.items():
+                e0.record()
+                for _ in range(reps):
+                    last[k] = f()
+                e1.record(); e1.synchronize()
+                res[k].append(e0.elapsed_time(e1) / reps)
+    M, H, G = o2.shape[0] * o2.shape[1], targ.q1.q[-2].in_features, 2
+    scale = float(1 + last["library"].abs().max())
+    out = {"shape": list(o2.shape), "rows": M, "hidden": [l.out_features for l in list(targ.q1.q)[:-2:2]], "dones_dtype": str(d.dtype).replace("torch.", ""),
+           "calls_per_round": reps, "finite": bool(all(torch.isfinite(v).all() for v in last.values())),
+           "max_diff_vs_library": {k: float((last[k] - last["library"]).abs().max()) / scale for k in ("fused_separate", "fused_backup")},
+           # what mms_q_heads_backup must move: both hidden activations, r (4) + d (1) + logp (4) in and the backup (4) out per row, the weights once
+           "tail_kernel_bytes": 4 * G * M * H + 13 * M + 4 * G * (H + 1)}
+    for k, v in res.items():
+        out[k + "_ms_per_call"] = float(np.median(v))
+        out[k + "_ms_rounds"] = v
+        out[k + "_ms_spread"] = float(max(v) - min(v))
+    out["speedup_fused_backup"] = out["library_ms_per_call"] / out["fused_backup_ms_per_call"]
+    out["speedup_fused_separate"] = out["library_ms_per_call"] / out["fused_separate_ms_per_call"]
     return out
 
 
