@@ -120,10 +120,10 @@ __global__ void __launch_bounds__(256) mlp_tsplit_kernel(TransSplitArgs a) {
         if (a.out && in) a.out[m * a.ldo + k] = v;
     }
     __syncthreads();
-    if (a.colp && t < 64) {
-        float s = 0.f;
-        for (int r = 0; r < 32; r++) s += tile[r][t];
-        a.colp[(size_t)mc * a.ldc + blockIdx.x * 64 + t] = s;
+    if (a.colp && t < 64) {                       // summed in double, rounded once: a serial fp32 sum over the rows is worse than a tree's
+        double s = 0.0;
+        for (int r = 0; r < 32; r++) s += (double)tile[r][t];
+        a.colp[(size_t)mc * a.ldc + blockIdx.x * 64 + t] = (float)s;
     }
     const int n = t >> 2, g = t & 3, row = blockIdx.x * 64 + n;
     const int p = mc / a.MCs, j = mc - p * a.MCs;
@@ -133,16 +133,18 @@ __global__ void __launch_bounds__(256) mlp_tsplit_kernel(TransSplitArgs a) {
     store_planes(a.dst + (((size_t)p * a.rows_pad + row) * a.pitch + a.coff + j) * kChunk + g * 16, v);
 }
 
-// out[n, k] = sum over g (in order) of part[g][n, k]  (part rows of ldp floats, `stride` floats apart)
+// out[n, k] = sum over g (in order) of part[g][n, k]  (part rows of ldp floats, `stride` floats apart), accumulated in Acc: float for
+// the few row parts of a weight gradient, double for a bias gradient's column sums (one per 32-row chunk: up to 65535 of them)
+template <typename Acc>
 __global__ void __launch_bounds__(256) mlp_reduce_kernel(const float* __restrict__ part, int groups, size_t stride, int ldp, int N, int K,
                                                           float* __restrict__ out) {
     const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (id >= (int64_t)N * K) return;
     const int n = (int)(id / K), k = (int)(id - (int64_t)n * K);
     const float* p = part + (size_t)n * ldp + k;
-    float s = 0.f;
-    for (int g = 0; g < groups; g++) s += p[g * stride];
-    out[id] = s;
+    Acc s = 0;
+    for (int g = 0; g < groups; g++) s += (Acc)p[g * stride];
+    out[id] = (float)s;
 }
 
 // dst [rd, cd] (pitch ldd) = src [rs, cs] (pitch lds), zero outside
@@ -247,9 +249,10 @@ static hipError_t copy2d(const float* src, int64_t rs, int cs, int lds, float* d
     return hipGetLastError();
 }
 
+template <typename Acc>
 static hipError_t reduce(const float* part, int groups, size_t stride, int ldp, int N, int K, float* out, hipStream_t s) {
     const int64_t n = (int64_t)N * K;
-    hipLaunchKernelGGL(mlp_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, groups, stride, ldp, N, K, out);
+    hipLaunchKernelGGL(mlp_reduce_kernel<Acc>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, groups, stride, ldp, N, K, out);
     return hipGetLastError();
 }
 
@@ -264,8 +267,8 @@ static hipError_t weight_grad(const MlpPlan& P, int l, int prods, uint8_t* ws, f
     const size_t xs = (size_t)P.np[l] * MCs * kChunk, wsz = (size_t)P.np[l - 1] * MCs * kChunk, ys = (size_t)P.np[l] * P.np[l - 1];
     float* part = reinterpret_cast<float*>(ws + P.part);
     MMS_TRY(gemm(G, P.np[l], P.np[l - 1], MCs, ws + P.ta, xs, ws + P.tb, wsz, reinterpret_cast<const float*>(ws + P.zb), part, ys, s));
-    MMS_TRY(reduce(part, G, ys, P.np[l - 1], P.n[l], P.n[l - 1], dw, s));
-    if (db) MMS_TRY(reduce(reinterpret_cast<const float*>(ws + P.colp), P.MC, (size_t)P.np[l], P.np[l], 1, P.n[l], db, s));
+    MMS_TRY(reduce<float>(part, G, ys, P.np[l - 1], P.n[l], P.n[l - 1], dw, s));
+    if (db) MMS_TRY(reduce<double>(reinterpret_cast<const float*>(ws + P.colp), P.MC, (size_t)P.np[l], P.np[l], 1, P.n[l], db, s));
     return hipSuccess;
 }
 
@@ -336,7 +339,8 @@ hipError_t mlp_grad_rop(const MlpPlan& P, const float* x, const float* const* h,
     for (int l = L; l >= 1; l--) {
         const int S = P.S[l];
         const OperandArgs od = l == L ? operand(g, P.n[L]) : operand(d[l - 1], P.n[l]);
-        const OperandArgs ord = operand(T, P.np[l], 2, h[l - 1], P.n[l], e[l - 1], P.n[l], F(P.ra[l]), P.np[l]);   // Rd_l (l < L)
+        // Rd_l (l < L; h and e hold L - 1 pointers: index L - 1 is not the caller's to read)
+        const OperandArgs ord = l < L ? operand(T, P.np[l], 2, h[l - 1], P.n[l], e[l - 1], P.n[l], F(P.ra[l]), P.np[l]) : operand(nullptr, 0);
         const OperandArgs orh = l >= 2 ? operand(F(P.ra[l - 1]), P.np[l - 1], 1, h[l - 2], P.n[l - 1]) : operand(nullptr, 0);  // Rh_{l-1}
         int prods = 0;
         if (l < L) {                                               // Rd_l^T h_{l-1}
