@@ -44,6 +44,8 @@
  *     (algorithms/rl/trpo/trpo.py:290) and the create_graph=True
  *     gradient of the KL (:427)
  *   TRPO double backward of the KL's Hessian-vector product (:431)      mms_mlp_grad_rop
+ *   PPO.update's loss head: KL, clipped surrogate, value loss, entropy  mms_ppo_loss
+ *     and their backward (algorithms/rl/ppo/ppo.py:270-302)
  *
  * Ownership: the engine owns every buffer it reports through mms_get_tensor for the lifetime of the
  * handle; callers wrap them as NON-owning views and must keep the handle alive while any view exists.
@@ -554,6 +556,41 @@ int mms_mlp_grad(int device, int32_t layers, int64_t M, const int32_t* dims, con
 int mms_mlp_grad_rop(int device, int32_t layers, int64_t M, const int32_t* dims, const float* x, const float* const* h, const float* const* w,
                      const float* const* v, const float* const* c, const float* g, const float* const* d, const float* const* e, float* rmu,
                      float* const* rdw, float* const* rdb, void* workspace, int64_t* ws_bytes, void* hip_stream);
+
+/* ---- The PPO update's loss head and its gradients in one call (csrc/ppo_loss_kernels.hip) ------------------------------------------
+ * What agents/algorithms/rl/ppo/ppo.py:270-302 evaluates per minibatch behind ActorCritic.evaluate, as seven advanced-index gathers and
+ * a few dozen element-wise launches forward and again in backward(): the KL of the adaptive schedule, the clipped surrogate, the
+ * (clipped) value loss, the entropy term, and the gradients of the loss with respect to the networks' outputs.
+ * Dense inputs, the networks' outputs for the minibatch: mu [M, A], log_std [A] (l below), value [M].  Stored inputs, read in place as
+ * row indices[i] of their base (row i when indices == NULL): actions [*, A], old_logp [*], adv [*], returns [*], target_values [*],
+ * old_mu [*, A], old_sigma [*, A] (what the reference stores as "sigma": log_std rows).  All f32 and contiguous, indices int64.
+ *   z_ij    = (a_ij - mu_ij) exp(-2 l_j)
+ *   logp_i  = sum_j (-0.5 z_ij^2 - 2 l_j - 0.5 log 2pi)          scale_tril = diag(sigma^2), as module.py:76-77 and ActorCritic.evaluate
+ *   entropy = sum_j (0.5 + 0.5 log 2pi + 2 l_j)
+ *   kl      = mean_i sum_j (l_j - os_ij + (exp(os_ij)^2 + (om_ij - mu_ij)^2) / (2 exp(l_j)^2) - 0.5)       (no gradient, ppo.py:273-275)
+ *   r_i     = exp(logp_i - old_logp_i)
+ *   surrogate  = mean_i max(-adv_i r_i, -adv_i clamp(r_i, 1 - clip, 1 + clip))
+ *   value_loss = clipped_value ? mean_i max((v_i - ret_i)^2, (vc_i - ret_i)^2), vc_i = tv_i + clamp(v_i - tv_i, -clip, clip)
+ *                              : mean_i (ret_i - v_i)^2
+ *   loss    = surrogate + value_coef value_loss - entropy_coef entropy
+ * out [5] = {loss, surrogate, value_loss, entropy, kl}.  dmu [M, A], dlog_std [A], dvalue [M] = d loss / d (mu, log_std, value), all
+ * three or none (none: the five terms only) -- torch autograd's result, including how maximum and clamp split ties:
+ *   g_i        = -adv_i r_i / M  where 1 - clip <= r_i <= 1 + clip or -adv_i r_i > -adv_i clamp(r_i), else 0
+ *   dmu_ij     = g_i z_ij exp(-2 l_j)            dlog_std_j = sum_i g_i (2 z_ij^2 - 2) - 2 entropy_coef
+ *   dvalue_i   = value_coef 2 (v_i - ret_i) / M  where clipped_value is off, |v_i - tv_i| <= clip or (v_i - ret_i)^2 > (vc_i - ret_i)^2, else 0
+ * (one measure-zero difference: outside the clip range with exactly equal squares torch gives half the gradient, this gives none).
+ * Sums over rows are per-block partials in double, added in a fixed order and rounded once: no atomics, results bit-identical run to
+ * run; a row's dmu and dvalue depend on that row, M and the scalars alone.  At most two launches on hip_stream, no host synchronisation.
+ * The entry cannot see the values of indices: every one must be a valid row of all seven stored inputs.
+ * workspace / ws_bytes: mms_mlp_grad's convention (NULL stores the bytes needed and returns 0 -- nothing else is read; 256-byte aligned;
+ * a smaller one is an error; the CPU build needs 0 and runs on any aligned non-NULL workspace).  The workspace needs no initialisation.
+ * 1 <= M <= 0x7fffffff, 1 <= A <= MMS_PPO_LOSS_MAX_A.  Inputs are taken to be finite (finite-math device code).  Bad arguments return
+ * non-zero with mms_last_error(NULL) and write nothing. */
+#define MMS_PPO_LOSS_MAX_A 128
+int mms_ppo_loss(int device, int64_t M, int32_t A, const float* mu, const float* log_std, const float* value, const int64_t* indices,
+                 const float* actions, const float* old_logp, const float* adv, const float* returns, const float* target_values,
+                 const float* old_mu, const float* old_sigma, float clip, float value_coef, float entropy_coef, int32_t clipped_value,
+                 float* out, float* dmu, float* dlog_std, float* dvalue, void* workspace, int64_t* ws_bytes, void* hip_stream);
 
 const char* mms_last_error(mms_handle h);   /* h may be NULL: error of the last failed mms_create */
 int mms_abi_version(void);

@@ -729,3 +729,16 @@ class ActorCritic(nn.Module):
         entropy = (0.5 + 0.5 * math.log(2.0 * math.pi) + scale_log).sum(-1).expand(mean.shape[0])
         value = self.critic(states if self.asymmetric else observations)
         return log_prob, entropy, value, mean, self.log_std.repeat(mean.shape[0], 1)
+
+    def ppo_loss(self, observations, states, storage, indices, clip_param, value_loss_coef, entropy_coef, use_clipped_value_loss=True):
+        """Not in the reference: `evaluate` and the loss head of PPO.update (ppo.py:266-302) in one call, (loss, info) of loss.ppo_loss.
+        observations / states: the minibatch's gathered rows, as `evaluate` takes them; storage: the RolloutStorage they came from;
+        indices: the minibatch's rows of its flat views (a list or an int64 tensor).  Actor and critic run under autograd; actions,
+        log-probabilities, advantages, returns, values, mu and sigma are read where the storage keeps them (mms_ppo_loss)."""
+        from .loss import ppo_loss
+        mu = self.actor(observations)
+        value = self.critic(states if self.asymmetric else observations)
+        s = storage
+        return ppo_loss(mu, self.log_std, value, s.actions.view(-1, s.actions.size(-1)), s.actions_log_prob.view(-1), s.advantages.view(-1),
+                        s.returns.view(-1), s.values.view(-1), s.mu.view(-1, s.mu.size(-1)), s.sigma.view(-1, s.sigma.size(-1)), clip_param,
+                        value_loss_coef, entropy_coef, use_clipped_value_loss, indices=indices)

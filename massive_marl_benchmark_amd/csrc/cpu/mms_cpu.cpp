@@ -18,6 +18,7 @@
 
 #include "../mms_host.h"
 #include "../rollout_lane.h"
+#include "../ppo_loss_lane.h"
 #include "../q_lane.h"
 #include "../sac_lane.h"
 #include "lane_step.h"
@@ -993,5 +994,66 @@ MMS_API int mms_mlp_grad_rop(int device, int32_t L, int64_t M, const int32_t* di
             Rd.swap(nd);
         }
     }
+    return 0;
+}
+
+// ---- the PPO update's loss head (include/mms.h: mms_ppo_loss) over ../ppo_loss_lane.h -----------------------------------------------
+// Rows in at most 1024 chunks of at least 256 (OpenMP over chunks): a row's logp and KL term summed in double over ascending columns,
+// a chunk's partials in double over ascending rows, the chunks added in ascending order and rounded once -- the result does not depend
+// on the number of threads.  No workspace.
+MMS_API int mms_ppo_loss(int device, int64_t M, int32_t A, const float* mu, const float* log_std, const float* value, const int64_t* indices,
+                         const float* actions, const float* old_logp, const float* adv, const float* returns, const float* target_values,
+                         const float* old_mu, const float* old_sigma, float clip, float value_coef, float entropy_coef, int32_t clipped_value,
+                         float* out, float* dmu, float* dlog_std, float* dvalue, void* workspace, int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_ppo_loss(M, A, mu, log_std, value, actions, old_logp, adv, returns, target_values, old_mu, old_sigma, out, dmu, dlog_std, dvalue,
+                               workspace, ws_bytes, 0)))
+        return 1;
+    if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query
+    const bool grads = dmu != nullptr;
+    int64_t chunk = (M + 1023) / 1024;
+    chunk = chunk < 256 ? 256 : chunk;
+    const int64_t nchunks = (M + chunk - 1) / chunk;
+    const float inv_m = 1.0f / (float)M;
+    float einv[MMS_PPO_LOSS_MAX_A], den[MMS_PPO_LOSS_MAX_A];
+    double entropy = 0.0;
+    for (int j = 0; j < A; j++) {
+        mms::ppo_col_consts(log_std[j], einv[j], den[j]);
+        entropy += (double)mms::ppo_entropy_term(log_std[j]);
+    }
+    std::vector<double> part((size_t)nchunks * (3 + A), 0.0);
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < nchunks; c++) {
+        double* p = part.data() + c * (3 + A);
+        const int64_t end = (c + 1) * chunk < M ? (c + 1) * chunk : M;
+        float z[MMS_PPO_LOSS_MAX_A];
+        for (int64_t row = c * chunk; row < end; row++) {
+            const int64_t src = indices ? indices[row] : row;
+            const float *m = mu + row * A, *a = actions + src * A, *om = old_mu + src * A, *os = old_sigma + src * A;
+            double logp = 0.0, kl = 0.0;
+            for (int j = 0; j < A; j++) {
+                logp += (double)mms::ppo_logp_term(a[j], m[j], log_std[j], einv[j], z[j]);
+                kl += (double)mms::ppo_kl_term(log_std[j], os[j], om[j], m[j], den[j]);
+            }
+            const mms::PpoRow r = mms::ppo_row(logp, old_logp[src], adv[src], value[row], returns[src], target_values[src], clip, value_coef,
+                                               clipped_value != 0, inv_m);
+            p[0] += (double)r.surrogate;
+            p[1] += (double)r.value_loss;
+            p[2] += kl;
+            if (grads) {
+                dvalue[row] = r.dvalue;
+                for (int j = 0; j < A; j++) {
+                    dmu[row * A + j] = mms::ppo_dmu(r.g, z[j], einv[j]);
+                    p[3 + j] += (double)mms::ppo_dlog_std_term(r.g, z[j]);
+                }
+            }
+        }
+    }
+    std::vector<double> tot(3 + A, 0.0);
+    for (int64_t c = 0; c < nchunks; c++)
+        for (int q = 0; q < 3 + A; q++) tot[q] += part[c * (3 + A) + q];
+    mms::ppo_finish_scalars(tot[0], tot[1], tot[2], entropy, M, value_coef, entropy_coef, out);
+    if (grads)
+        for (int j = 0; j < A; j++) dlog_std[j] = mms::ppo_finish_dlog_std(tot[3 + j], entropy_coef);
     return 0;
 }

@@ -26,6 +26,9 @@ hipError_t launch_sac_head_act(const float*, int, const float*, const float*, co
                                float*, float*, float*, float*, float*, float*, int64_t, int, hipStream_t);
 hipError_t launch_q_heads_backup(int, int64_t, int, const float* const*, const float* const*, const float* const*, float* const*, const float*,
                                  const uint8_t*, const float*, float, float, float*, hipStream_t);
+int64_t ppo_loss_ws_bytes(int64_t, int);
+hipError_t launch_ppo_loss(int64_t, int, const float*, const float*, const float*, const int64_t*, const float*, const float*, const float*, const float*,
+                           const float*, const float*, const float*, float, float, float, int, float*, float*, float*, float*, void*, hipStream_t);
 struct MlpPlan;
 }  // namespace mms
 
@@ -647,6 +650,26 @@ __attribute__((visibility("default"))) int mms_mlp_grad_rop(int device, int32_t 
     const int ws = mlp_workspace("mms_mlp_grad_rop", layers, M, dims, true, workspace, ws_bytes, &P);
     if (ws != 0) return ws == 2 ? 0 : 1;
     MMS_FREE(mms::mlp_grad_rop(P, x, h, w, v, c, g, d, e, rmu, rdw, rdb, static_cast<uint8_t*>(workspace), (hipStream_t)s));
+    return 0;
+}
+
+// ---- the PPO update's loss head (ppo_loss_kernels.hip) ------------------------------------------------------------------------------
+
+__attribute__((visibility("default"))) int mms_ppo_loss(int device, int64_t M, int32_t A, const float* mu, const float* log_std, const float* value,
+                                                        const int64_t* indices, const float* actions, const float* old_logp, const float* adv,
+                                                        const float* returns, const float* target_values, const float* old_mu,
+                                                        const float* old_sigma, float clip, float value_coef, float entropy_coef,
+                                                        int32_t clipped_value, float* out, float* dmu, float* dlog_std, float* dvalue,
+                                                        void* workspace, int64_t* ws_bytes, void* s) {
+    MMS_DEV(device)
+    const bool shapes = M >= 1 && M <= 0x7fffffff && A >= 1 && A <= MMS_PPO_LOSS_MAX_A;
+    const int64_t need = shapes ? mms::ppo_loss_ws_bytes(M, A) : 0;
+    if (refused(check_ppo_loss(M, A, mu, log_std, value, actions, old_logp, adv, returns, target_values, old_mu, old_sigma, out, dmu, dlog_std, dvalue,
+                               workspace, ws_bytes, need)))
+        return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }                // the size query
+    MMS_FREE(mms::launch_ppo_loss(M, A, mu, log_std, value, indices, actions, old_logp, adv, returns, target_values, old_mu, old_sigma, clip, value_coef,
+                                  entropy_coef, clipped_value, out, dmu, dlog_std, dvalue, workspace, (hipStream_t)s));
     return 0;
 }
 

@@ -332,6 +332,24 @@ static inline std::string check_q_heads_backup(int64_t M, int32_t H, const float
     return {};
 }
 
+// mms_ppo_loss: the shapes, then (workspace NULL is the size query: nothing else is read) the operands and the workspace against
+// `need`, the bytes this build's plan asks for (the CPU build's: 0).
+static inline std::string check_ppo_loss(int64_t M, int32_t A, const float* mu, const float* log_std, const float* value, const float* actions,
+                                         const float* old_logp, const float* adv, const float* returns, const float* target_values,
+                                         const float* old_mu, const float* old_sigma, const float* out, const float* dmu, const float* dlog_std,
+                                         const float* dvalue, const void* workspace, const int64_t* ws_bytes, int64_t need) {
+    if (!ws_bytes) return "mms_ppo_loss: ws_bytes required";
+    if (M < 1 || M > 0x7fffffff) return "mms_ppo_loss: M must be in 1..2147483647";
+    if (A < 1 || A > MMS_PPO_LOSS_MAX_A) return "mms_ppo_loss: A must be in 1.." + std::to_string(MMS_PPO_LOSS_MAX_A);
+    if (!workspace) return {};
+    if (!mu || !log_std || !value || !actions || !old_logp || !adv || !returns || !target_values || !old_mu || !old_sigma || !out)
+        return "mms_ppo_loss: null pointer (mu, log_std, value, actions, old_logp, adv, returns, target_values, old_mu, old_sigma and out are required)";
+    if ((dmu || dlog_std || dvalue) && !(dmu && dlog_std && dvalue)) return "mms_ppo_loss: dmu, dlog_std and dvalue go together (all three, or all NULL: the terms only)";
+    if (*ws_bytes < need) return "mms_ppo_loss: workspace too small (" + std::to_string(*ws_bytes) + " bytes, needs " + std::to_string(need) + ")";
+    if (addr(workspace) & 255) return "mms_ppo_loss: workspace must be 256-byte aligned";
+    return {};
+}
+
 static inline std::string check_linear2_act(int64_t M, int32_t N, int32_t K, const float* x0, const float* w0, const float* b0, const float* y0,
                                             const float* x1, const float* w1, const float* b1, const float* y1, int32_t act) {
     if (!x0 || !w0 || !b0 || !y0 || M < 0 || M > 0x7fffffff || N <= 0 || K <= 0 || (K % 4) != 0 || act < 0 || act > 3)
