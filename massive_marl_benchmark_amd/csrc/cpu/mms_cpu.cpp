@@ -706,6 +706,9 @@ MMS_API int mms_linear_group_act_split16(int device, int32_t groups, int64_t M, 
     return 0;
 }
 
+// log(std) + 0.5 log(2 pi) in double, rounded once (policy_kernels.hip: log_density_const); logp = fma(-z / 2, z, -this)
+static inline float log_density_const(float sd) { return (float)(log((double)sd) + 0.9189385332046727); }
+
 static void chan_combine(const float* part, int64_t M, int64_t row, int slots, float& mean, float& m2) {
     float sum = 0.f;
     for (int k = 0; k < slots; k++) sum += part[((size_t)k * M + row) * 2];
@@ -752,7 +755,7 @@ MMS_API int mms_marl_heads_finish(int device, int32_t groups, int64_t M, int32_t
                 if (!sd) { out[g][r * pitch + j] = mu; continue; }
                 const float z = mms::rand_normal(seed + (uint64_t)g, (uint64_t)(row_offset + r), (uint64_t)c, (uint32_t)j);
                 out[g][r * pitch + j] = mu + sd[j] * z;
-                if (logp && logp[g]) logp[g][r * pitch + j] = -0.5f * z * z - logf(sd[j]) - 0.9189385332046727f;
+                if (logp && logp[g]) logp[g][r * pitch + j] = fmaf(-0.5f * z, z, -log_density_const(sd[j]));
             }
             if (cnt) cnt[r] = c + 1;
         }
@@ -842,7 +845,7 @@ MMS_API int mms_marl_heads_act(int device, int32_t groups, int64_t M, int32_t H,
                                float* const* out, float* const* logp, const int32_t* out_pitch, int64_t* const* counters, uint64_t seed,
                                int64_t row_offset, float eps, void*) {
     if (cpu_only(device)) return 1;
-    if (refused(check_marl_heads_act(groups, M, H, h, gamma, beta, w, b, A, out, out_pitch))) return 1;
+    if (refused(check_marl_heads_act(groups, M, H, h, gamma, beta, w, b, A, out, out_pitch, eps))) return 1;
     for (int g = 0; g < groups; g++) {
         const int op = out_pitch ? out_pitch[g] : A[g];
         const float* sd = std ? std[g] : nullptr;
@@ -865,7 +868,7 @@ MMS_API int mms_marl_heads_act(int device, int32_t groups, int64_t M, int32_t H,
                 if (sd) {
                     const float z = mms::rand_normal(seed + (uint64_t)g, (uint64_t)(row_offset + m), (uint64_t)c, (uint32_t)j);
                     p += sd[j] * z;
-                    if (lp) lp[m * op + j] = -0.5f * z * z - logf(sd[j]) - 0.9189385332046727f;
+                    if (lp) lp[m * op + j] = fmaf(-0.5f * z, z, -log_density_const(sd[j]));
                 }
                 out[g][m * op + j] = p;
             }

@@ -598,10 +598,10 @@ __attribute__((visibility("default"))) int mms_marl_heads_act(int device, int32_
                                                               float* const* logp, const int32_t* out_pitch, int64_t* const* counters, uint64_t seed,
                                                               int64_t row_offset, float eps, void* s) {
     MMS_DEV(device)
-    if (refused(check_marl_heads_act(groups, M, H, h, gamma, beta, w, b, A, out, out_pitch))) return 1;
+    if (refused(check_marl_heads_act(groups, M, H, h, gamma, beta, w, b, A, out, out_pitch, eps))) return 1;
     mms::HeadsArgs a = {};
     for (int g = 0; g < groups; g++) {
-        a.h[g] = h[g]; a.gamma[g] = gamma[g]; a.beta[g] = beta[g]; a.w[g] = w[g]; a.b[g] = b[g]; a.A[g] = A[g]; a.out[g] = out[g];
+        a.h[g] = h[g]; a.gamma[g] = eps >= 0.f ? gamma[g] : nullptr; a.beta[g] = eps >= 0.f ? beta[g] : nullptr; a.w[g] = w[g]; a.b[g] = b[g]; a.A[g] = A[g]; a.out[g] = out[g];
         a.out_pitch[g] = out_pitch ? out_pitch[g] : A[g];
         a.std[g] = std ? std[g] : nullptr;
         a.logp[g] = logp ? logp[g] : nullptr;

@@ -543,12 +543,13 @@ static inline std::string check_layernorm_group(int32_t groups, int64_t M, int32
 
 static inline std::string check_marl_heads_act(int32_t groups, int64_t M, int32_t H, const float* const* h, const float* const* gamma,
                                                const float* const* beta, const float* const* w, const float* const* b, const int32_t* A,
-                                               float* const* out, const int32_t* out_pitch) {
+                                               float* const* out, const int32_t* out_pitch, float eps) {
     std::string bad = check_groups("mms_marl_heads_act", groups);
     if (!bad.empty()) return bad;
-    if (!h || !gamma || !beta || !w || !b || !A || !out || M < 0 || H <= 0 || H > 1024) return "mms_marl_heads_act: bad arguments (1 <= H <= 1024)";
+    const bool ln = eps >= 0.f;                          // eps < 0: the plain output layer -- gamma / beta are not read (NULL allowed)
+    if (!h || (ln && (!gamma || !beta)) || !w || !b || !A || !out || M < 0 || H <= 0 || H > 1024) return "mms_marl_heads_act: bad arguments (1 <= H <= 1024)";
     for (int g = 0; g < groups; g++) {
-        if (!h[g] || !gamma[g] || !beta[g] || !w[g] || !b[g] || !out[g] || A[g] < 1 || A[g] > 16)
+        if (!h[g] || (ln && (!gamma[g] || !beta[g])) || !w[g] || !b[g] || !out[g] || A[g] < 1 || A[g] > 16)
             return "mms_marl_heads_act: null pointer in a group, or outputs outside 1..16";
         if (out_pitch && out_pitch[g] < A[g]) return "mms_marl_heads_act: out_pitch below the number of outputs";
     }

@@ -516,6 +516,13 @@ __global__ void __launch_bounds__(256) layernorm_rows_kernel(LayerNormArgs a) {
 // (ROWS = 2 for small launches -- the PPO bootstrap value head, one network x 4096 rows: 128 blocks of 32 rows left half the CUs idle,
 //  18.9 us; with 8 rows per block every CU has two)
 constexpr int kHeadRows = 8;
+
+// log(std) + 0.5 log(2 pi), the part of a Gaussian log-density that does not depend on the draw: evaluated in double and rounded ONCE
+// (per lane / per block, outside the row loops), so that logp = fma(-z / 2, z, -this) carries two roundings.  The fp32 logf of this
+// build (fast-math: v_log_f32 x ln 2) is a full ulp of log2(std) off, 1.7e-7 at std = 0.1 -- as much as everything else together.
+// Keep the SUM in double: (float)log((double)sd) + c would round twice, and as fp32 arithmetic it falls under this file's fast-math.
+__device__ __forceinline__ float log_density_const(float sd) { return (float)(log((double)sd) + 0.9189385332046727); }
+
 template <int ROWS>
 __global__ void __launch_bounds__(256) marl_heads_kernel(HeadsArgs a) {
     extern __shared__ __attribute__((aligned(16))) float s_w[];          // [A][H]
@@ -525,15 +532,17 @@ __global__ void __launch_bounds__(256) marl_heads_kernel(HeadsArgs a) {
     const float* __restrict__ beta = a.beta[g];
     for (int k = threadIdx.x; k < A * H; k += 256) s_w[k] = a.w[g][k];
     __syncthreads();
+    const bool ln = a.eps >= 0.f;                       // (eps < 0: no LayerNorm in front of the output layer; gamma / beta are not read and may be NULL)
     float gm[kLnPerLane], bt[kLnPerLane];
 #pragma unroll
     for (int i = 0; i < kLnPerLane; i++) {
         const int k = lane + 64 * i;
-        gm[i] = (k < H) ? gamma[k] : 0.f;
-        bt[i] = (k < H) ? beta[k] : 0.f;
+        gm[i] = (ln && k < H) ? gamma[k] : 0.f;
+        bt[i] = (ln && k < H) ? beta[k] : 0.f;
     }
     const float bias = (lane < A) ? a.b[g][lane] : 0.f;
     const float sd = (a.std[g] && lane < A) ? a.std[g][lane] : 0.f;
+    const float lk = (a.std[g] && lane < A) ? log_density_const(sd) : 0.f;
     const int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * ROWS;
     for (int r = 0; r < ROWS; r++) {
         const int64_t row = row0 + r;
@@ -542,7 +551,7 @@ __global__ void __launch_bounds__(256) marl_heads_kernel(HeadsArgs a) {
         float v[kLnPerLane];
 #pragma unroll
         for (int i = 0; i < kLnPerLane; i++) v[i] = (lane + 64 * i < H) ? h[lane + 64 * i] : 0.f;
-        if (a.eps >= 0.f) {                             // (eps < 0: no LayerNorm in front of the output layer)
+        if (ln) {
             float mean, rstd;
             row_stats(v, H, lane, a.eps, mean, rstd);
 #pragma unroll
@@ -568,7 +577,7 @@ __global__ void __launch_bounds__(256) marl_heads_kernel(HeadsArgs a) {
             const float z = rand_normal(a.seed + (uint64_t)g, (uint64_t)(a.row_offset + row), (uint64_t)c, (uint32_t)lane);
             out[lane] = mine + sd * z;                  // Normal.sample
             // FixedNormal.log_probs (distributions.py:31-34) is the PER-DIMENSION log-density: the reference keeps [M, A], no sum
-            if (a.logp[g]) a.logp[g][row * a.out_pitch[g] + lane] = -0.5f * z * z - logf(sd) - 0.9189385332046727f;
+            if (a.logp[g]) a.logp[g][row * a.out_pitch[g] + lane] = fmaf(-0.5f * z, z, -lk);
         }
         if (lane == 0 && a.counters[g]) a.counters[g][row] = c + 1;
     }
@@ -639,13 +648,16 @@ hipError_t launch_row_stats_chan(const RowStatsArgs& a, int groups, hipStream_t 
 
 // thread = (row, network): finishes the output head of the last split layer (HeadsFinishArgs) and samples as marl_heads_kernel does
 __global__ void __launch_bounds__(256) marl_heads_finish_kernel(HeadsFinishArgs a) {
+    __shared__ float s_lk[16];                                           // log(std_j) + 0.5 log(2 pi), once per block
     const int g = blockIdx.y;
+    const int A = a.A[g];
+    if (a.std[g] && (int)threadIdx.x < A) s_lk[threadIdx.x] = log_density_const(a.std[g][threadIdx.x]);
+    __syncthreads();
     const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (row >= a.M) return;
     float mean, m2;
     chan_combine(reinterpret_cast<const float2*>(a.part[g]), a.M, row, a.slots, mean, m2);
     const float rstd = 1.0f / sqrtf(m2 / (float)a.width + a.eps);
-    const int A = a.A[g];
     float* out = a.out[g] + row * a.out_pitch[g];
     const int64_t c = (a.std[g] && a.counters[g]) ? a.counters[g][row] : 0;
     float dots[16];                                                      // a row's partials of one slot are contiguous: 16-byte loads, coalesced over the rows
@@ -672,7 +684,7 @@ __global__ void __launch_bounds__(256) marl_heads_finish_kernel(HeadsFinishArgs 
                 const float sd = a.std[g][j];
                 const float z = rand_normal(a.seed + (uint64_t)g, (uint64_t)(a.row_offset + row), (uint64_t)c, (uint32_t)j);
                 out[j] = mu + sd * z;
-                if (a.logp[g]) a.logp[g][row * a.out_pitch[g] + j] = -0.5f * z * z - logf(sd) - 0.9189385332046727f;
+                if (a.logp[g]) a.logp[g][row * a.out_pitch[g] + j] = fmaf(-0.5f * z, z, -s_lk[j]);
             }
         }
     }
