@@ -212,22 +212,27 @@ int mms_set_obs_outputs(mms_handle h, int32_t raw, int32_t clipped);
 int mms_bind_rollout_out(mms_handle h, float* rew_out, uint8_t* done_out);
 
 /* MARL wrapper views (multi_vec_task.py:105-142): obs_all [N,A,per_agent+shared] from a clamped
- * observation buffer [N, A*per_agent+shared]. */
+ * observation buffer [N, A*per_agent+shared].  n >= 0 (n = 0: an empty batch, nothing is read or written), agents >= 1,
+ * per_agent >= 1, shared >= 0, both pointers required when n > 0.  Bad arguments return non-zero with mms_last_error(NULL) and write
+ * nothing. */
 int mms_marl_views(int device, const float* obs_clipped, float* obs_all, int64_t n, int32_t agents,
                    int32_t per_agent, int32_t shared, void* hip_stream);
 
 /* PPO GAE (storage.py:51-65).  rewards/values/returns/advantages are [T,N] f32, dones [T,N] u8,
  * last_values [N].  Writes returns and UN-normalised advantages, and stats[0..2] =
- * {sum(adv), sum(adv^2), count} as float64 so that ranks can all-reduce them.  */
+ * {sum(adv), sum(adv^2), count} as float64 so that ranks can all-reduce them.  Every pointer is required, T >= 1, N >= 1.  Bad
+ * arguments return non-zero with mms_last_error(NULL) and write nothing. */
 int mms_gae_ppo(int device, const float* rewards, const uint8_t* dones, const float* values,
                 const float* last_values, float* returns, float* advantages, double* stats,
                 int32_t T, int64_t N, float gamma, float lam, void* hip_stream);
-/* advantages := (advantages - mean) / (std + 1e-8) with the unbiased std from stats. */
+/* advantages := (advantages - mean) / (std + 1e-8) with the unbiased std from stats.  Both pointers are required, count >= 1.  Bad
+ * arguments return non-zero with mms_last_error(NULL) and write nothing. */
 int mms_adv_normalize(int device, float* advantages, const double* stats, int64_t count, void* hip_stream);
 /* mms_gae_ppo + mms_adv_normalize for ONE rank (nothing to all-reduce in between), the whole of storage.py:51-65: the scan leaves
  * per-block partial sums instead of float64 atomics and the normalisation sums them in a fixed order -- bit-reproducible, and stats
  * needs no zeroing (the atomics' 24-byte memset costs two fill kernels inside a captured rollout).  stats: f64 [MMS_GAE_STATS_DOUBLES]
- * = {sum(adv), sum(adv^2), count} of the un-normalised advantages, then scratch for the partials. */
+ * = {sum(adv), sum(adv^2), count} of the un-normalised advantages, then scratch for the partials.  Every pointer is required, T >= 1,
+ * N >= 1.  Bad arguments return non-zero with mms_last_error(NULL) and write nothing. */
 #define MMS_GAE_STATS_DOUBLES (3 + 2 * 2048)
 int mms_gae_ppo_normalized(int device, const float* rewards, const uint8_t* dones, const float* values, const float* last_values,
                            float* returns, float* advantages, double* stats, int32_t T, int64_t N, float gamma, float lam,
@@ -244,14 +249,17 @@ int mms_layer_clock_probe(int device, uint64_t* out, int32_t slots);
 
 /* MARL GAE (separated_buffer.py:153-164, use_proper_time_limits=False): value_preds [T+1,N]
  * (row T already holds next_value), masks [T+1,N], rewards [T,N], returns [T+1,N];
- * denormalisation x*sqrt(var)+mean when use_norm (PopArt / ValueNorm). */
+ * denormalisation x*sqrt(var)+mean when use_norm (PopArt / ValueNorm): norm_mean and norm_var [1] are then required (and not read
+ * otherwise).  Row T of returns is not written.  rewards, value_preds, masks and returns are required, T >= 1, N >= 1.  Bad arguments
+ * return non-zero with mms_last_error(NULL) and write nothing. */
 int mms_gae_marl(int device, const float* rewards, const float* value_preds, const float* masks,
                  float* returns, int32_t T, int64_t N, float gamma, float lam,
                  int32_t use_norm, const float* norm_mean, const float* norm_var, void* hip_stream);
 
 /* The same for all A agents of all envs in one launch (rollout-buffer fusion):
  * value_preds / returns [T+1,N,A] (agent fastest), rewards [T,N] and masks [T+1,N] stored once per env instead of
- * once per agent buffer (runner.py:250-255 inserts the same reward / mask into ten buffers); norm_mean / norm_var [A]. */
+ * once per agent buffer (runner.py:250-255 inserts the same reward / mask into ten buffers); norm_mean / norm_var [A].  The same
+ * rules, and A >= 1.  Bad arguments return non-zero with mms_last_error(NULL) and write nothing. */
 int mms_gae_marl_agents(int device, const float* rewards, const float* value_preds, const float* masks,
                         float* returns, int32_t T, int64_t N, int32_t A, float gamma, float lam,
                         int32_t use_norm, const float* norm_mean, const float* norm_var, void* hip_stream);
@@ -264,7 +272,9 @@ int mms_gae_marl_agents(int device, const float* rewards, const float* value_pre
  *   action   = mean + scale * noise;   log_prob_i = sum_j (-0.5 noise_ij^2 - log(scale_j) - 0.5 log(2 pi))
  * Destinations (any may be NULL): actions_out [N,A] (e.g. the engine's "actions" buffer), act_slot / mu_slot / sigma_slot
  * [N,A], logp_slot / value_slot [N].  sigma_slot receives log_std broadcast, which is what module.py:87 returns as sigma.
- * counters is a device array [N] of int64 so that a captured hipGraph draws fresh noise on every replay. */
+ * counters is a device array [N] of int64 so that a captured hipGraph draws fresh noise on every replay.
+ * mean, log_std and counters are required, N >= 0 (N = 0 succeeds and touches nothing), 1 <= A <= 128.  Bad arguments return non-zero
+ * with mms_last_error(NULL) and write nothing. */
 int mms_ppo_act(int device, const float* mean, const float* value, const float* log_std, uint64_t seed, int64_t* counters,
                 int64_t row_offset, int32_t reference_scale, float* actions_out, float* act_slot, float* logp_slot,
                 float* value_slot, float* mu_slot, float* sigma_slot, int64_t N, int32_t A, void* hip_stream);
@@ -274,7 +284,9 @@ int mms_ppo_act(int device, const float* mean, const float* value, const float* 
  * same sampling and stores; hidden [N,H] f32 is the output of the last activation, weight [A,H] and bias [A] are torch's Linear
  * parameters; H must be a multiple of 64, A <= 128.  Critic (module.py:49: nn.Linear(vf_hid_sizes[-1], 1)) when vhidden is given:
  * value_i = vhidden[i, :] . vweight + vbias[0] (vhidden [N,VH] f32 = output of the critic's last activation, VH a multiple of 4)
- * goes to value_slot and `value` is ignored; vhidden = NULL: `value` [N] (or NULL) is stored as in mms_ppo_act. */
+ * goes to value_slot and `value` is ignored; vhidden = NULL: `value` [N] (or NULL) is stored as in mms_ppo_act.
+ * hidden, weight, vhidden and vweight are read as 16-byte vectors and must be 16-byte aligned (rows then are: H and VH are multiples
+ * of 4).  Bad arguments return non-zero with mms_last_error(NULL) and write nothing. */
 int mms_ppo_heads_act(int device, const float* hidden, const float* weight, const float* bias, int32_t H, const float* value,
                       const float* vhidden, const float* vweight, const float* vbias, int32_t VH, const float* log_std, uint64_t seed,
                       int64_t* counters, int64_t row_offset, int32_t reference_scale, float* actions_out, float* act_slot,

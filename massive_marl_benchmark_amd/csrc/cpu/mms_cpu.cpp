@@ -133,6 +133,7 @@ static int cpu_only(int device) {
 }
 MMS_API int mms_marl_views(int device, const float* obs_clipped, float* obs_all, int64_t n, int32_t agents, int32_t per_agent, int32_t shared, void*) {
     if (cpu_only(device)) return 1;
+    if (refused(check_marl_views(obs_clipped, obs_all, n, agents, per_agent, shared))) return 1;
     const int64_t total = n * agents * (per_agent + shared);
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < total; i++) obs_all[i] = obs_clipped[mms::marl_view_source(i, agents, per_agent, shared)];
@@ -141,14 +142,26 @@ MMS_API int mms_marl_views(int device, const float* obs_clipped, float* obs_all,
 MMS_API int mms_gae_ppo(int device, const float* rewards, const uint8_t* dones, const float* values, const float* last_values, float* returns,
                         float* advantages, double* stats, int32_t T, int64_t N, float gamma, float lam, void*) {
     if (cpu_only(device)) return 1;
+    if (refused(check_gae_ppo(rewards, dones, values, last_values, returns, advantages, stats, T, N))) return 1;
+    // partial sums per 256 columns (a block of the device's launch), added in order: the result does not depend on the number of threads
+    // or on the order in which they finish (an OpenMP reduction's does), so mms_gae_ppo_normalized is bit-reproducible here as well
+    const int64_t chunks = (N + 255) / 256;
+    std::vector<double> psum((size_t)chunks), psq((size_t)chunks);
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < chunks; c++) {
+        double s = 0.0, q = 0.0;
+        const int64_t end = (c + 1) * 256 < N ? (c + 1) * 256 : N;
+        for (int64_t i = c * 256; i < end; i++) mms::gae_ppo_column(rewards, dones, values, last_values, returns, advantages, T, N, i, gamma, lam, s, q);
+        psum[(size_t)c] = s; psq[(size_t)c] = q;
+    }
     double sum = 0.0, sq = 0.0;
-#pragma omp parallel for schedule(static) reduction(+ : sum, sq)
-    for (int64_t i = 0; i < N; i++) mms::gae_ppo_column(rewards, dones, values, last_values, returns, advantages, T, N, i, gamma, lam, sum, sq);
+    for (int64_t c = 0; c < chunks; c++) { sum += psum[(size_t)c]; sq += psq[(size_t)c]; }
     stats[0] = sum; stats[1] = sq; stats[2] = (double)T * (double)N;
     return 0;
 }
 MMS_API int mms_adv_normalize(int device, float* advantages, const double* stats, int64_t count, void*) {
     if (cpu_only(device)) return 1;
+    if (refused(check_adv_normalize(advantages, stats, count))) return 1;
     float fm, inv;
     mms::adv_norm_params(stats, fm, inv);
 #pragma omp parallel for schedule(static)
@@ -171,6 +184,7 @@ MMS_API int mms_gae_ppo_normalized(int device, const float* rewards, const uint8
 MMS_API int mms_gae_marl(int device, const float* rewards, const float* value_preds, const float* masks, float* returns, int32_t T, int64_t N,
                          float gamma, float lam, int32_t use_norm, const float* norm_mean, const float* norm_var, void*) {
     if (cpu_only(device)) return 1;
+    if (refused(check_gae_marl("mms_gae_marl", rewards, value_preds, masks, returns, T, N, 1, use_norm, norm_mean, norm_var))) return 1;
     const float mean = use_norm ? norm_mean[0] : 0.f, var = use_norm ? norm_var[0] : 1.f;
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < N; i++) mms::gae_marl_column(rewards, value_preds, masks, returns, T, N, N, i, i, gamma, lam, use_norm, mean, var);
@@ -179,6 +193,7 @@ MMS_API int mms_gae_marl(int device, const float* rewards, const float* value_pr
 MMS_API int mms_gae_marl_agents(int device, const float* rewards, const float* value_preds, const float* masks, float* returns, int32_t T,
                                 int64_t N, int32_t A, float gamma, float lam, int32_t use_norm, const float* norm_mean, const float* norm_var, void*) {
     if (cpu_only(device)) return 1;
+    if (refused(check_gae_marl("mms_gae_marl_agents", rewards, value_preds, masks, returns, T, N, A, use_norm, norm_mean, norm_var))) return 1;
     const int64_t cols = N * A;
 #pragma omp parallel for schedule(static)
     for (int64_t c = 0; c < cols; c++) {

@@ -256,12 +256,14 @@ __attribute__((visibility("default"))) int mms_bind_policy_head(mms_handle h, co
 
 __attribute__((visibility("default"))) int mms_marl_views(int device, const float* obs_clipped, float* obs_all, int64_t n, int32_t agents, int32_t per_agent, int32_t shared, void* s) {
     MMS_DEV(device)
+    if (refused(check_marl_views(obs_clipped, obs_all, n, agents, per_agent, shared))) return 1;
     MMS_FREE(mms::launch_marl_views(obs_clipped, obs_all, n, agents, per_agent, shared, (hipStream_t)s));
     return 0;
 }
 __attribute__((visibility("default"))) int mms_gae_ppo(int device, const float* rewards, const uint8_t* dones, const float* values, const float* last_values, float* returns,
                 float* advantages, double* stats, int32_t T, int64_t N, float gamma, float lam, void* s) {
     MMS_DEV(device)
+    if (refused(check_gae_ppo(rewards, dones, values, last_values, returns, advantages, stats, T, N))) return 1;
     MMS_FREE(mms::launch_gae_ppo(rewards, dones, values, last_values, returns, advantages, stats, T, N, gamma, lam, (hipStream_t)s));
     return 0;
 }
@@ -274,12 +276,14 @@ __attribute__((visibility("default"))) int mms_gae_ppo_normalized(int device, co
 }
 __attribute__((visibility("default"))) int mms_adv_normalize(int device, float* advantages, const double* stats, int64_t count, void* s) {
     MMS_DEV(device)
+    if (refused(check_adv_normalize(advantages, stats, count))) return 1;
     MMS_FREE(mms::launch_adv_normalize(advantages, stats, count, (hipStream_t)s));
     return 0;
 }
 __attribute__((visibility("default"))) int mms_gae_marl(int device, const float* rewards, const float* value_preds, const float* masks, float* returns, int32_t T, int64_t N,
                  float gamma, float lam, int32_t use_norm, const float* norm_mean, const float* norm_var, void* s) {
     MMS_DEV(device)
+    if (refused(check_gae_marl("mms_gae_marl", rewards, value_preds, masks, returns, T, N, 1, use_norm, norm_mean, norm_var))) return 1;
     MMS_FREE(mms::launch_gae_marl(rewards, value_preds, masks, returns, T, N, gamma, lam, use_norm, norm_mean, norm_var, (hipStream_t)s));
     return 0;
 }
@@ -288,6 +292,7 @@ __attribute__((visibility("default"))) int mms_gae_marl_agents(int device, const
                                                                float* returns, int32_t T, int64_t N, int32_t A, float gamma, float lam,
                                                                int32_t use_norm, const float* norm_mean, const float* norm_var, void* s) {
     MMS_DEV(device)
+    if (refused(check_gae_marl("mms_gae_marl_agents", rewards, value_preds, masks, returns, T, N, A, use_norm, norm_mean, norm_var))) return 1;
     MMS_FREE(mms::launch_gae_marl_agents(rewards, value_preds, masks, returns, T, N, A, gamma, lam, use_norm, norm_mean, norm_var, (hipStream_t)s));
     return 0;
 }

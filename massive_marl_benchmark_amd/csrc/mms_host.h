@@ -295,6 +295,34 @@ static inline std::string check_gae_ppo_normalized(const float* rewards, const u
     return {};
 }
 
+static inline std::string check_gae_ppo(const float* rewards, const uint8_t* dones, const float* values, const float* last_values,
+                                        const float* returns, const float* advantages, const double* stats, int32_t T, int64_t N) {
+    if (!rewards || !dones || !values || !last_values || !returns || !advantages || !stats || T < 1 || N < 1)
+        return "mms_gae_ppo: bad arguments (null pointer, T < 1 or N < 1)";
+    return {};
+}
+
+static inline std::string check_adv_normalize(const float* advantages, const double* stats, int64_t count) {
+    if (!advantages || !stats || count < 1) return "mms_adv_normalize: bad arguments (null pointer or count < 1)";
+    return {};
+}
+
+// mms_gae_marl (A = 1) and mms_gae_marl_agents
+static inline std::string check_gae_marl(const char* entry, const float* rewards, const float* value_preds, const float* masks, const float* returns,
+                                         int32_t T, int64_t N, int32_t A, int32_t use_norm, const float* norm_mean, const float* norm_var) {
+    if (!rewards || !value_preds || !masks || !returns || T < 1 || N < 1 || A < 1)
+        return std::string(entry) + ": bad arguments (null pointer, T < 1, N < 1 or A < 1)";
+    if (use_norm && (!norm_mean || !norm_var)) return std::string(entry) + ": use_norm needs norm_mean and norm_var";
+    return {};
+}
+
+// (n = 0, an empty batch, is accepted: nothing is launched over)
+static inline std::string check_marl_views(const float* obs_clipped, const float* obs_all, int64_t n, int32_t agents, int32_t per_agent, int32_t shared) {
+    if (n < 0 || agents < 1 || per_agent < 1 || shared < 0 || (n > 0 && (!obs_clipped || !obs_all)))
+        return "mms_marl_views: bad arguments (null pointer, n < 0, agents < 1, per_agent < 1 or shared < 0)";
+    return {};
+}
+
 static inline std::string check_ppo_act(const float* mean, const float* log_std, const int64_t* counters, int64_t N, int32_t A) {
     if (!mean || !log_std || !counters || N < 0 || A <= 0 || A > 128) return "mms_ppo_act: bad arguments (A must be in 1..128)";
     return {};
@@ -307,6 +335,8 @@ static inline std::string check_ppo_heads_act(const float* hidden, const float* 
         return "mms_ppo_heads_act: bad arguments (A must be in 1..128, H a positive multiple of 64)";
     if (vhidden && (!vweight || !vbias || VH <= 0 || (VH % 4) != 0))
         return "mms_ppo_heads_act: the value head needs weight, bias and a hidden width that is a multiple of 4";
+    if ((addr(hidden) | addr(weight) | addr(vhidden) | addr(vweight)) & 15)
+        return "mms_ppo_heads_act: hidden, weight, vhidden and vweight must be 16-byte aligned";
     return {};
 }
 

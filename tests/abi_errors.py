@@ -155,6 +155,23 @@ def check_abi_error_paths(L, device, messages=None):
     fails(L.mms_marl_heads_act(device, 1, 8, 8, one, one, one, one, one, (ctypes.c_int32 * 1)(17), None, one, None, None, None, 0, 0, 1e-5, None))
     fails(L.mms_gae_ppo_normalized(device, zp, zp, zp, zp, zp, zp, zp, 0, 1, 0.9, 0.9, None), contains="T < 1")
     fails(L.mms_gae_ppo_normalized(device, zp, zp, zp, None, zp, zp, zp, 1, 1, 0.9, 0.9, None), contains="null")
+    # the rollout tail: GAE, normalisation, MARL views (tests/ppo_rollout_check.py also holds their outputs untouched)
+    fails(L.mms_gae_ppo(device, zp, zp, zp, zp, zp, zp, zp, 0, 1, 0.9, 0.9, None), contains="mms_gae_ppo: bad arguments")
+    fails(L.mms_gae_ppo(device, zp, zp, zp, zp, zp, zp, zp, 1, 0, 0.9, 0.9, None), contains="N < 1")
+    fails(L.mms_gae_ppo(device, zp, zp, zp, zp, zp, zp, None, 1, 1, 0.9, 0.9, None), contains="null")
+    fails(L.mms_adv_normalize(device, zp, zp, 0, None), contains="count < 1")
+    fails(L.mms_adv_normalize(device, zp, None, 1, None), contains="null")
+    fails(L.mms_gae_marl(device, zp, zp, zp, zp, 0, 1, 0.9, 0.9, 0, None, None, None), contains="mms_gae_marl: bad arguments")
+    fails(L.mms_gae_marl(device, zp, zp, zp, None, 1, 1, 0.9, 0.9, 0, None, None, None), contains="null")
+    fails(L.mms_gae_marl(device, zp, zp, zp, zp, 1, 1, 0.9, 0.9, 1, zp, None, None), contains="use_norm needs")
+    fails(L.mms_gae_marl_agents(device, zp, zp, zp, zp, 1, 1, 0, 0.9, 0.9, 0, None, None, None), contains="A < 1")
+    fails(L.mms_gae_marl_agents(device, zp, zp, zp, zp, 1, 0, 1, 0.9, 0.9, 0, None, None, None), contains="mms_gae_marl_agents: bad arguments")
+    fails(L.mms_gae_marl_agents(device, zp, zp, zp, zp, 1, 1, 2, 0.9, 0.9, 1, None, zp, None), contains="use_norm needs")
+    fails(L.mms_marl_views(device, zp, zp, 1, 0, 1, 0, None), contains="agents < 1")
+    fails(L.mms_marl_views(device, zp, zp, -1, 1, 1, 0, None), contains="n < 0")
+    fails(L.mms_marl_views(device, None, zp, 1, 1, 1, 0, None), contains="null")
+    assert L.mms_marl_views(device, None, None, 0, 2, 1, 0, None) == 0                # an empty batch: accepted
+    assert L.mms_ppo_act(device, zp, None, zp, 0, zp, 0, 1, None, None, None, None, None, None, 0, 1, None) == 0   # N = 0: a success that touches nothing
     fails(L.mms_layer_clock_probe(device, zp, 0), contains="slots")
     fails(L.mms_layer_clock_probe(device, ctypes.c_void_p(zp.value + 4), 1), contains="aligned")
     assert L.mms_layer_clock_probe(device, None, 0) == 0                              # off: always accepted
@@ -174,6 +191,10 @@ def check_abi_error_paths(L, device, messages=None):
     fails(L.mms_split_planes16_group(device, 1, 8, 8, 8, al, al, al, al, 0, 0, None, None, None, off4, 0.0, None), contains="misaligned stat")
     fails(L.mms_weight_planes16_group(device, 1, n8, k8, al, al, al, off8, None, None), contains="misaligned")
     fails(L.mms_fold_planes16_group(device, 1, n8, k8, al, None, None, None, off8, al, None, None, None, None, None), contains="misaligned")
+    for k in range(4):                                                                # hidden, weight, vhidden, vweight of mms_ppo_heads_act, one at a time
+        q = [vp(base + (8 if i == k else 0)) for i in range(4)]
+        fails(L.mms_ppo_heads_act(device, q[0], q[1], vp(base), 64, None, q[2], q[3], vp(base), 4, vp(base), 0, vp(base), 0, 1, None, None, None, None, None, None,
+                                  1, 1, None), contains="16-byte aligned")
     a4 = (ctypes.c_int32 * 1)(4)
     fails(L.mms_marl_heads_finish(device, 1, 8, 2, off4, al, al, al, a4, None, al, None, None, None, 0, 0, 1e-5, None), contains="8-byte aligned")
     fails(L.mms_marl_heads_finish(device, 1, 8, 2, al, off8, al, al, a4, None, al, None, None, None, 0, 0, 1e-5, None), contains="16-byte aligned")

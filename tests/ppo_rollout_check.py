@@ -1,0 +1,836 @@
+"""Per-entry checks of the PPO rollout's tail (include/mms.h: mms_ppo_act, mms_ppo_heads_act, mms_gae_ppo, mms_adv_normalize,
+mms_gae_ppo_normalized, mms_gae_marl, mms_gae_marl_agents, mms_marl_views) -- one check list for both builds:
+tests/test_ppo_rollout.py runs it on libmms_cpu.so, tests/test_ppo_rollout_gpu.py on libmms.so.
+
+Every function takes env = (L, device_index, stream, torch_device) and drives the C ABI through ctypes.  Truth is numpy float64 of the
+formula the header documents, on the same fp32 inputs.  Every output is NaN-filled before the launch and has a guard (one row, or one
+element) behind it; a NaN in an output or a touched guard fails.  Every gate is per output element with a scale built from absolute
+values; u = 2^-24 is the unit roundoff of fp32.  Where a bound is derived, the docstring counts the roundings (first order), the
+bound is TWICE that count, and the same formula evaluated in numpy float32 must stay within half of the bound (the yardstick: the
+bound is neither vacuous nor unreachable).  No bound is fitted to a kernel's output.  Each check returns (and records with
+parity.record) its worst observed error / bound; with `mutation` set a check corrupts its own truth and only returns the ratio
+(tests/test_ppo_rollout.py: every mutation must miss its gate by 100 x)."""
+import ctypes
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+if __name__ == "__main__":                                          # the child of section 4 runs this file as a script
+    _here = os.path.dirname(os.path.abspath(__file__))
+    for _d in (_here, os.path.dirname(_here)):
+        if _d not in sys.path:
+            sys.path.insert(0, _d)
+
+import parity
+from massive_marl_benchmark_amd import _lib
+
+U = 2.0 ** -24
+HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+F = np.float32
+DESTS = ("actions_out", "act_slot", "logp_slot", "value_slot", "mu_slot", "sigma_slot")
+
+
+# ---- plumbing ------------------------------------------------------------------------------------------------------------------
+def _p(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _sync(tdev):
+    if torch.device(tdev).type == "cuda":
+        torch.cuda.synchronize()
+
+
+def _where(tdev):
+    return "gpu" if torch.device(tdev).type == "cuda" else "cpu"
+
+
+def _up(a, tdev):
+    return torch.from_numpy(np.array(a, copy=True, order="C")).to(tdev)              # (a copy: on the CPU build the tensor would alias the array)
+
+
+def _ok(L, rc, what):
+    _lib.check(rc, None, what, L)
+
+
+class Out:
+    """A NaN-filled output of `shape` with a guard behind it (one row of a matrix, one element of a vector)."""
+
+    def __init__(self, shape, tdev, dtype=torch.float32, fill=float("nan")):
+        self.shape = tuple(int(s) for s in shape)
+        self.n = int(np.prod(self.shape))
+        self.buf = torch.full((self.n + (self.shape[-1] if len(self.shape) > 1 else 1),), fill, dtype=dtype, device=tdev)
+        self.t = self.buf[:self.n].view(self.shape)
+
+    def guard_intact(self):
+        return bool(torch.isnan(self.buf[self.n:]).all())
+
+    def untouched(self):
+        return bool(torch.isnan(self.buf).all())
+
+    def get(self):
+        assert self.guard_intact(), "guard written"
+        return self.t.cpu().numpy().copy()
+
+
+def _ratio(err, tol):
+    """largest err / tol (0 where err is 0); inf if anything is not finite: a NaN (an output still poisoned) never passes"""
+    err, tol = np.asarray(err, np.float64), np.asarray(tol, np.float64)
+    if err.size == 0:
+        return 0.0
+    if not (np.isfinite(err).all() and np.isfinite(tol).all()):
+        return float("inf")
+    return float(np.where(err > 0, err / np.maximum(tol, 1e-300), 0.0).max())
+
+
+def report(tdev, name, **ratios):
+    print("%s/ppo_rollout/%s: %s" % (_where(tdev), name, ", ".join("%s %.3g" % kv for kv in sorted(ratios.items()))))
+    parity.record("%s/ppo_rollout/%s" % (_where(tdev), name), **ratios)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint64)
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and bool((_bits(a) == _bits(b)).all())
+
+
+# ---- the noise stream, restated (csrc/mms_lane.h: mix32, rand_uniform, rand_normal) ---------------------------------------------
+def _mix32(x):
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7feb352d)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846ca68b)
+    return x ^ (x >> np.uint32(16))
+
+
+def uniform_int(seed, row, ctr, k):
+    """rand_uniform's 24-bit integer (the uniform is this times 2^-24), exact: seed a Python int, row / ctr uint64 arrays, k uint32 array"""
+    u32, u64 = np.uint32, np.uint64
+    lo = lambda v: (v & u64(0xFFFFFFFF)).astype(u32)
+    hi = lambda v: (v >> u64(32)).astype(u32)
+    s = np.array([seed & (2 ** 64 - 1)], u64)
+    x = _mix32(lo(s) ^ u32(0x9E3779B9))
+    x = _mix32(x ^ hi(s))
+    x = _mix32(x ^ lo(row))
+    x = _mix32(x ^ hi(row) ^ u32(0x85EBCA6B))
+    x = _mix32(x ^ lo(ctr))
+    x = _mix32(x ^ hi(ctr) ^ (k * u32(0xC2B2AE35)))
+    return x >> u32(8)
+
+
+def normal64(seed, row_offset, ctr, A):
+    """Box-Muller in float64 on the stream's two uniforms for rows 0 .. len(ctr), actions 0 .. A: [N, A].  The uniforms are the fp32
+    numbers the stream is defined by (u1 = n1 2^-24 + 2^-25 rounded to fp32, "moved off zero"; u2 = n2 2^-24, exact); the logarithm, the
+    root, 2 pi and the cosine are float64."""
+    with np.errstate(over="ignore"):
+        N = len(ctr)
+        row = (np.int64(row_offset) + np.arange(N, dtype=np.int64)).astype(np.uint64)[:, None]
+        c = np.asarray(ctr, np.int64).astype(np.uint64)[:, None]
+        j = np.arange(A, dtype=np.uint32)[None, :]
+        n1 = uniform_int(seed, row, c, np.uint32(2) * j)
+        n2 = uniform_int(seed, row, c, np.uint32(2) * j + np.uint32(1))
+    u1 = (n1.astype(F) * F(2.0 ** -24) + F(2.0 ** -25)).astype(np.float64)
+    u2 = n2.astype(np.float64) * 2.0 ** -24
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+
+# ---- the heads entry and the sampling entry ---------------------------------------------------------------------------------------
+def head_waves(H, A):
+    """the K split launch_ppo_head_act picks: 8, 4, 2 or 1 waves by H % 512, 256, 128, and 4 when 8 waves x 8 column tiles pass 64 KB"""
+    w = 8 if H % 512 == 0 else 4 if H % 256 == 0 else 2 if H % 128 == 0 else 1
+    if (w + 1) * 16 * (16 * ((A + 15) // 16)) * 4 > 64 * 1024:
+        w = 4
+    return w
+
+
+def heads_data(N, H, A, VH, seed):
+    """hidden [N, H], weight [A, H], bias [A], vhidden [N, VH], vweight [VH], vbias [1], value [N], log_std [A] spread over [-3, 0.5]"""
+    g = np.random.default_rng(seed)
+    r = lambda *sh: g.standard_normal(sh).astype(F)
+    pr = dict(N=N, H=H, A=A, VH=VH, hidden=r(N, H) * F(0.8) + F(0.1), weight=r(A, H) / F(H ** 0.5), bias=r(A) * F(0.1), vhidden=r(N, VH) * F(0.7) - F(0.2),
+              vweight=r(VH) / F(VH ** 0.5), vbias=r(1) * F(0.3), value=r(N), log_std=g.permutation(np.linspace(-3.0, 0.5, A)).astype(F))
+    if A == 1:
+        pr["log_std"][:] = F(-1.25)
+    pr["mean"] = r(N, A)                                                     # the input of mms_ppo_act
+    return pr
+
+
+def _dev(pr, tdev):
+    key = "_dev_%s" % tdev
+    if key not in pr:
+        pr[key] = {k: _up(v, tdev) for k, v in pr.items() if isinstance(v, np.ndarray)}
+    return pr[key]
+
+
+def sample_run(env, pr, entry="heads", *, N=None, row0=0, ref_scale=1, value="array", vhead=True, counters=None, seed=0x1234567811, row_offset=0,
+               dests=DESTS):
+    """One mms_ppo_heads_act (entry "heads") or mms_ppo_act ("act") call on rows row0 .. row0 + N of pr.  value: "array" | "nan" (a
+    NaN-filled array) | None (NULL); vhead: the value head (heads only).  dests: the destinations handed over, the others are NULL.
+    Returns name -> numpy for every destination (NULL ones: None), "counters" and "value_in"."""
+    L, di, stream, tdev = env
+    d = _dev(pr, tdev)
+    N = pr["N"] - row0 if N is None else N
+    A = pr["A"]
+    cnt = _up(np.zeros(max(N, 1), np.int64) if counters is None else np.asarray(counters, np.int64), tdev)     # (N = 0: one counter, to stay 0)
+    shapes = dict(actions_out=(N, A), act_slot=(N, A), logp_slot=(N,), value_slot=(N,), mu_slot=(N, A), sigma_slot=(N, A))
+    o = {k: (Out(shapes[k], tdev) if k in dests else None) for k in DESTS}
+    vin = None if value is None else (d["value"][row0:row0 + N] if value == "array" else torch.full((N,), float("nan"), device=tdev))
+    ptr = [None if o[k] is None else _p(o[k].buf) for k in DESTS]
+    if entry == "heads":
+        vh = vhead and pr["VH"] > 0
+        rc = L.mms_ppo_heads_act(di, _p(d["hidden"][row0:]), _p(d["weight"]), _p(d["bias"]), pr["H"], _p(vin), _p(d["vhidden"][row0:]) if vh else None,
+                                 _p(d["vweight"]) if vh else None, _p(d["vbias"]) if vh else None, pr["VH"] if vh else 0, _p(d["log_std"]), seed, _p(cnt), row_offset,
+                                 ref_scale, *ptr, N, A, stream)
+    else:
+        rc = L.mms_ppo_act(di, _p(d["mean"][row0:]), _p(vin), _p(d["log_std"]), seed, _p(cnt), row_offset, ref_scale, *ptr, N, A, stream)
+    _ok(L, rc, "mms_ppo_%s" % ("heads_act" if entry == "heads" else "act"))
+    _sync(tdev)
+    res = {k: (None if o[k] is None else o[k].get()) for k in DESTS}
+    res["counters"] = cnt.cpu().numpy()[:N]
+    assert N > 0 or int(cnt[0]) == 0
+    res["value_in"] = None if vin is None else vin.cpu().numpy()
+    return res
+
+
+def value_head_f32(vh, vw, vb):
+    """the value head in numpy float32 in the kernel's order (head_block.h): lane l of 64 takes floats 4 l .. 4 l + 3 of every 256-float
+    trip, adds the four products to its partial sum, a six-level xor butterfly adds the lanes, then the bias"""
+    N, VH = vh.shape
+    pad = (-VH) % 256
+    p = np.pad(vh * vw[None, :], ((0, 0), (0, pad))).reshape(N, -1, 64, 4)
+    part = np.zeros((N, 64), F)
+    for t in range(p.shape[1]):
+        part = part + (((p[:, t, :, 0] + p[:, t, :, 1]) + p[:, t, :, 2]) + p[:, t, :, 3])
+    for m in (32, 16, 8, 4, 2, 1):
+        part = part + part[:, np.arange(64) ^ m]
+    return part[:, 0] + vb[0]
+
+
+def logp_truth(act, mu, log_std, ref_scale, A, exp_l=False):
+    """(truth [N], bound [N], z [N, A], scale [A]) of the log-probability identity, float64, from the call's own fp32 act, mu, log_std:
+      logp_i = sum_j (-0.5 z_ij^2 - log(scale_j) - 0.5 log 2 pi),  z_ij = (act_ij - mu_ij) / scale_j,  scale_j = exp(l_j)^2 | exp(l_j).
+    Roundings the kernel makes that the truth does not (u each, first order; T_ij = z^2 / 2 + |log scale| + 0.5 log 2 pi):
+      scale: expf within one ulp (2 u); squared: 2 x 2 u + u = 5 u =: e_s (reference_scale), else 2 u.  It moves z by e_s |z|.
+      act = fl(mu + fl(scale z)): u |scale z| and u |act|, seen through 1 / scale: u (|z| + |act| / scale) on z.
+      so d(z^2 / 2) = |z| (u |act| / scale + u |z| + e_s |z|).
+      log(scale): logf of the rounded scale: e_s + u |log scale| (reference_scale); l itself otherwise: 0.
+      three operations per term (the product, two subtractions), each on a number below T_ij, and the constant's own rounding: 4 u T_ij.
+      the row sum: ceil(A / 64) - 1 additions in the lane, six butterfly levels: (ceil(A / 64) + 5) u sum_j T_ij.
+    bound_i = 2 x the sum of these (the factor the module docstring allows)."""
+    l = log_std.astype(np.float64)
+    scale = np.exp(l) if (not ref_scale or exp_l) else np.exp(l) ** 2
+    z = (act.astype(np.float64) - mu.astype(np.float64)) / scale
+    lsc = np.log(scale)
+    truth = (-0.5 * z * z - lsc - HALF_LOG_2PI).sum(1)
+    T = 0.5 * z * z + np.abs(lsc) + HALF_LOG_2PI
+    e_s = 5 * U if ref_scale else 2 * U
+    per = np.abs(z) * (U * np.abs(act.astype(np.float64)) / scale + U * np.abs(z) + e_s * np.abs(z)) + (e_s + U * np.abs(lsc) if ref_scale else 0.0) + 4 * U * T
+    bound = 2.0 * (per.sum(1) + ((A + 63) // 64 + 5) * U * T.sum(1))
+    return truth, bound, z, scale
+
+
+def logp_yardstick(A, ref_scale, N=64, seed=3):
+    """the identity's bound against numpy float32 of the header's formula (sampling and log-probability, term by term in order)"""
+    g = np.random.default_rng(seed)
+    mu = g.standard_normal((N, A)).astype(F)
+    l = np.linspace(-3.0, 0.5, A).astype(F)
+    z = normal64(seed, 0, np.zeros(N, np.int64), A).astype(F)
+    sd = np.exp(l)
+    scale = sd * sd if ref_scale else sd
+    lsc = np.log(scale) if ref_scale else l
+    act = mu + scale[None, :] * z
+    lp = np.zeros(N, F)
+    for j in range(A):
+        lp = lp + (F(-0.5) * z[:, j] * z[:, j] - lsc[j] - F(0.9189385332046727))
+    truth, bound, _, _ = logp_truth(act, mu, l, ref_scale, A)
+    r = _ratio(np.abs(lp.astype(np.float64) - truth), bound)
+    assert r <= 0.5, ("logp yardstick", A, ref_scale, r)
+    return r
+
+
+def gate_sample(pr, o, entry, *, N, row0=0, ref_scale=1, seed, row_offset=0, counters=None, vhead=True, waves=None, mutation=None):
+    """Every gate of one call's outputs `o` (sample_run): {"mu", "value", "draw", "logp"} -> worst error / bound, exact parts asserted.
+      mu (heads): |mu - h W^T - b| <= (H / WAVES + WAVES + 2) u (|h| |W|^T + |b|): the serial fp32 chain of one wave, the wave-order sum
+        and the bias; (act): mu_slot is the mean, bit for bit.
+      value (heads, value head): float64 dot product; a product passes through its own rounding, at most three additions inside its group
+        of four, one accumulation per 256-float trip, six butterfly levels and the bias: (trips + 11) u (|vh| . |vw| + |vb|), doubled;
+        value_head_f32 is the yardstick.
+      draw: z = (act - mu) / scale in float64 against Box-Muller in float64 on the restated stream (normal64):
+        |z - z64| <= 2e-5 + u (|mu| + |scale z|) / scale.
+      logp: logp_truth's identity and bound.
+    Exact: counters + 1; sigma_slot = log_std broadcast; actions_out = act_slot bit for bit; value_slot (no value head) = value."""
+    A = pr["A"]
+    ctr0 = np.zeros(N, np.int64) if counters is None else np.asarray(counters, np.int64)
+    rows = slice(row0, row0 + N)
+    out = {}
+    assert (o["counters"] == ctr0 + 1).all(), "counters must advance by exactly 1 per row"
+    assert same_bits(o["sigma_slot"], np.broadcast_to(pr["log_std"], (N, A)).copy()), "sigma_slot is log_std broadcast"
+    assert same_bits(o["actions_out"], o["act_slot"]), "actions_out and act_slot differ"
+    mu, act = o["mu_slot"], o["act_slot"]
+    if entry == "heads":
+        h, w, b = pr["hidden"][rows].astype(np.float64), pr["weight"].astype(np.float64), pr["bias"].astype(np.float64)
+        ref = h @ w.T + b
+        if mutation == "drop_k":                                     # one group of four k dropped from row 0
+            ref[0] -= h[0, 4:8] @ w[:, 4:8].T
+        W = head_waves(pr["H"], A) if waves is None else waves
+        out["mu"] = _ratio(np.abs(mu - ref), (pr["H"] / W + W + 2) * U * (np.abs(h) @ np.abs(w).T + np.abs(b)))
+    else:
+        assert same_bits(mu, pr["mean"][rows]), "mu_slot is the mean"
+    if entry == "heads" and vhead:
+        vh, vw, vb = pr["vhidden"][rows], pr["vweight"], pr["vbias"]
+        ref = vh.astype(np.float64) @ vw.astype(np.float64) + float(vb[0])
+        if mutation == "value_from_value":
+            ref = pr["value"][rows].astype(np.float64)
+        tol = 2.0 * (-(-pr["VH"] // 256) + 11) * U * (np.abs(vh).astype(np.float64) @ np.abs(vw).astype(np.float64) + abs(float(vb[0])))
+        yard = _ratio(np.abs(value_head_f32(vh, vw, vb) - vh.astype(np.float64) @ vw.astype(np.float64) - float(vb[0])), tol)
+        assert yard <= 0.5, ("value head yardstick", pr["VH"], yard)
+        out["value"] = _ratio(np.abs(o["value_slot"] - ref), tol)
+    elif o["value_in"] is not None:
+        assert same_bits(o["value_slot"], o["value_in"]), "value_slot must be `value` bit for bit"
+    else:
+        assert np.isnan(o["value_slot"]).all(), "value == NULL must leave value_slot alone"
+    truth, bound, z, scale = logp_truth(act, mu, pr["log_std"], ref_scale, A, exp_l=(mutation == "exp_l"))
+    ctr = ctr0.copy()
+    if mutation == "counter":
+        ctr[0] += 1
+    z64 = normal64(seed, row_offset, ctr, A)
+    out["draw"] = _ratio(np.abs(z - z64), 2e-5 + U * (np.abs(mu.astype(np.float64)) + np.abs(scale * z)) / scale)
+    out["logp"] = _ratio(np.abs(o["logp_slot"] - truth), bound)
+    return out
+
+
+def _merge(worst, r):
+    for k, v in r.items():
+        worst[k] = max(worst.get(k, 0.0), v)
+
+
+# ---- 1. the actor head's mean (and with it every other gate of the call) ------------------------------------------------------------
+HS = (64, 128, 192, 256, 384, 512, 768, 1024, 1536)
+AS = (1, 15, 16, 17, 33, 64, 65, 80, 112, 113, 128)
+NS = (1, 15, 16, 17, 37, 1003, 4096)
+
+
+def heads_shapes():
+    """(N, H, A): every H at A = 80 and 128, every A at H = 512 and 64 (N = 37: three row blocks, the last of five rows), every N at (512, 80)"""
+    s = [(37, H, A) for H in HS for A in (80, 128)] + [(37, H, A) for H in (512, 64) for A in AS] + [(N, 512, 80) for N in NS]
+    return sorted(set(s))
+
+
+def check_heads(env, N, H, A, VH=None, mutation=None):
+    """mms_ppo_heads_act at one shape with the value head (VH differs from H), both reference_scale values, counters and row_offset not
+    zero, the seed with a high word: every gate of gate_sample."""
+    VH = H + 68 if VH is None else VH
+    pr = heads_data(N, H, A, VH, 1000 * H + 10 * A + N)
+    worst = {}
+    for ref_scale in ((1,) if mutation else (0, 1)):
+        ctr = (np.arange(N, dtype=np.int64) * 7) % 5 + (2 ** 32 if N == 17 else 0)
+        kw = dict(ref_scale=ref_scale, seed=0x9E3779B97F4A7C15 + ref_scale, row_offset=3 + (2 ** 33 if N == 15 else 0), counters=ctr)
+        o = sample_run(env, pr, "heads", value="nan", **kw)
+        _merge(worst, gate_sample(pr, o, "heads", N=N, mutation=mutation, **kw))
+    if mutation is None:
+        assert max(worst.values()) <= 1.0, ("heads", N, H, A, worst)
+    return worst
+
+
+# ---- 2. the value head ------------------------------------------------------------------------------------------------------------------
+def check_value_head(env, VH, N=37, H=64, A=3):
+    """The vhidden path at width VH (below, at, and off the 256-float stride of its loop), VH != H, N not a multiple of 16 and N = 1:
+    `value` as a NaN-filled array and as NULL must both leave value_slot equal to the head's value (bit for bit the same); with vhidden
+    = NULL value_slot is `value` bit for bit, and untouched with value = NULL too."""
+    worst = {}
+    for n in (N, 1):
+        pr = heads_data(n, H, A, VH, 77 * VH + n)
+        kw = dict(seed=5, row_offset=0)
+        a = sample_run(env, pr, "heads", value="nan", **kw)
+        b = sample_run(env, pr, "heads", value=None, **kw)
+        c = sample_run(env, pr, "heads", value="array", **kw)
+        assert same_bits(a["value_slot"], b["value_slot"]) and same_bits(a["value_slot"], c["value_slot"]), "`value` must be ignored when vhidden is given"
+        _merge(worst, gate_sample(pr, a, "heads", N=n, **kw))
+        for value in ("array", None):
+            o = sample_run(env, pr, "heads", value=value, vhead=False, **kw)
+            gate_sample(pr, o, "heads", N=n, vhead=False, **kw)                                   # asserts value_slot == value / untouched
+            assert same_bits(o["act_slot"], a["act_slot"]) and same_bits(o["logp_slot"], a["logp_slot"])
+    assert max(worst.values()) <= 1.0, ("value head", VH, worst)
+    return worst
+
+
+# ---- 3. sampling --------------------------------------------------------------------------------------------------------------------------
+def _pr_for(entry, N, A, seed):
+    return heads_data(N, 64, A, 68, seed)
+
+
+def check_sampling_exact(env, entry, N=37, A=80):
+    """The exact parts (gate_sample asserts them) with every destination, and one destination at a time: each equals the full call's,
+    a NULL destination is skipped, the counters still advance."""
+    pr = _pr_for(entry, N, A, 11)
+    kw = dict(seed=77, row_offset=5, counters=np.arange(N) % 3)
+    full = sample_run(env, pr, entry, **kw)
+    gate_sample(pr, full, entry, N=N, **kw)
+    for k in DESTS:
+        one = sample_run(env, pr, entry, dests=(k,), **kw)
+        assert same_bits(one[k], full[k]), k
+        assert all(one[q] is None for q in DESTS if q != k) and (one["counters"] == kw["counters"] + 1).all(), k
+    if entry == "act":                                                       # N = 0: a success that touches nothing
+        o = sample_run(env, pr, entry, N=0)
+        assert o["counters"].size == 0
+
+
+def check_keying(env, entry, A=17):
+    """The stream is keyed (seed, row_offset + row, counter, j), bit for bit: rows k .. k + n under row_offset 0 equal rows 0 .. n under
+    row_offset k; a row's outputs depend neither on N nor on its position in its block (37 rows alone, and from row 1003 of 4096);
+    (row 1, counter 0) and (row 0, counter 1) and neighbouring j draw differently; both words of the seed and the high word of
+    row_offset + row matter."""
+    pr = _pr_for(entry, 4096, A, 21)
+    seed = 0xABCDEF0112345678
+    big = sample_run(env, pr, entry, seed=seed, row_offset=0)
+    k, n = 1003, 37
+    small = sample_run(env, pr, entry, N=n, row0=k, seed=seed, row_offset=k)
+    for d in DESTS:
+        assert same_bits(small[d], big[d][k:k + n]), ("row_offset / N / block position", d)
+    z = lambda o: (o["act_slot"].astype(np.float64) - o["mu_slot"]) / np.exp(2.0 * pr["log_std"].astype(np.float64))
+    zb = z(big)
+    assert (np.abs(zb[:, :-1] - zb[:, 1:]) > 1e-6).mean() > 0.99, "neighbouring j"
+    two = sample_run(env, pr, entry, N=2, seed=seed, counters=[1, 0])       # (row 0, counter 1), (row 1, counter 0)
+    z2 = z(two)
+    assert (np.abs(z2[0] - z2[1]) > 1e-6).mean() > 0.9 and (np.abs(z2[0] - zb[0]) > 1e-6).mean() > 0.9 and same_bits(two["act_slot"][1], big["act_slot"][1])
+    base = sample_run(env, pr, entry, N=33, seed=seed, row_offset=5)
+    for what, kw in (("seed low word", dict(seed=seed ^ 1, row_offset=5)), ("seed high word", dict(seed=seed ^ (1 << 32), row_offset=5)),
+                     ("row_offset + 2^32", dict(seed=seed, row_offset=5 + 2 ** 32))):
+        other = sample_run(env, pr, entry, N=33, **kw)
+        assert (np.abs(z(other) - z(base)) > 1e-6).mean() > 0.9, what
+        if entry == "heads":
+            assert same_bits(other["mu_slot"], base["mu_slot"]), what
+
+
+def check_draw(env, entry, mutation=None):
+    """The draw and the log-probability identity at A = 1, 80, 128, both reference_scale values, log_std over [-3, 0.5], keys with high
+    words (seed, row_offset past 2^32, counters past 2^32): gate_sample's `draw` and `logp`."""
+    worst = {}
+    for A in (1, 80, 128):
+        for ref_scale in ((1,) if mutation else (0, 1)):
+            logp_yardstick(A, ref_scale)
+            N = 1003
+            pr = _pr_for(entry, N, A, 31 + A)
+            ctr = np.arange(N, dtype=np.int64) % 7 + np.where(np.arange(N) % 5 == 0, 2 ** 32 + 3, 0)
+            kw = dict(ref_scale=ref_scale, seed=0xFEDCBA9876543210, row_offset=2 ** 32 + 12345, counters=ctr)
+            o = sample_run(env, pr, entry, **kw)
+            r = gate_sample(pr, o, entry, N=N, mutation=mutation, **kw)
+            _merge(worst, {k: r[k] for k in ("draw", "logp")})
+    if mutation is None:
+        report(env[3], "%s_draw" % entry, **worst)
+        assert worst["draw"] <= 1.0 and worst["logp"] <= 1.0, (entry, worst)
+    return worst
+
+
+def check_moments(env, entry, N=4096, A=80):
+    """4096 x 80 draws at three counters: mean and standard deviation of z within 0.01 of (0, 1), the project's gate on this quantity;
+    no two of the three replays are equal."""
+    pr = _pr_for(entry, N, A, 41)
+    zs = []
+    for c in range(3):
+        o = sample_run(env, pr, entry, seed=99, counters=np.full(N, c), dests=("act_slot", "mu_slot"))
+        zs.append((o["act_slot"].astype(np.float64) - o["mu_slot"]) / np.exp(2.0 * pr["log_std"].astype(np.float64)))
+    assert not any(np.array_equal(zs[a], zs[b]) for a, b in ((0, 1), (0, 2), (1, 2))), "two replays drew the same noise"
+    z = np.stack(zs)
+    m, s = float(z.mean()), float(z.std())
+    report(env[3], "%s_moments" % entry, mean=abs(m) / 0.01, std=abs(s - 1) / 0.01)
+    assert abs(m) <= 0.01 and abs(s - 1) <= 0.01, (m, s)
+
+
+def check_cross_entry(env, N=1003, A=80):
+    """The slots of one mms_ppo_act call fed to mms_ppo_loss with the same mu and log_std and adv = 1: the loss recomputes the
+    log-probability the rollout stored.  kl = mean_i sum_j (l - os + (exp(os)^2 + 0) / (2 exp(l)^2) - 0.5) with os = l: the quotient is
+    0.5 after at most 16 roundings (two exponentials within one ulp, squared; a product, a quotient): |kl| <= 8 u A.  surrogate = -mean_i
+    exp(logp_i - old_logp_i): |surrogate + 1| within the mean of the per-row identity bounds (logp_truth)."""
+    L, di, stream, tdev = env
+    pr = _pr_for("act", N, A, 51)
+    o = sample_run(env, pr, "act", ref_scale=1, seed=7)
+    _, bound, _, _ = logp_truth(o["act_slot"], o["mu_slot"], pr["log_std"], 1, A)
+    t = {k: _up(o[k], tdev) for k in ("act_slot", "logp_slot", "mu_slot", "sigma_slot")}
+    d = _dev(pr, tdev)
+    ones, zeros = torch.ones(N, device=tdev), torch.zeros(N, device=tdev)
+    need = ctypes.c_int64(-1)
+    _ok(L, L.mms_ppo_loss(di, N, A, *([None] * 11), 0.2, 1.0, 0.0, 1, None, None, None, None, None, ctypes.byref(need), stream), "mms_ppo_loss (size query)")
+    ws = torch.zeros(int(need.value) + 512, dtype=torch.uint8, device=tdev)
+    wp = ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256)
+    out = Out((5,), tdev)
+    _ok(L, L.mms_ppo_loss(di, N, A, _p(d["mean"]), _p(d["log_std"]), _p(zeros), None, _p(t["act_slot"]), _p(t["logp_slot"]), _p(ones), _p(zeros), _p(zeros),
+                          _p(t["mu_slot"]), _p(t["sigma_slot"]), 0.2, 1.0, 0.0, 1, _p(out.buf), None, None, None, wp, ctypes.byref(need), stream), "mms_ppo_loss")
+    _sync(tdev)
+    res = out.get()
+    r = dict(kl=abs(float(res[4])) / (8 * U * A), surrogate=abs(float(res[1]) + 1.0) / float(bound.mean()))
+    report(tdev, "cross_entry", **r)
+    assert r["kl"] <= 1.0 and r["surrogate"] <= 1.0, (res, r)
+    return r
+
+
+# ---- 4. the 32-row form (MMS_HEAD_RT=2, read once per process: a fresh child) ---------------------------------------------------------------
+DUMP_CALLS = ((4096, 512, 80), (37, 1024, 33), (32, 512, 128), (33, 512, 113), (16, 512, 80))
+DUMP_KW = dict(ref_scale=1, seed=0x51ED270B1234, row_offset=9)
+
+
+def dump_calls(env):
+    """every output of the heads calls of section 4 (all with the value head): "N_H_A/name" -> array"""
+    res = {}
+    for N, H, A in DUMP_CALLS:
+        pr = heads_data(N, H, A, H + 68, 7000 + N + H + A)
+        o = sample_run(env, pr, "heads", value=None, counters=np.arange(N) % 3, **DUMP_KW)
+        for k in DESTS + ("counters",):
+            res["%d_%d_%d/%s" % (N, H, A, k)] = o[k]
+    return res
+
+
+def check_dump(child, mine):
+    """The child's outputs (32 rows per block where N >= 32 and eight waves split K) against this process's at the default: bit for bit
+    where the wave split and the order of products agree (A <= 112, and N < 32: the 16-row form in both); for A >= 113 the default
+    falls back to four waves, and the child's outputs are held to the gates of sections 1-3 with WAVES = 8."""
+    worst = {}
+    for N, H, A in DUMP_CALLS:
+        tag = "%d_%d_%d/" % (N, H, A)
+        if A <= 112:
+            for k in DESTS + ("counters",):
+                assert child[tag + k].shape == mine[tag + k].shape and child[tag + k].tobytes() == mine[tag + k].tobytes(), (tag, k)
+            continue
+        pr = heads_data(N, H, A, H + 68, 7000 + N + H + A)
+        o = {k: child[tag + k] for k in DESTS + ("counters",)}
+        o["value_in"] = None
+        r = gate_sample(pr, o, "heads", N=N, counters=np.arange(N) % 3, waves=8, **DUMP_KW)
+        assert max(r.values()) <= 1.0, (tag, r)
+        _merge(worst, r)
+    return worst
+
+
+# ---- 5. GAE -----------------------------------------------------------------------------------------------------------------------------
+GAE_SHAPES_SMALL = ((1, 2), (8, 1), (1, 257), (13, 1000))
+GAE_SHAPES_CAP = ((2, 2048 * 256 + 5), (1, 3 * 2048 * 256 + 1))       # past grid_for's 2048 blocks of 256: the grid-stride loops' second trip
+GAE_REGIMES = ("random", "all_done", "none_done", "last_done", "gamma0", "lam0", "lam1", "shifted", "constant")
+
+
+def gae_data(T, N, regime, seed=0):
+    """rewards, values [T, N], last_values [N], dones [T, N] u8, gamma, lam.  all_done / constant: every step done and the data on a
+    2^-6 grid below 8, so that r - v and (r - v) + v are exact in fp32: returns = rewards and adv = r - v bit for bit (with arbitrary
+    fp32 data (r - v) + v need not round back to r).  constant: r = v + 0.5, every advantage 0.5.  shifted: the rewards moved so that
+    |mean adv| / std(adv) is about 1e3."""
+    g = np.random.default_rng(seed + 131 * T + N)
+    r = lambda *sh: g.standard_normal(sh).astype(F)
+    d = dict(T=T, N=N, rewards=r(T, N), values=r(T, N) * F(2), last=r(N) * F(2), dones=(g.random((T, N)) < 0.15).astype(np.uint8), gamma=F(0.96), lam=F(0.95))
+    if regime in ("all_done", "constant"):
+        grid = lambda *sh: (g.integers(-256, 257, sh) / 64.0).astype(F)
+        d["dones"][:] = 1
+        d["values"] = grid(T, N)
+        d["rewards"] = d["values"] + F(0.5) if regime == "constant" else grid(T, N)
+    elif regime == "none_done":
+        d["dones"][:] = 0
+    elif regime == "last_done":
+        d["dones"][:] = 0
+        d["dones"][T - 1] = 1
+    elif regime == "gamma0":
+        d["gamma"] = F(0)
+    elif regime == "lam0":
+        d["lam"] = F(0)
+    elif regime == "lam1":
+        d["lam"] = F(1)
+    elif regime == "shifted":
+        a0 = gae_truth(d)[1]
+        g1 = gae_truth(dict(d, rewards=np.ones((T, N), F), values=np.zeros((T, N), F), last=np.zeros(N, F)))[1]
+        d["rewards"] = (d["rewards"] + F(1e3 * max(a0.std(), 0.5) / g1.mean())).astype(F)
+    return d
+
+
+def gae_truth(d, dtype=np.float64, ignore_done=None):
+    """(returns, advantages, returns bound, advantages bound) of storage.py:51-65 in `dtype`, operation by operation as gae_ppo_column:
+      delta = r + nt gamma v' - v;  adv = delta + nt gamma lam adv';  ret = adv + v;  a = ret - v,  nt = 1 - done.
+    The running bound E_t of the scan's state beside it (u each, first order; nt and nt gamma are exact):
+      delta: the product, the sum, the difference, each on a number below D = |r| + gamma |v'| + |v|: 3 u D.
+      nt gamma lam adv': two products: 2 u |adv'|;  the sum: u |adv|.   All below 3 u (D + |adv'| + |adv|), c = 3:
+      E_t = nt gamma lam E_{t+1} + 3 u (|r| + gamma |v'| + |v| + |adv_{t+1}| + |adv_t|)
+    returns carry one more rounding, u |ret|; the advantages two, u |ret| + u |a|.  Both bounds are doubled."""
+    T, N = d["T"], d["N"]
+    c = lambda x: np.asarray(x).astype(dtype)
+    rew, val, gamma, lam = c(d["rewards"]), c(d["values"]), dtype(d["gamma"]), dtype(d["lam"])
+    done = d["dones"].copy()
+    if ignore_done is not None:
+        done[ignore_done] = 0
+    ret, adv, rb, ab = (np.zeros((T, N), dtype) for _ in range(4))
+    a, nv, E = np.zeros(N, dtype), c(d["last"]), np.zeros(N, np.float64)
+    for t in range(T - 1, -1, -1):
+        nt = dtype(1) - done[t].astype(dtype)
+        delta = rew[t] + nt * gamma * nv - val[t]
+        a_new = delta + nt * gamma * lam * a
+        D = np.abs(rew[t]) + gamma * np.abs(nv) + np.abs(val[t])
+        E = nt * gamma * lam * E + 3 * U * (D + np.abs(a) + np.abs(a_new)).astype(np.float64)
+        a = a_new
+        ret[t] = a + val[t]
+        adv[t] = ret[t] - val[t]
+        rb[t] = 2 * (E + U * np.abs(ret[t]))
+        ab[t] = 2 * (E + U * np.abs(ret[t]) + U * np.abs(adv[t]))
+        nv = val[t]
+    return ret, adv, rb, ab
+
+
+def norm_truth(a32, biased=False):
+    """(normalised advantages, bound) in float64 from the kernel's own fp32 raw advantages: (a - m) / (std + 1e-8), std unbiased.
+    Roundings of adv_norm_params and the kernel (u each): the mean rounded to fp32 moves every output by u |m| / s (s = std + 1e-8);
+    1 / s rounded to fp32, the difference and the product: 3 u |a - m| / s; the variance is formed in double as (sq - n m^2) / (n - 1),
+    which cancels: 2^-50 (sq / n) / var relative on s.  Doubled."""
+    a = a32.astype(np.float64).ravel()
+    n = a.size
+    m = a.mean()
+    var = ((a - m) ** 2).sum() / (n if biased else max(n - 1, 1))
+    s = math.sqrt(var) + 1e-8
+    ev = 2.0 ** -50 * (a * a).mean() / var if var > 0 else 0.0
+    out = (a - m) / s
+    tol = 2 * (U * abs(m) / s + (3 * U + ev) * np.abs(a - m) / s)
+    return out.reshape(a32.shape), tol.reshape(a32.shape), m, s
+
+
+def gae_run(env, d, entry, stats_fill=float("nan")):
+    """entry "raw": mms_gae_ppo; "two": mms_gae_ppo + mms_adv_normalize; "normalized": mms_gae_ppo_normalized -> (returns, advantages, stats[:3])"""
+    L, di, stream, tdev = env
+    T, N = d["T"], d["N"]
+    key = "_dev_%s" % tdev
+    if key not in d:
+        d[key] = [_up(d[k], tdev) for k in ("rewards", "dones", "values", "last")]
+    rew, done, val, last = d[key]
+    ret, adv = Out((T, N), tdev), Out((T, N), tdev)
+    stats = Out((3 + 2 * 2048,), tdev, dtype=torch.float64, fill=stats_fill)
+    args = (di, _p(rew), _p(done), _p(val), _p(last), _p(ret.buf), _p(adv.buf), _p(stats.buf), T, N, float(d["gamma"]), float(d["lam"]), stream)
+    if entry == "normalized":
+        _ok(L, L.mms_gae_ppo_normalized(*args), "mms_gae_ppo_normalized")
+    else:
+        _ok(L, L.mms_gae_ppo(*args), "mms_gae_ppo")
+        if entry == "two":
+            _ok(L, L.mms_adv_normalize(di, _p(adv.buf), _p(stats.buf), T * N, stream), "mms_adv_normalize")
+    _sync(tdev)
+    st = stats.buf.cpu().numpy()
+    if entry != "normalized":
+        assert np.isnan(st[3:]).all(), "mms_gae_ppo wrote past stats[0..2]"
+    elif math.isnan(stats_fill):
+        assert np.isnan(st[-1]), "stats guard written"
+    return ret.get(), adv.get(), st[:3].copy()
+
+
+def gae_yardstick(d):
+    """the running bound against the same recurrence in numpy float32"""
+    r64, a64, rb, ab = gae_truth(d)
+    r32, a32, _, _ = gae_truth(d, F)
+    y = max(_ratio(np.abs(r32 - r64), rb), _ratio(np.abs(a32 - a64), ab))
+    assert y <= 0.5, ("GAE yardstick", d["T"], d["N"], y)
+    n64, tol, m, s = norm_truth(a32)
+    if a32.size > 1 and s > 1e-6:
+        n32 = (a32 - F(m)) * F(1.0 / s)
+        yn = _ratio(np.abs(n32.astype(np.float64) - n64), tol)
+        assert yn <= 0.5, ("normalisation yardstick", d["T"], d["N"], yn)
+    return y
+
+
+def check_gae_ppo(env, T, N, regime, mutation=None):
+    """mms_gae_ppo, mms_adv_normalize and mms_gae_ppo_normalized on one (T, N, regime):
+      returns and raw advantages against gae_truth within its running bound; all_done / constant: returns = rewards, adv = r - v exactly.
+      stats against float64 sums of the call's own fp32 advantages at 1e-12 of sum |a| and sum a^2; the count exact.
+      both normalised forms against norm_truth of the raw advantages (mms_gae_ppo_normalized's returns must equal mms_gae_ppo's bit for
+      bit: the same column arithmetic, so the same raw advantages); constant advantages normalise to exactly 0, as the float64 truth.
+      mms_gae_ppo_normalized equals itself bit for bit on a second run from a 1e30-filled stats."""
+    d = gae_data(T, N, regime)
+    if mutation == "ignore_done":
+        d["dones"][T // 2, N // 2] = 1                                    # (a done the kernel sees and the truth ignores)
+    else:
+        gae_yardstick(d)
+    ret, adv, st = gae_run(env, d, "raw")
+    r64, a64, rb, ab = gae_truth(d, ignore_done=((T // 2, N // 2) if mutation == "ignore_done" else None))
+    r = dict(returns=_ratio(np.abs(ret - r64), rb), adv=_ratio(np.abs(adv - a64), ab))
+    if mutation == "ignore_done":
+        return r
+    a = adv.astype(np.float64)
+    r["stats_sum"] = abs(st[0] - a.sum()) / max(1e-12 * np.abs(a).sum(), 1e-300) if st[0] != a.sum() else 0.0
+    r["stats_sq"] = abs(st[1] - (a * a).sum()) / max(1e-12 * (a * a).sum(), 1e-300) if st[1] != (a * a).sum() else 0.0
+    assert st[2] == float(T) * float(N), "count"
+    if regime in ("all_done", "constant"):
+        assert same_bits(ret, d["rewards"]) and same_bits(adv, d["rewards"] - d["values"]), "all done: returns = rewards, adv = r - v"
+    n64, tol, m, s = norm_truth(adv, biased=(mutation == "biased"))
+    if T * N > 1:
+        for entry in ("two", "normalized"):
+            ret2, nadv, st2 = gae_run(env, d, entry)
+            assert same_bits(ret2, ret), (entry, "returns differ from mms_gae_ppo's")
+            assert st2[2] == float(T) * float(N) and abs(st2[0] - a.sum()) <= 1e-12 * np.abs(a).sum() and abs(st2[1] - (a * a).sum()) <= 1e-12 * (a * a).sum(), entry
+            if regime == "constant":
+                assert (n64 == 0).all() and (nadv == 0).all(), "constant advantages must normalise to exactly 0"
+            else:
+                r["norm_" + entry] = _ratio(np.abs(nadv - n64), tol)
+        if mutation is None:
+            _, again, st3 = gae_run(env, d, "normalized", stats_fill=1e30)
+            assert same_bits(again, nadv) and (st3 == st2).all(), "mms_gae_ppo_normalized must not depend on what stats held"
+    if mutation is None:
+        assert max(r.values()) <= 1.0, ("gae_ppo", T, N, regime, r)
+    return r
+
+
+def marl_data(T, N, A, seed=0, fractional=True):
+    """rewards [T, N], value_preds [T + 1, N, A], masks [T + 1, N] of 0 / 1 (and one 0.5), per-agent (mean, var) orders of magnitude apart"""
+    g = np.random.default_rng(seed + 17 * T + N + 1000 * A)
+    r = lambda *sh: g.standard_normal(sh).astype(F)
+    masks = (g.random((T + 1, N)) > 0.1).astype(F)
+    if fractional:
+        masks[T // 2 + 1 if T > 1 else 1, N // 2] = F(0.5)
+    mean = np.array([0.0, 10.0, -1000.0, 3.0, 0.5, -2.0, 100.0, 0.0, 1.0, 7.0][:A], F)
+    var = np.array([1.0, 1e-4, 1e4, 2.0, 0.25, 1e2, 1e-2, 1.0, 9.0, 1e3][:A], F)
+    return dict(T=T, N=N, A=A, rewards=r(T, N), vp=r(T + 1, N, A), masks=masks, mean=mean, var=var, gamma=F(0.99), lam=F(0.95))
+
+
+def marl_truth(d, use_norm, dtype=np.float64, shift_norm=False):
+    """(returns [T, N, A], bound) of separated_buffer.py:153-164 in `dtype`, operation by operation as gae_marl_column:
+      v = vp sqrt(var) + mean (use_norm);  delta = r + gamma v1 m - v0;  gae = delta + gamma lam m gae';  ret = gae + v0.
+    Roundings (u each, first order): the root (2.5 ulp = 5 u by the device build's reciprocal-based root), the product and the sum of the
+    denormalisation: dv = u (7 |vp sd| + |v|);  delta: two products, a sum, a difference below D = |r| + gamma |v1 m| + |v0|: 4 u D, and
+    the two values' own errors: gamma m dv1 + dv0;  gamma lam m gae': three products, 3 u |gae'|;  the sum: u |gae|:
+      E_t = gamma lam m E_{t+1} + 4 u (D + |gae_{t+1}| + |gae_t|) + gamma m dv1 + dv0;   ret: E_t + dv0 + u |ret|.   Doubled."""
+    T, N, A = d["T"], d["N"], d["A"]
+    c = lambda x: np.asarray(x).astype(dtype)
+    gamma, lam = dtype(d["gamma"]), dtype(d["lam"])
+    mean, var = c(d["mean"]), c(d["var"])
+    if shift_norm:                                                          # agent k's normaliser applied to agent k + 1
+        mean, var = np.roll(mean, 1), np.roll(var, 1)
+    sd = np.sqrt(var)
+    den = (lambda v: v * sd + mean) if use_norm else (lambda v: v)
+    dverr = (lambda v: U * (7 * np.abs(v * sd) + np.abs(v * sd + mean)).astype(np.float64)) if use_norm else (lambda v: np.zeros(v.shape))
+    rew, m_all, vp = c(d["rewards"]), c(d["masks"]), c(d["vp"])
+    ret, rb = np.zeros((T, N, A), dtype), np.zeros((T, N, A), np.float64)
+    gae, E = np.zeros((N, A), dtype), np.zeros((N, A), np.float64)
+    v1, dv1 = den(vp[T]), dverr(vp[T])
+    for t in range(T - 1, -1, -1):
+        v0, dv0 = den(vp[t]), dverr(vp[t])
+        m = m_all[t + 1][:, None]
+        delta = rew[t][:, None] + gamma * v1 * m - v0
+        new = delta + gamma * lam * m * gae
+        D = np.abs(rew[t])[:, None] + gamma * np.abs(v1) * m + np.abs(v0)
+        E = (gamma * lam * m * E + 4 * U * (D + np.abs(gae) + np.abs(new)) + gamma * m * dv1 + dv0).astype(np.float64)
+        gae = new
+        ret[t] = gae + v0
+        rb[t] = 2 * (E + dv0 + U * np.abs(ret[t]))
+        v1, dv1 = v0, dv0
+    return ret, rb
+
+
+def marl_run(env, d, use_norm, agent=None):
+    """mms_gae_marl_agents on [T + 1, N, A] (agent None) or mms_gae_marl on the strided copy of one agent: returns [T, N, A] | [T, N];
+    row T of returns must be untouched"""
+    L, di, stream, tdev = env
+    T, N, A = d["T"], d["N"], d["A"]
+    rew, masks, mean, var = (_up(d[k], tdev) for k in ("rewards", "masks", "mean", "var"))
+    if agent is None:
+        vp, ret = _up(d["vp"], tdev), Out((T + 1, N, A), tdev)
+        rc = L.mms_gae_marl_agents(di, _p(rew), _p(vp), _p(masks), _p(ret.buf), T, N, A, float(d["gamma"]), float(d["lam"]), use_norm,
+                                   _p(mean) if use_norm else None, _p(var) if use_norm else None, stream)
+    else:
+        vp, ret = _up(d["vp"][:, :, agent], tdev), Out((T + 1, N), tdev)
+        rc = L.mms_gae_marl(di, _p(rew), _p(vp), _p(masks), _p(ret.buf), T, N, float(d["gamma"]), float(d["lam"]), use_norm,
+                            _p(mean[agent:agent + 1]) if use_norm else None, _p(var[agent:agent + 1]) if use_norm else None, stream)
+    _ok(L, rc, "mms_gae_marl%s" % ("_agents" if agent is None else ""))
+    _sync(tdev)
+    got = ret.get()
+    assert np.isnan(got[T]).all(), "row T of returns written"
+    return got[:T]
+
+
+def check_gae_marl(env, T, N, A, mutation=None):
+    """mms_gae_marl_agents with and without use_norm against marl_truth within its running bound; the agents form equals A calls of
+    mms_gae_marl on strided copies bit for bit (at most three agents where N A is large)."""
+    d = marl_data(T, N, A)
+    r = {}
+    for use_norm in ((1,) if mutation else (0, 1)):
+        r64, rb = marl_truth(d, use_norm, shift_norm=(mutation == "shift_norm"))
+        if mutation is None:
+            y = _ratio(np.abs(marl_truth(d, use_norm, F)[0] - r64), rb)
+            assert y <= 0.5, ("MARL GAE yardstick", T, N, A, use_norm, y)
+        got = marl_run(env, d, use_norm)
+        r["norm%d" % use_norm] = _ratio(np.abs(got - r64), rb)
+        if mutation is None:
+            for k in range(A if N * A < 100000 else min(A, 2)):
+                assert same_bits(marl_run(env, d, use_norm, agent=k), np.ascontiguousarray(got[:, :, k])), ("agents form against one agent", k, use_norm)
+    if mutation is None:
+        assert max(r.values()) <= 1.0, ("gae_marl", T, N, A, r)
+    return r
+
+
+VIEW_SHAPES = ((5, 10, 38, 8), (3, 1, 7, 2), (4, 3, 5, 0), (257, 2, 1, 1), (2731, 10, 38, 8))     # the last: 1 256 260 elements, past the grid cap
+
+
+def check_marl_views(env):
+    """mms_marl_views: an exact gather against numpy indexing; agents = 1, shared = 0, one shape past the grid cap, an empty batch."""
+    L, di, stream, tdev = env
+    for n, agents, per, shared in VIEW_SHAPES:
+        obs = np.random.default_rng(n).standard_normal((n, agents * per + shared)).astype(F)
+        want = np.concatenate([obs[:, :agents * per].reshape(n, agents, per), np.broadcast_to(obs[:, None, agents * per:], (n, agents, shared))], axis=2)
+        out = Out((n, agents, per + shared), tdev)
+        src = _up(obs, tdev)
+        _ok(L, L.mms_marl_views(di, _p(src), _p(out.buf), n, agents, per, shared, stream), "mms_marl_views")
+        _sync(tdev)
+        assert same_bits(out.get(), np.ascontiguousarray(want)), (n, agents, per, shared)
+    out = Out((4,), tdev)
+    _ok(L, L.mms_marl_views(di, _p(out.buf), _p(out.buf), 0, 2, 1, 0, stream), "mms_marl_views (empty)")
+    _sync(tdev)
+    assert out.untouched()
+
+
+# ---- 6. refusals ------------------------------------------------------------------------------------------------------------------------
+def check_refusals(env):
+    """Bad arguments return non-zero with mms_last_error(NULL) and write nothing (every output stays NaN): NULL required pointers, T, N,
+    A, count < 1, use_norm without both statistics, misaligned hidden / weight / vhidden / vweight of mms_ppo_heads_act.  Nothing is
+    launched by a refused call.  Accepted: an empty view batch, mms_ppo_act with N = 0."""
+    L, di, stream, tdev = env
+    n = 0
+    z = torch.zeros(4096, device=tdev)
+    zb = torch.zeros(64, dtype=torch.uint8, device=tdev)
+    outs = [Out((8, 8), tdev) for _ in range(6)]
+    st = Out((3 + 2 * 2048,), tdev, dtype=torch.float64)
+    o = [_p(x.buf) for x in outs]
+    zp, sp = _p(z), _p(st.buf)
+
+    def refused(rc, contains):
+        nonlocal n
+        msg = _lib.last_error(None, L)
+        assert rc != 0 and msg and contains in msg, (rc, msg, contains)
+        _sync(tdev)
+        assert all(x.untouched() for x in outs) and st.untouched(), ("a refused call wrote", msg)
+        n += 1
+
+    gp = lambda **kw: L.mms_gae_ppo(di, *[kw.get(k, v) for k, v in (("rew", zp), ("done", _p(zb)), ("val", zp), ("last", zp), ("ret", o[0]), ("adv", o[1]), ("stats", sp),
+                                                                  ("T", 2), ("N", 4))], 0.9, 0.9, stream)
+    for kw in (dict(T=0), dict(N=0), dict(T=-1)) + tuple({k: None} for k in ("rew", "done", "val", "last", "ret", "adv", "stats")):
+        refused(gp(**kw), "mms_gae_ppo: bad arguments")
+    refused(L.mms_adv_normalize(di, o[0], sp, 0, stream), "mms_adv_normalize")
+    refused(L.mms_adv_normalize(di, None, sp, 8, stream), "mms_adv_normalize")
+    refused(L.mms_adv_normalize(di, o[0], None, 8, stream), "mms_adv_normalize")
+    for name, fn, extra in (("mms_gae_marl", L.mms_gae_marl, ()), ("mms_gae_marl_agents", L.mms_gae_marl_agents, (2,))):
+        gm = lambda rew=zp, vp=zp, m=zp, ret=o[0], T=2, N=4, extra=extra, un=0, mean=None, var=None: fn(di, rew, vp, m, ret, T, N, *extra, 0.9, 0.9, un, mean, var, stream)
+        for kw in (dict(T=0), dict(N=0), dict(rew=None), dict(vp=None), dict(m=None), dict(ret=None)):
+            refused(gm(**kw), name + ": bad arguments")
+        for kw in (dict(un=1), dict(un=1, mean=zp), dict(un=1, var=zp)):
+            refused(gm(**kw), name + ": use_norm needs")
+    refused(L.mms_gae_marl_agents(di, zp, zp, zp, o[0], 2, 4, 0, 0.9, 0.9, 0, None, None, stream), "A < 1")
+    for kw in ((None, o[0], 2, 2, 2, 1), (zp, None, 2, 2, 2, 1), (zp, o[0], -1, 2, 2, 1), (zp, o[0], 2, 0, 2, 1), (zp, o[0], 2, 2, 0, 1), (zp, o[0], 2, 2, 2, -1)):
+        refused(L.mms_marl_views(di, *kw, stream), "mms_marl_views: bad arguments")
+    cnt = torch.zeros(8, dtype=torch.int64, device=tdev)
+    base = z.data_ptr()
+    assert base % 16 == 0
+    for k in range(4):
+        q = [ctypes.c_void_p(base + (8 if i == k else 0)) for i in range(4)]
+        rc = L.mms_ppo_heads_act(di, q[0], q[1], zp, 64, None, q[2], q[3], zp, 4, zp, 1, _p(cnt), 0, 1, *o, 8, 8, stream)
+        refused(rc, "16-byte aligned")
+        assert bool((cnt == 0).all())
+    assert L.mms_ppo_act(di, zp, None, zp, 1, _p(cnt), 0, 1, *o, 0, 8, stream) == 0
+    _sync(tdev)
+    assert all(x.untouched() for x in outs) and bool((cnt == 0).all()), "mms_ppo_act with N = 0 must touch nothing"
+    return n
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "--dump":
+        L_, dev_, stream_ = _lib.for_device("cuda:0")
+        np.savez(sys.argv[2], **dump_calls((L_, dev_, stream_, "cuda")))
+    else:
+        sys.exit("usage: ppo_rollout_check.py --dump FILE.npz")
