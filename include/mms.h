@@ -46,6 +46,9 @@
  *   TRPO double backward of the KL's Hessian-vector product (:431)      mms_mlp_grad_rop
  *   PPO.update's loss head: KL, clipped surrogate, value loss, entropy  mms_ppo_loss
  *     and their backward (algorithms/rl/ppo/ppo.py:270-302)
+ *   MAPPO / HAPPO ppo_update's loss head: surrogate, entropy, PopArt /   mms_marl_ppo_loss
+ *     Huber value loss, masks and their backward
+ *     (algorithms/marl/mappo_trainer.py:63-179, happo_trainer.py:48-170)
  *
  * Ownership: the engine owns every buffer it reports through mms_get_tensor for the lifetime of the
  * handle; callers wrap them as NON-owning views and must keep the handle alive while any view exists.
@@ -604,6 +607,61 @@ int mms_ppo_loss(int device, int64_t M, int32_t A, const float* mu, const float*
                  const float* actions, const float* old_logp, const float* adv, const float* returns, const float* target_values,
                  const float* old_mu, const float* old_sigma, float clip, float value_coef, float entropy_coef, int32_t clipped_value,
                  float* out, float* dmu, float* dlog_std, float* dvalue, void* workspace, int64_t* ws_bytes, void* hip_stream);
+
+/* ---- The MAPPO / HAPPO update's loss head and its gradients in one call (csrc/marl_loss_kernels.hip) --------------------------------
+ * What agents/algorithms/marl/mappo_trainer.py:63-179 and happo_trainer.py:48-170 evaluate per minibatch behind
+ * ACTLayer.evaluate_actions (utils/act.py:154-165, FixedNormal.log_probs, util.py:23-29) for a Box action space: the per-dimension
+ * Gaussian log-density, the clipped surrogate (with HAPPO's factor), the entropy term, the PopArt-normalised, clipped, Huber or
+ * squared value loss, the active masks, and the gradients of the objective with respect to the networks' outputs.
+ * Dense inputs, the networks' outputs for the minibatch: mu [M, A], std [A] (sigmoid(log_std / std_x_coef) std_y_coef, formed by the
+ * caller), value [M].  Stored inputs, read in place: field F's row for minibatch row i is F.base + indices[i] * F.pitch (row i when
+ * indices == NULL), pitch in floats -- a SeparatedReplayBuffer's tensors (pitch A or 1) as well as one agent's view of a shared
+ * [T, N, agents, A] or [T+1, N, agents] block (pitch agents * A or agents).  actions and old_logp hold A floats per row (pitch >= A),
+ * adv, value_preds, returns, active_masks and factor one (pitch >= 1).  A [T+1, N, .] field is read through its first T N rows, so
+ * one flat index t N + n serves every field.  active_masks.base is required only with a mask flag and not read otherwise;
+ * factor.base NULL means f = 1.  All f32, indices int64.
+ *   logp_ij = -(a_ij - mu_ij)^2 / (2 std_j^2) - log std_j - 0.5 log 2pi                  per dimension, not summed (as stored)
+ *   r_i     = exp(sum_j (logp_ij - old_logp_ij))
+ *   s_i     = f_i min(r_i adv_i, clamp(r_i, 1 - clip, 1 + clip) adv_i)
+ *   w_i     = m_i / sum_k m_k where the respective mask flag (policy_masks / value_masks) is on, else 1 / M
+ *   policy_loss  = -sum_i w_i s_i
+ *   dist_entropy = sum_j (0.5 + 0.5 log 2pi + log std_j) * (policy_masks ? 1 : 1 / A)    (act.py:161 against act.py:163)
+ *   t_i     = use_norm ? (ret_i - norm_mean) / sqrt(norm_var) : ret_i                    norm_mean, norm_var: device scalars [1]
+ *   vc_i    = vp_i + clamp(v_i - vp_i, -clip, clip);  e_o = t_i - v_i;  e_c = t_i - vc_i
+ *   h(e)    = use_huber ? (|e| <= d: e^2 / 2;  e > d: d (|e| - d / 2);  e < -d: 0) : e^2 / 2    (util.py:23-26: b = (e > d))
+ *   vl_i    = clipped_value ? max(h(e_o), h(e_c)) : h(e_o);   value_loss = sum_i w_i vl_i
+ *   objective = policy_loss - entropy_coef dist_entropy + value_loss_coef value_loss
+ * out [5] = {objective, policy_loss, value_loss, dist_entropy, ratio_mean = mean_i r_i}.  dmu [M, A], dstd [A], dvalue [M] =
+ * d objective / d (mu, std, value), all three or none (none: the terms only) -- torch autograd's result, including how min, max and
+ * clamp split ties:
+ *   g_i      = -f_i adv_i r_i w_i   where 1 - clip <= r_i <= 1 + clip or adv_i r_i < adv_i clamp(r_i), else 0
+ *   dmu_ij   = g_i (a_ij - mu_ij) / std_j^2
+ *   dstd_j   = sum_i g_i ((a_ij - mu_ij)^2 / std_j^3 - 1 / std_j) - entropy_coef (policy_masks ? 1 : 1 / A) / std_j
+ *   h'(e)    = use_huber ? (|e| <= d: e;  e > d: d;  e < -d: 0) : e
+ *   dvalue_i = -value_loss_coef w_i h'(e_o)  where clipped_value is off, h(e_o) > h(e_c) or |v_i - vp_i| <= clip, else 0
+ * (one measure-zero difference: outside the clip range with exactly equal non-zero losses torch gives half the gradient, this none).
+ * row_logp [M] = sum_j logp_ij, or NULL: what HAPPO's factor update evaluates before and after an agent's update.
+ * Sums over rows are per-block partials in double, added in a fixed order and rounded once: no atomics, no memset, results
+ * bit-identical run to run; the lane roles and every sum's order depend on A alone.  Two launches on hip_stream, three with a mask
+ * flag (sum_k m_k first), no host synchronisation.  A mask sum of zero is the caller's error, as in the reference (0 / 0).
+ * The entry cannot see the values of indices: every one must be a valid row of every stored field.
+ * workspace / ws_bytes: mms_mlp_grad's convention (NULL stores the bytes needed and returns 0 -- nothing else is read; 256-byte aligned;
+ * a smaller one is an error; the CPU build needs 0 and runs on any aligned non-NULL workspace).  The workspace needs no initialisation.
+ * 1 <= M <= 0x7fffffff, 1 <= A <= MMS_MARL_LOSS_MAX_A.  Inputs are taken to be finite (finite-math device code).  Bad arguments return
+ * non-zero with mms_last_error(NULL) and write nothing. */
+#define MMS_MARL_LOSS_MAX_A 128
+typedef struct {
+    const float* base;
+    int64_t pitch;          /* floats from one row to the next */
+} mms_rows;
+typedef struct {
+    mms_rows actions, old_logp, adv, value_preds, returns, active_masks, factor;
+} mms_marl_loss_fields;
+int mms_marl_ppo_loss(int device, int64_t M, int32_t A, const float* mu, const float* std, const float* value, const int64_t* indices,
+                      const mms_marl_loss_fields* fields, float clip, float value_loss_coef, float entropy_coef, float huber_delta,
+                      int32_t use_huber, int32_t clipped_value, int32_t policy_masks, int32_t value_masks, int32_t use_norm,
+                      const float* norm_mean, const float* norm_var, float* out, float* dmu, float* dstd, float* dvalue, float* row_logp,
+                      void* workspace, int64_t* ws_bytes, void* hip_stream);
 
 const char* mms_last_error(mms_handle h);   /* h may be NULL: error of the last failed mms_create */
 int mms_abi_version(void);

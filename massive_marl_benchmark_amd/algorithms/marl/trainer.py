@@ -1,0 +1,201 @@
+"""MAPPO and HAPPO trainers with the update's loss head and its gradients in one call (loss.marl_ppo_loss / mms_marl_ppo_loss).
+
+Drop-ins for the reference's trainers (agents/algorithms/marl/mappo_trainer.py: MAPPO, happo_trainer.py: HAPPO): the constructor
+`(config, policy, device)`, the attributes (`policy`, `value_normalizer`, `clip_param`, ...), `ppo_update(sample, update_actor=True)`,
+`train(buffer, update_actor=True)`, `prep_training`, `prep_rollout`, the returned tuples and the `train_info` keys are theirs, so a
+runner that imports these classes in place of the reference's trains unchanged.
+
+The policy is taken as it is: `policy.actor`, `.critic`, `.actor_optimizer`, `.critic_optimizer`, with the module attributes that
+GroupedPolicyInference relies on (`.base.feature_norm`, `.base.mlp.fc1 / fc2`, `.act.action_out.{fc_mean, log_std, std_x_coef,
+std_y_coef}`, `.v_out`).  An update runs actor.base -> fc_mean and critic.base -> v_out in torch, forms std from log_std, calls
+marl_ppo_loss, does ONE backward() of the objective (the reference's two backward() calls reach disjoint parameter sets), clips the two
+gradient norms separately and steps both optimizers.  Recurrent policies and action spaces other than Box raise in the constructor;
+nothing falls back silently.
+
+`ppo_update` takes the reference's gathered tuple.  `train` draws the permutation exactly as feed_forward_generator does
+(torch.randperm(batch), the same slices), gathers only the network inputs (share_obs, obs) and the returns the normaliser's batch
+moments need, and hands the index vector and the buffer's own tensors to the loss: under the same torch seed it equals a loop of
+ppo_update over buffer.feed_forward_generator bit for bit.
+
+The reference is mirrored as it runs:
+  * MAPPO.cal_value_loss forms the errors in its `use_valuenorm` branch and then overwrites them in the `else` of `if self._use_popart`:
+    with ValueNorm the normaliser is updated, but the targets are the raw returns.  Here too.
+  * HAPPO's loss looks at `use_popart` only (no ValueNorm).
+  * With PopArt, cal_value_loss calls the normaliser's forward twice on the same returns (once per error), so its statistics take each
+    minibatch in twice.  Here too; the entry takes one (mean, var), the statistics after both updates -- what the reference's unclipped
+    error is formed with.  This is a deviation from the reference wherever the clipped error is the selected one: the reference forms
+    it with the statistics BETWEEN the two updates.  The second update moves the debiased mean by
+    (1 - beta) (batch mean - mean) / debiasing term, the mean of squares likewise: nothing on a fresh normaliser (its first update
+    already gives the batch's own moments; every test of this path starts there, so none sees the deviation), about
+    (batch mean - mean) / (n + 2) after n earlier updates while n << 1 / (1 - beta) = 1e5 -- with returns that drift between rollouts
+    this is well above fp32 rounding in the first rollouts of a run -- and 1e-5 (batch mean - mean) on a settled one.  It touches the
+    clipped error's target only, by that shift over sqrt(var), and thereby which of the two losses a row near a tie selects.
+  * Both advantage preparations of train() are the reference's, in torch: returns minus (denormalised) value predictions, normalised by
+    their mean and std over the whole buffer.
+  * `imp_weights`, the last element of ppo_update's tuple, is the [M, 1] tensor of ratios in the reference, of which train() takes
+    .mean(); here it is that mean, a device scalar (its .mean() is itself)."""
+import math
+
+import torch
+import torch.nn as nn
+
+from .loss import marl_ppo_loss
+from .utils.valuenorm import ValueNorm
+
+
+def _rows(x):
+    return x.reshape(-1, *x.shape[2:])
+
+
+def _base(base, x):
+    """MLPBase.forward (agents/algorithms/utils/mlp.py:59-66, 31-35) from the module's attributes."""
+    if getattr(base, "_use_feature_normalization", hasattr(base, "feature_norm")):
+        x = base.feature_norm(x)
+    x = base.mlp.fc1(x)
+    for layer in base.mlp.fc2:
+        x = layer(x)
+    return x
+
+
+def get_grad_norm(params):
+    """agents/utils/util.py:8-15 (get_gard_norm)."""
+    total = 0.0
+    for p in params:
+        if p.grad is not None:
+            total += p.grad.norm() ** 2
+    return math.sqrt(total)
+
+
+class _Trainer:
+    _has_valuenorm = False          # MAPPO reads config["use_valuenorm"]; HAPPO does not
+    _has_factor = False
+
+    def __init__(self, config, policy, device=torch.device("cpu")):
+        self.device = device
+        self.tpdv = dict(dtype=torch.float32, device=device)
+        self.policy = policy
+        self.clip_param = config["clip_param"]
+        self.ppo_epoch = config["ppo_epoch"]
+        self.num_mini_batch = config["num_mini_batch"]
+        self.data_chunk_length = config["data_chunk_length"]
+        self.value_loss_coef = config["value_loss_coef"]
+        self.entropy_coef = config["entropy_coef"]
+        self.max_grad_norm = config["max_grad_norm"]
+        self.huber_delta = config["huber_delta"]
+        self._use_valuenorm = bool(config["use_valuenorm"]) if self._has_valuenorm else False
+        self._use_recurrent_policy = config["use_recurrent_policy"]
+        self._use_naive_recurrent = config["use_naive_recurrent_policy"]
+        self._use_max_grad_norm = config["use_max_grad_norm"]
+        self._use_clipped_value_loss = config["use_clipped_value_loss"]
+        self._use_huber_loss = config["use_huber_loss"]
+        self._use_popart = config["use_popart"]
+        self._use_value_active_masks = config["use_value_active_masks"]
+        self._use_policy_active_masks = config["use_policy_active_masks"]
+        name = type(self).__name__
+        assert not (self._use_popart and self._use_valuenorm), "self._use_popart and self._use_valuenorm can not be set True simultaneously"
+        if self._use_recurrent_policy or self._use_naive_recurrent:
+            raise NotImplementedError("%s: recurrent policies are not covered (use_recurrent_policy / use_naive_recurrent_policy)" % name)
+        head = getattr(getattr(policy.actor, "act", None), "action_out", None)
+        if head is None or not (hasattr(head, "fc_mean") and hasattr(head, "log_std")):
+            raise NotImplementedError("%s: only Box action spaces (ACTLayer.action_out = DiagGaussian) are covered" % name)
+        self.value_normalizer = ValueNorm(1, device=self.device) if (self._use_popart or self._use_valuenorm) else None
+        self.loss_fn = marl_ppo_loss            # (a benchmark swaps in marl_ppo_loss_torch)
+
+    # -- one update -------------------------------------------------------------------------------------------------------------
+    def _update(self, share_obs, obs, returns_rows, fields, indices, update_actor):
+        actor, critic = self.policy.actor, self.policy.critic
+        head = actor.act.action_out
+        values = critic.v_out(_base(critic.base, share_obs))
+        if update_actor:
+            mu = head.fc_mean(_base(actor.base, obs))
+            std = torch.sigmoid(head.log_std / head.std_x_coef) * head.std_y_coef
+        else:
+            with torch.no_grad():
+                mu = head.fc_mean(_base(actor.base, obs))
+                std = torch.sigmoid(head.log_std / head.std_x_coef) * head.std_y_coef
+        norm = (None, None)
+        if self._use_valuenorm:
+            self.value_normalizer.update(returns_rows)                 # ... and the targets stay raw (module docstring)
+        if self._use_popart:
+            self.value_normalizer.update(returns_rows)
+            self.value_normalizer.update(returns_rows)
+            norm = self.value_normalizer.running_mean_var()
+        objective, info = self.loss_fn(mu, std, values, *fields, clip_param=self.clip_param, value_loss_coef=self.value_loss_coef,
+                                       entropy_coef=self.entropy_coef, huber_delta=self.huber_delta, use_huber_loss=self._use_huber_loss,
+                                       use_clipped_value_loss=self._use_clipped_value_loss, use_policy_active_masks=self._use_policy_active_masks,
+                                       use_value_active_masks=self._use_value_active_masks, norm_mean=norm[0], norm_var=norm[1], indices=indices)
+        self.policy.actor_optimizer.zero_grad()
+        self.policy.critic_optimizer.zero_grad()
+        objective.backward()
+        if self._use_max_grad_norm:
+            actor_grad_norm = nn.utils.clip_grad_norm_(actor.parameters(), self.max_grad_norm)
+            critic_grad_norm = nn.utils.clip_grad_norm_(critic.parameters(), self.max_grad_norm)
+        else:
+            actor_grad_norm = get_grad_norm(actor.parameters())
+            critic_grad_norm = get_grad_norm(critic.parameters())
+        self.policy.actor_optimizer.step()
+        self.policy.critic_optimizer.step()
+        return info["value_loss"], critic_grad_norm, info["policy_loss"], info["dist_entropy"], actor_grad_norm, info["ratio"]
+
+    def ppo_update(self, sample, update_actor=True):
+        """One update from the generators' gathered tuple; returns (value_loss, critic_grad_norm, policy_loss, dist_entropy,
+        actor_grad_norm, imp_weights) -- imp_weights: the mean ratio (module docstring)."""
+        share_obs, obs, _, _, actions, value_preds, returns, _, active_masks, old_logp, adv = sample[:11]
+        cast = lambda x: torch.as_tensor(x).to(**self.tpdv)
+        factor = cast(sample[12]) if self._has_factor else None
+        fields = (cast(actions), cast(old_logp), cast(adv), cast(value_preds), cast(returns), cast(active_masks), factor)
+        return self._update(cast(share_obs), cast(obs), fields[4], fields, None, update_actor)
+
+    def train(self, buffer, update_actor=True):
+        """The reference's train(): ppo_epoch passes over num_mini_batch random minibatches of the buffer; returns train_info."""
+        if self.value_normalizer is not None:
+            advantages = buffer.returns[:-1] - self.value_normalizer.denormalize(buffer.value_preds[:-1])
+        else:
+            advantages = buffer.returns[:-1] - buffer.value_preds[:-1]
+        advantages_copy = advantages.clone()
+        mean_advantages = torch.mean(advantages_copy)
+        std_advantages = torch.std(advantages_copy)
+        advantages = ((advantages - mean_advantages) / (std_advantages + 1e-5)).contiguous()
+        train_info = {k: 0 for k in ("value_loss", "policy_loss", "dist_entropy", "actor_grad_norm", "critic_grad_norm", "ratio")}
+        T, N = buffer.rewards.shape[0:2]
+        batch = T * N
+        assert batch >= self.num_mini_batch, ("PPO requires the number of processes (%d) * number of steps (%d) = %d to be greater than or "
+                                              "equal to the number of PPO mini batches (%d)." % (N, T, batch, self.num_mini_batch))
+        mini_batch_size = batch // self.num_mini_batch
+        fields = (buffer.actions, buffer.action_log_probs, advantages, buffer.value_preds, buffer.returns, buffer.active_masks,
+                  buffer.factor if self._has_factor else None)
+        share_rows, obs_rows, return_rows = _rows(buffer.share_obs[:-1]), _rows(buffer.obs[:-1]), _rows(buffer.returns[:-1])
+        for _ in range(self.ppo_epoch):
+            perm = torch.randperm(batch)                               # feed_forward_generator's draw and slices (generators.py)
+            for b in range(self.num_mini_batch):
+                idx = perm[b * mini_batch_size:(b + 1) * mini_batch_size].to(buffer.rewards.device)
+                value_loss, critic_grad_norm, policy_loss, dist_entropy, actor_grad_norm, imp_weights = self._update(
+                    share_rows[idx], obs_rows[idx], return_rows[idx], fields, idx, update_actor)
+                train_info["value_loss"] += value_loss.item()
+                train_info["policy_loss"] += policy_loss.item()
+                train_info["dist_entropy"] += dist_entropy.item()
+                train_info["actor_grad_norm"] += actor_grad_norm
+                train_info["critic_grad_norm"] += critic_grad_norm
+                train_info["ratio"] += imp_weights.mean()
+        num_updates = self.ppo_epoch * self.num_mini_batch
+        for k in train_info.keys():
+            train_info[k] /= num_updates
+        return train_info
+
+    def prep_training(self):
+        self.policy.actor.train()
+        self.policy.critic.train()
+
+    def prep_rollout(self):
+        self.policy.actor.eval()
+        self.policy.critic.eval()
+
+
+class MAPPO(_Trainer):
+    """agents/algorithms/marl/mappo_trainer.py: MAPPO (module docstring)."""
+    _has_valuenorm = True
+
+
+class HAPPO(_Trainer):
+    """agents/algorithms/marl/happo_trainer.py: HAPPO: the surrogate carries the buffer's factor; PopArt or no normaliser."""
+    _has_factor = True

@@ -19,6 +19,7 @@
 #include "../mms_host.h"
 #include "../rollout_lane.h"
 #include "../ppo_loss_lane.h"
+#include "../marl_loss_lane.h"
 #include "../q_lane.h"
 #include "../sac_lane.h"
 #include "lane_step.h"
@@ -1073,5 +1074,81 @@ MMS_API int mms_ppo_loss(int device, int64_t M, int32_t A, const float* mu, cons
     mms::ppo_finish_scalars(tot[0], tot[1], tot[2], entropy, M, value_coef, entropy_coef, out);
     if (grads)
         for (int j = 0; j < A; j++) dlog_std[j] = mms::ppo_finish_dlog_std(tot[3 + j], entropy_coef);
+    return 0;
+}
+
+// ---- the MAPPO / HAPPO update's loss head (include/mms.h: mms_marl_ppo_loss) over ../marl_loss_lane.h -------------------------------
+// Chunks and sums as mms_ppo_loss above: a row's sums in double over ascending columns, a chunk's partials in double over ascending
+// rows, the chunks added in ascending order and rounded once; the mask sum in double over ascending rows.  No workspace.
+MMS_API int mms_marl_ppo_loss(int device, int64_t M, int32_t A, const float* mu, const float* std, const float* value, const int64_t* indices,
+                              const mms_marl_loss_fields* fields, float clip, float value_loss_coef, float entropy_coef, float huber_delta,
+                              int32_t use_huber, int32_t clipped_value, int32_t policy_masks, int32_t value_masks, int32_t use_norm,
+                              const float* norm_mean, const float* norm_var, float* out, float* dmu, float* dstd, float* dvalue, float* row_logp,
+                              void* workspace, int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_marl_ppo_loss(M, A, mu, std, value, fields, policy_masks, value_masks, use_norm, norm_mean, norm_var, out, dmu, dstd, dvalue,
+                                    workspace, ws_bytes, 0)))
+        return 1;
+    if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query
+    const mms_marl_loss_fields f = *fields;
+    const bool grads = dmu != nullptr, pm = policy_masks != 0, vm = value_masks != 0;
+    int64_t chunk = (M + 1023) / 1024;
+    chunk = chunk < 256 ? 256 : chunk;
+    const int64_t nchunks = (M + chunk - 1) / chunk;
+    const double inv_m = 1.0 / (double)M;
+    mms::MarlCol col[MMS_MARL_LOSS_MAX_A];
+    double entropy = 0.0;
+    for (int j = 0; j < A; j++) {
+        col[j] = mms::marl_col_consts(std[j]);
+        entropy += mms::marl_entropy_term(std[j]);
+    }
+    mms::MarlScalars sc;
+    sc.clip = clip; sc.value_coef = value_loss_coef; sc.delta = huber_delta;
+    sc.huber = use_huber != 0; sc.clipped_value = clipped_value != 0; sc.use_norm = use_norm != 0;
+    sc.norm_mean = use_norm ? (double)norm_mean[0] : 0.0;
+    sc.norm_inv_sd = use_norm ? 1.0 / sqrt((double)norm_var[0]) : 1.0;
+    double msum = 0.0;
+    if (pm || vm)
+        for (int64_t row = 0; row < M; row++) msum += (double)f.active_masks.base[(indices ? indices[row] : row) * f.active_masks.pitch];
+    const double inv_msum = (pm || vm) ? 1.0 / msum : 0.0;
+    std::vector<double> part((size_t)nchunks * (3 + A), 0.0);
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < nchunks; c++) {
+        double* p = part.data() + c * (3 + A);
+        const int64_t end = (c + 1) * chunk < M ? (c + 1) * chunk : M;
+        float d[MMS_MARL_LOSS_MAX_A];
+        for (int64_t row = c * chunk; row < end; row++) {
+            const int64_t src = indices ? indices[row] : row;
+            const float *m = mu + row * A, *a = f.actions.base + src * f.actions.pitch, *ol = f.old_logp.base + src * f.old_logp.pitch;
+            double dlogp = 0.0, logp = 0.0;
+            for (int j = 0; j < A; j++) {
+                const double t = mms::marl_logp_term(a[j], m[j], col[j], d[j]);
+                dlogp += t - (double)ol[j];
+                logp += t;
+            }
+            const float mask = (pm || vm) ? f.active_masks.base[src * f.active_masks.pitch] : 1.0f;
+            const float fac = f.factor.base ? f.factor.base[src * f.factor.pitch] : 1.0f;
+            const mms::MarlRow r = mms::marl_row(dlogp, f.adv.base[src * f.adv.pitch], fac, value[row], f.value_preds.base[src * f.value_preds.pitch],
+                                                 f.returns.base[src * f.returns.pitch], sc, pm ? (double)mask * inv_msum : inv_m, vm ? (double)mask * inv_msum : inv_m);
+            p[0] += pm ? (double)mask * (double)r.surrogate : (double)r.surrogate;
+            p[1] += vm ? (double)mask * (double)r.value_loss : (double)r.value_loss;
+            p[2] += (double)r.ratio;
+            if (row_logp) row_logp[row] = (float)logp;
+            if (grads) {
+                dvalue[row] = r.dvalue;
+                for (int j = 0; j < A; j++) {
+                    dmu[row * A + j] = mms::marl_dmu(r.g, d[j], col[j]);
+                    p[3 + j] += mms::marl_dstd_term(r.g, d[j], col[j]);
+                }
+            }
+        }
+    }
+    std::vector<double> tot(3 + A, 0.0);
+    for (int64_t c = 0; c < nchunks; c++)
+        for (int q = 0; q < 3 + A; q++) tot[q] += part[c * (3 + A) + q];
+    const double ent_scale = pm ? 1.0 : 1.0 / (double)A;
+    mms::marl_finish_scalars(tot[0], tot[1], tot[2], entropy, pm ? msum : (double)M, vm ? msum : (double)M, ent_scale, M, value_loss_coef, entropy_coef, out);
+    if (grads)
+        for (int j = 0; j < A; j++) dstd[j] = mms::marl_finish_dstd(tot[3 + j], std[j], entropy_coef, ent_scale);
     return 0;
 }

@@ -29,6 +29,9 @@ hipError_t launch_q_heads_backup(int, int64_t, int, const float* const*, const f
 int64_t ppo_loss_ws_bytes(int64_t, int);
 hipError_t launch_ppo_loss(int64_t, int, const float*, const float*, const float*, const int64_t*, const float*, const float*, const float*, const float*,
                            const float*, const float*, const float*, float, float, float, int, float*, float*, float*, float*, void*, hipStream_t);
+int64_t marl_loss_ws_bytes(int64_t, int);
+hipError_t launch_marl_ppo_loss(int64_t, int, const float*, const float*, const float*, const int64_t*, const mms_marl_loss_fields&, float, float, float,
+                                float, int, int, int, int, int, const float*, const float*, float*, float*, float*, float*, float*, void*, hipStream_t);
 struct MlpPlan;
 }  // namespace mms
 
@@ -675,6 +678,27 @@ __attribute__((visibility("default"))) int mms_ppo_loss(int device, int64_t M, i
     if (!workspace) { *ws_bytes = need; return 0; }                // the size query
     MMS_FREE(mms::launch_ppo_loss(M, A, mu, log_std, value, indices, actions, old_logp, adv, returns, target_values, old_mu, old_sigma, clip, value_coef,
                                   entropy_coef, clipped_value, out, dmu, dlog_std, dvalue, workspace, (hipStream_t)s));
+    return 0;
+}
+
+// ---- the MAPPO / HAPPO update's loss head (marl_loss_kernels.hip) -----------------------------------------------------------------
+
+__attribute__((visibility("default"))) int mms_marl_ppo_loss(int device, int64_t M, int32_t A, const float* mu, const float* std, const float* value,
+                                                             const int64_t* indices, const mms_marl_loss_fields* fields, float clip,
+                                                             float value_loss_coef, float entropy_coef, float huber_delta, int32_t use_huber,
+                                                             int32_t clipped_value, int32_t policy_masks, int32_t value_masks, int32_t use_norm,
+                                                             const float* norm_mean, const float* norm_var, float* out, float* dmu, float* dstd,
+                                                             float* dvalue, float* row_logp, void* workspace, int64_t* ws_bytes, void* s) {
+    MMS_DEV(device)
+    const bool shapes = M >= 1 && M <= 0x7fffffff && A >= 1 && A <= MMS_MARL_LOSS_MAX_A;
+    const int64_t need = shapes ? mms::marl_loss_ws_bytes(M, A) : 0;
+    if (refused(check_marl_ppo_loss(M, A, mu, std, value, fields, policy_masks, value_masks, use_norm, norm_mean, norm_var, out, dmu, dstd, dvalue,
+                                    workspace, ws_bytes, need)))
+        return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }                // the size query
+    MMS_FREE(mms::launch_marl_ppo_loss(M, A, mu, std, value, indices, *fields, clip, value_loss_coef, entropy_coef, huber_delta, use_huber, clipped_value,
+                                       policy_masks, value_masks, use_norm, norm_mean, norm_var, out, dmu, dstd, dvalue, row_logp, workspace,
+                                       (hipStream_t)s));
     return 0;
 }
 

@@ -380,6 +380,29 @@ static inline std::string check_ppo_loss(int64_t M, int32_t A, const float* mu, 
     return {};
 }
 
+// mms_marl_ppo_loss: as check_ppo_loss, with the stored fields' pitches and what each flag requires.
+static inline std::string check_marl_ppo_loss(int64_t M, int32_t A, const float* mu, const float* std, const float* value, const mms_marl_loss_fields* f,
+                                              int32_t policy_masks, int32_t value_masks, int32_t use_norm, const float* norm_mean,
+                                              const float* norm_var, const float* out, const float* dmu, const float* dstd, const float* dvalue,
+                                              const void* workspace, const int64_t* ws_bytes, int64_t need) {
+    if (!ws_bytes) return "mms_marl_ppo_loss: ws_bytes required";
+    if (M < 1 || M > 0x7fffffff) return "mms_marl_ppo_loss: M must be in 1..2147483647";
+    if (A < 1 || A > MMS_MARL_LOSS_MAX_A) return "mms_marl_ppo_loss: A must be in 1.." + std::to_string(MMS_MARL_LOSS_MAX_A);
+    if (!workspace) return {};
+    if (!mu || !std || !value || !f || !out || !f->actions.base || !f->old_logp.base || !f->adv.base || !f->value_preds.base || !f->returns.base)
+        return "mms_marl_ppo_loss: null pointer (mu, std, value, fields, its actions, old_logp, adv, value_preds and returns, and out are required)";
+    if ((policy_masks || value_masks) && !f->active_masks.base) return "mms_marl_ppo_loss: a mask flag is on but active_masks is NULL";
+    if (use_norm && (!norm_mean || !norm_var)) return "mms_marl_ppo_loss: use_norm needs norm_mean and norm_var";
+    if (f->actions.pitch < A || f->old_logp.pitch < A) return "mms_marl_ppo_loss: the pitch of actions and old_logp must be at least A";
+    if (f->adv.pitch < 1 || f->value_preds.pitch < 1 || f->returns.pitch < 1 || (f->active_masks.base && f->active_masks.pitch < 1) ||
+        (f->factor.base && f->factor.pitch < 1))
+        return "mms_marl_ppo_loss: the pitch of adv, value_preds, returns, active_masks and factor must be at least 1";
+    if ((dmu || dstd || dvalue) && !(dmu && dstd && dvalue)) return "mms_marl_ppo_loss: dmu, dstd and dvalue go together (all three, or all NULL: the terms only)";
+    if (*ws_bytes < need) return "mms_marl_ppo_loss: workspace too small (" + std::to_string(*ws_bytes) + " bytes, needs " + std::to_string(need) + ")";
+    if (addr(workspace) & 255) return "mms_marl_ppo_loss: workspace must be 256-byte aligned";
+    return {};
+}
+
 static inline std::string check_linear2_act(int64_t M, int32_t N, int32_t K, const float* x0, const float* w0, const float* b0, const float* y0,
                                             const float* x1, const float* w1, const float* b1, const float* y1, int32_t act) {
     if (!x0 || !w0 || !b0 || !y0 || M < 0 || M > 0x7fffffff || N <= 0 || K <= 0 || (K % 4) != 0 || act < 0 || act > 3)

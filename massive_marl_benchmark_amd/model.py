@@ -83,6 +83,17 @@ class MmsPolicyHead(ctypes.Structure):
                 ("weight_tiles", ctypes.c_void_p)]
 
 
+class MmsRows(ctypes.Structure):
+    """struct mms_rows (include/mms.h): a stored field read in place, row r at base + r * pitch floats."""
+    _fields_ = [("base", ctypes.c_void_p), ("pitch", ctypes.c_int64)]
+
+
+class MmsMarlLossFields(ctypes.Structure):
+    """struct mms_marl_loss_fields (include/mms.h): the stored operands of mms_marl_ppo_loss."""
+    NAMES = ("actions", "old_logp", "adv", "value_preds", "returns", "active_masks", "factor")
+    _fields_ = [(n, MmsRows) for n in NAMES]
+
+
 # ----------------------------------------------------------------------------------------------
 # ant description (restated from nv_ant.xml; see module docstring)
 # ----------------------------------------------------------------------------------------------
