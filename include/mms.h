@@ -40,6 +40,8 @@
  *     (algorithms/rl/sac/module.py:23-61; sac.py:166, 374-376)
  *   MLPQFunction last layer + min + Bellman backup (Q target)           mms_q_heads_backup
  *     (rl/sac/sac.py:379-382; td3/td3.py:370-373; ddpg/ddpg.py:368-369)
+ *   MLPQFunction's torch.cat([obs, act]) in front of the two-plane      mms_split_planes16_cat
+ *     fp16 layers (rl/{ddpg,td3,sac}/module.py, layers="f16x2")
  *   TRPO actor backward: torch.autograd.grad of the surrogate loss      mms_mlp_grad
  *     (algorithms/rl/trpo/trpo.py:290) and the create_graph=True
  *     gradient of the KL (:427)
@@ -490,6 +492,18 @@ int mms_linear_group_act_split(int device, int32_t groups, int64_t M, int32_t N,
 int mms_split_planes16_group(int device, int32_t groups, int64_t rows, int32_t K, int32_t x_pitch, const float* const* x, void* const* planes,
                              float* const* scale, float* const* inv, int32_t nchains, int32_t L, const float* const* chain,
                              float* const* chain_scale, float* const* chain_inv, float* const* stat, float eps, void* hip_stream);
+
+/* mms_split_planes16_group with groups = 1 and stat = NULL on the row-wise concatenation [x0[r, 0:K0] | x1[r, 0:K1]], K = K0 + K1, which
+ * is never written: the input of an off-policy critic, cat(obs, act) (algorithms/rl/{ddpg,td3,sac}/module.py), read where its halves
+ * lie -- a replay ring's observation rows and the actor's freshly written actions.  planes (H32 of [rows, K], zero columns past K),
+ * scale and inv (f32 [rows], either may be NULL), chain_scale and chain_inv (f32 [nchains, L, rows]) are bit-identical to that call on
+ * the materialised concatenation: the row's bound is the largest magnitude over both sources, an all-zero row keeps scale 1.
+ * pitch0 / pitch1: floats between consecutive rows of x0 / x1 (0 = the source's own K, otherwise >= it: a row may be a slice of a wider
+ * block).  K0, K1 >= 1; sources 4-byte aligned (a source whose rows are not all 16-byte aligned takes scalar loads), planes 16-byte
+ * aligned.  rows == 0 succeeds and writes nothing.  Bad arguments return non-zero with mms_last_error(NULL) and write nothing. */
+int mms_split_planes16_cat(int device, int64_t rows, int32_t K0, int32_t pitch0, const float* x0, int32_t K1, int32_t pitch1, const float* x1,
+                           void* planes, float* scale, float* inv, int32_t nchains, int32_t L, const float* chain, float* chain_scale,
+                           float* chain_inv, void* hip_stream);
 
 /* The weights' side of the same layers, refreshed ON THE DEVICE after every parameter update (no host synchronisation, every output at
  * the caller's address: the two calls may sit at the head of a captured hipGraph of a rollout, so that a replay after an optimizer step

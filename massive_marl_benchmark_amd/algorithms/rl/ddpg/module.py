@@ -14,7 +14,19 @@ and the last Linear(H, 1) through `mms_q_heads_backup` (`fused_q_forward`).  `ML
 whole target: both critics of TD3 / SAC per launch, and the min and the Bellman backup inside the last one (`fused_q_backup`).
 Wherever a gradient is wanted (the online critics of compute_loss_q, compute_loss_pi), on the CPU, or with shapes the kernels do
 not take, the critics are the plain torch modules.  `fused_q=False` in the constructor means torch always.
+
+`layers="f16x2"` (constructor keyword of MLPActor, MLPQFunction and MLPActorCritic; the default is "fp32", which is everything above,
+launch for launch and bit for bit) moves the hidden Linear + activation pairs of those fused paths from the exact-fp32 MFMA kernel to
+the two-plane fp16 kernel the PPO modules use, `mms_linear_group_act_split16` (`split16_hidden`).  What it trades, in the words of
+include/mms.h: "x s = hi + lo 2^-11 with s a power of two per ROW ... the operand is kept to 2^-22 |x| (worst case; 4e-8 rms) instead
+of exactly", relative to the row's bound, and the product is three f16 MFMA products with fp32 accumulation instead of fp32 ones.  The
+critics' cat(obs, act) is then never written: `mms_split_planes16_cat` reads the two halves where they lie.  The weights' planes are
+rebuilt from the parameters on EVERY call (two launches), so an optimizer step or a polyak update between two calls -- or between two
+replays of a captured graph -- is followed with no validity rule at all.  Shapes the kernel does not take (batch or a hidden width
+not a multiple of 128) run the "fp32" chain and give its bits.  The actor's Linear(H, act_dim) + tanh stays one `mms_linear2_act`
+launch, the critics' Linear(H, 1) stays inside `mms_q_heads_backup`.
 """
+import copy
 import ctypes
 
 import torch
@@ -64,6 +76,150 @@ def fused_mlp_forward(seq, x):
     return h
 
 
+LAYERS = ("fp32", "f16x2")
+_MAX_GROUPS = 32         # include/mms.h: MMS_MAX_GROUPS
+_last_split16 = None     # the launch arguments of a split16_hidden call without a scratch dict: referenced until the next one
+
+
+def _h32_bytes(rows, K):
+    return rows * ((K + 31) // 32) * 128       # include/mms.h: MMS_H32_BYTES
+
+
+class _Split16Owner:
+    """What a module with the `layers` keyword keeps: the setting and a plain dict of split16_hidden's scratch memory.  The dict is
+    no parameter and no buffer (state_dict keys stay the reference's); a deepcopy (actor_critic_targ) and a pickle get an EMPTY one."""
+
+    def _init_layers(self, layers):
+        if layers not in LAYERS:
+            raise ValueError("layers must be one of %s, not %r" % (LAYERS, layers))
+        self.layers = layers
+        self._split16_scratch = {}
+
+    def __deepcopy__(self, memo):
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = {} if k == "_split16_scratch" else copy.deepcopy(v, memo)
+        return new
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state["_split16_scratch"] = {}
+        return state
+
+
+def split16_hidden(nets, x_or_pair, scratch=None):
+    """The hidden Linear + activation pairs of one or two networks of equal shape (`nets`: nn.Sequential prefixes) on two scaled fp16
+    planes per operand; the input is a 2-D fp32 tensor or an (obs, act) pair whose row-wise concatenation the networks take (never
+    written).  Returns the last hidden activations [M, H] f32 per network (fresh tensors), or None -- decided before the first launch
+    -- when anything does not qualify: fp32, dense 16-byte aligned parameters, ELU / ReLU / Tanh / Identity, M > 0 and every hidden
+    width multiples of 128, nothing wanting a gradient.  The library is the input's device's (_lib.for_device): the CPU build runs it too.
+
+    Every call, in order: mms_weight_planes16_group over all hidden matrices of all nets (planes, row scales, row 1-norms),
+    mms_chain_refresh16 with rows = 0 (the bound chain), mms_split_planes16_cat (a pair) or mms_split_planes16_group (one split
+    serves every network; it also leaves each row's hidden scales), then one mms_linear_group_act_split16 per layer for all nets,
+    planes out (out_mode 1) but for the last (f32).  The weights are re-split UNCONDITIONALLY: there is no version counter, address
+    tag or refresh(), so whatever rewrote the parameters since the last call (optimizer.step(), the polyak loop, .data writes) is in
+    this result.  No host synchronisation: after one call that allocated the scratch the sequence is graph-capturable.
+    `scratch`: the owning module's dict; it keeps device scratch memory per (device, M, layer shapes, number of nets) and, until
+    the next call, the ctypes arrays and every tensor the launches read."""
+    global _last_split16
+    nets = [list(n) for n in nets]
+    pair = isinstance(x_or_pair, (tuple, list))
+    xs = list(x_or_pair) if pair else [x_or_pair]
+    G = len(nets)
+    if G not in (1, 2) or len(xs) != (2 if pair else 1) or any(len(m) != len(nets[0]) or len(m) % 2 or len(m) < 2 for m in nets):
+        return None
+    x0 = xs[0]
+    for x in xs:
+        if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or x.device != x0.device or x.shape[0] != x0.shape[0] or x.shape[1] < 1:
+            return None
+        if x.stride(1) != 1 or x.stride(0) < x.shape[1] or x.data_ptr() % 4:
+            return None
+    dev, M = x0.device, x0.shape[0]
+    if dev.type not in ("cuda", "cpu") or M <= 0 or M % 128:
+        return None
+    nl = len(nets[0]) // 2
+    if G * nl > _MAX_GROUPS:
+        return None
+    grad = torch.is_grad_enabled()
+    if grad and any(x.requires_grad for x in xs):
+        return None
+    K_in = sum(x.shape[1] for x in xs)
+    for m in nets:
+        for i in range(nl):
+            lin, fn, lin0, fn0 = m[2 * i], m[2 * i + 1], nets[0][2 * i], nets[0][2 * i + 1]
+            if not isinstance(lin, nn.Linear) or lin.bias is None or type(fn) not in _ACT_CODES or type(fn) is not type(fn0):
+                return None
+            if isinstance(fn, nn.ELU) and fn.alpha != 1.0:
+                return None
+            if not isinstance(lin0, nn.Linear) or (lin.in_features, lin.out_features) != (lin0.in_features, lin0.out_features) or lin.out_features % 128:
+                return None
+            for t in (lin.weight, lin.bias):
+                if t.dtype != torch.float32 or t.device != dev or not _kernel_layout(t) or (grad and t.requires_grad):
+                    return None
+            if lin.in_features != (K_in if i == 0 else m[2 * i - 2].out_features):
+                return None
+    acts = [_ACT_CODES[type(nets[0][2 * i + 1])] for i in range(nl)]
+    lins = [[m[2 * i] for i in range(nl)] for m in nets]
+    shapes = tuple((l.out_features, l.in_features) for l in lins[0])
+    Lh = nl - 1                                           # layers whose output stays in planes: the bound chain's length
+    L, idx, stream = _lib.for_device(dev)
+    key = (str(dev), M, shapes, G)
+    holder = scratch if scratch is not None else {}
+    buf = holder.get(key)
+    if buf is None:
+        f32 = lambda *s: torch.empty(*s, device=dev)
+        u8 = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)
+        buf = {"w": [[(u8(_h32_bytes(N, K)), f32(N), f32(N), f32(N)) for N, K in shapes] for _ in range(G)],     # planes, scale, inv, l1
+               "chain": torch.zeros(G, max(Lh, 1), 2, device=dev),
+               "x": u8(_h32_bytes(M, K_in)), "xs": f32(M), "xi": f32(M), "cs": f32(G, max(Lh, 1), M), "ci": f32(G, max(Lh, 1), M),
+               "h": [[u8(_h32_bytes(M, N)) for N, _ in shapes[:-1]] for _ in range(G)]}
+        holder[key] = buf
+    out = [torch.empty(M, shapes[-1][0], device=dev) for _ in range(G)]
+    vp = ctypes.c_void_p
+    arr = lambda ts: (vp * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+    p = lambda t: vp(t.data_ptr())
+    flat = [(lins[g][i], buf["w"][g][i]) for g in range(G) for i in range(nl)]
+    ws, bs = [l.weight.detach() for l, _ in flat], [[l.bias.detach() for l in lins[g]] for g in range(G)]
+    keep = [xs, ws, bs, out, buf]
+    calls = [(L.mms_weight_planes16_group, (idx, len(flat), (ctypes.c_int64 * len(flat))(*[l.out_features for l, _ in flat]),
+                                            (ctypes.c_int32 * len(flat))(*[l.in_features for l, _ in flat]), arr(ws), arr([b[0] for _, b in flat]),
+                                            arr([b[1] for _, b in flat]), arr([b[2] for _, b in flat]), arr([b[3] for _, b in flat])), "mms_weight_planes16_group")]
+    if Lh:
+        ent = [(g, i) for g in range(G) for i in range(Lh)]
+        calls.append((L.mms_chain_refresh16, (idx, G, Lh, arr([buf["w"][g][i][3] for g, i in ent]), arr([bs[g][i] for g, i in ent]),
+                                              (ctypes.c_int32 * len(ent))(*[shapes[i][0] for _, i in ent]), p(buf["chain"]), 0.0, 0, None, None), "mms_chain_refresh16"))
+    nch = G if Lh else 0
+    if pair:
+        calls.append((L.mms_split_planes16_cat, (idx, M, xs[0].shape[1], xs[0].stride(0), p(xs[0]), xs[1].shape[1], xs[1].stride(0), p(xs[1]), p(buf["x"]), None,
+                                                 p(buf["xi"]), nch, Lh, p(buf["chain"]) if nch else None, p(buf["cs"]) if nch else None,
+                                                 p(buf["ci"]) if nch else None), "mms_split_planes16_cat"))
+    else:
+        calls.append((L.mms_split_planes16_group, (idx, 1, M, K_in, x0.stride(0), arr([x0]), arr([buf["x"]]), arr([buf["xs"]]), arr([buf["xi"]]), nch, Lh,
+                                                   arr([buf["chain"]]) if nch else None, arr([buf["cs"]]) if nch else None, arr([buf["ci"]]) if nch else None,
+                                                   None, 0.0), "mms_split_planes16_group"))
+    cur, cur_inv = [buf["x"]] * G, [buf["xi"]] * G
+    for i, (N, K) in enumerate(shapes):
+        last = i == nl - 1
+        y = out if last else [buf["h"][g][i] for g in range(G)]
+        ysc = None if last else [buf["cs"][g, i] for g in range(G)]
+        calls.append((L.mms_linear_group_act_split16, (idx, G, M, N, K, arr(cur), arr([buf["w"][g][i][0] for g in range(G)]), arr([bs[g][i] for g in range(G)]), arr(y),
+                                                       arr(cur_inv), arr([buf["w"][g][i][2] for g in range(G)]), None if last else arr(ysc), acts[i], 0 if last else 1,
+                                                       None, None, None, None, None, None), "mms_linear_group_act_split16"))
+        if not last:
+            cur, cur_inv = y, [buf["ci"][g, i] for g in range(G)]
+            keep.append((ysc, cur_inv))
+    keep.append(calls)
+    if scratch is not None:
+        scratch["last"] = keep
+    else:
+        _last_split16 = keep
+    for fn, args, what in calls:
+        _lib.check(fn(*args, stream), None, what, L)
+    return out
+
+
 def _q_chain(qs, obs, act):
     """The hidden layers of one or two MLPQFunctions of the same shape on cat(obs, act), both networks per mms_linear2_act launch.
     Returns (hidden activations per network [M, H], the last Linears, leading shape), or None if anything does not qualify --
@@ -93,6 +249,11 @@ def _q_chain(qs, obs, act):
                 return None
     if nets[0][0].in_features != obs.shape[-1] + act.shape[-1]:
         return None
+    if len(nets[0]) > 2 and all(getattr(q, "layers", "fp32") == "f16x2" for q in qs):
+        # the two-plane fp16 layers on (obs, act) where they lie: no cat; None (shapes the kernel does not take): the chain below
+        hs = split16_hidden([m[:-2] for m in nets], (obs.reshape(-1, obs.shape[-1]), act.reshape(-1, act.shape[-1])), getattr(qs[0], "_split16_scratch", None))
+        if hs is not None:
+            return hs, [m[-2] for m in nets], obs.shape[:-1]
     dev = obs.device
     L, idx, stream = _lib.for_device(dev)
     p = lambda t: ctypes.c_void_p(t.data_ptr())
@@ -168,24 +329,32 @@ def fused_q_backup(qs, obs, act, r, d, gamma, alpha=None, logp=None):
     return backup
 
 
-class MLPActor(nn.Module):
-    def __init__(self, obs_dim, act_dim, hidden_sizes, activation, act_limit):
+class MLPActor(_Split16Owner, nn.Module):
+    def __init__(self, obs_dim, act_dim, hidden_sizes, activation, act_limit, layers="fp32"):
         super().__init__()
         self.pi = mlp([obs_dim, *hidden_sizes, act_dim], activation, nn.Tanh)
         self.act_limit = act_limit
+        self._init_layers(layers)          # "f16x2": the hidden pairs through split16_hidden (module docstring)
 
     def forward(self, obs):
-        out = fused_mlp_forward(self.pi, obs)
+        out = None
+        if self.layers == "f16x2" and obs.is_cuda and obs.dim() == 2 and len(self.pi) > 2:
+            hs = split16_hidden([list(self.pi)[:-2]], obs, self._split16_scratch)
+            if hs is not None:             # Linear(H, act_dim) + tanh: act_dim is no multiple of 128, one mms_linear2_act launch
+                out = fused_mlp_forward(self.pi[-2:], hs[0])
+        if out is None:
+            out = fused_mlp_forward(self.pi, obs)
         if out is None:
             out = self.pi(obs)
         return out if self.act_limit == 1.0 else self.act_limit * out       # x 1.0 is exact: one launch less for the ant / helicopter tasks
 
 
-class MLPQFunction(nn.Module):
-    def __init__(self, obs_dim, act_dim, hidden_sizes, activation, fused_q=True):
+class MLPQFunction(_Split16Owner, nn.Module):
+    def __init__(self, obs_dim, act_dim, hidden_sizes, activation, fused_q=True, layers="fp32"):
         super().__init__()
         self.q = mlp([obs_dim + act_dim, *hidden_sizes, 1], activation)
         self.fused_q = bool(fused_q)       # False: torch always
+        self._init_layers(layers)          # "f16x2": the fused paths' hidden pairs through split16_hidden on (obs, act), no cat
 
     def forward(self, obs, act):
         out = fused_q_forward([self], obs, act) if self.fused_q else None
@@ -195,18 +364,21 @@ class MLPQFunction(nn.Module):
 
 
 class MLPActorCritic(nn.Module):
-    def __init__(self, observation_space, action_space, act_noise, device, hidden_sizes=(256, 256), activation=nn.ReLU, fused_q=True):
+    def __init__(self, observation_space, action_space, act_noise, device, hidden_sizes=(256, 256), activation=nn.ReLU, layers="fp32", fused_q=True):
         super().__init__()
         self.fused_q = bool(fused_q)
+        if layers not in LAYERS:
+            raise ValueError("layers must be one of %s, not %r" % (LAYERS, layers))
+        self.layers = layers               # handed down to the actor and the critics ("f16x2": module docstring)
         obs_dim, act_dim = observation_space.shape[0], action_space.shape[0]
         self.act_limit = action_space.high[0]
         self.act_noise = act_noise
         self.device = device
-        self.pi = MLPActor(obs_dim, act_dim, hidden_sizes, activation, self.act_limit)
+        self.pi = MLPActor(obs_dim, act_dim, hidden_sizes, activation, self.act_limit, self.layers)
         self._build_q(obs_dim, act_dim, hidden_sizes, activation)
 
     def _build_q(self, obs_dim, act_dim, hidden_sizes, activation):
-        self.q = MLPQFunction(obs_dim, act_dim, hidden_sizes, activation, self.fused_q)
+        self.q = MLPQFunction(obs_dim, act_dim, hidden_sizes, activation, self.fused_q, self.layers)
 
     def _critics(self):
         return [self.q]

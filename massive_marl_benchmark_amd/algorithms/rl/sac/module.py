@@ -10,6 +10,14 @@ and the head -- mu_layer, log_std_layer, clamp, rsample, the tanh-corrected log-
 is plain torch with the same formulae.  The critics under no_grad run fused as well (`MLPQFunction.forward`, `q_backup`: see
 ddpg.module); `fused_q=False` keeps them on torch.
 
+`layers="f16x2"` (constructor keyword of SquashedGaussianMLPActor, MLPQFunction and MLPActorCritic, which hands it down; default
+"fp32" = everything above, launch for launch and bit for bit): the hidden layers of those fused paths -- `net` in front of
+`mms_sac_heads_act`, the critics' hidden layers in front of `mms_q_heads_backup`, on (obs, act) without the cat -- run on the two-plane
+fp16 kernel through ddpg.module.split16_hidden.  include/mms.h on what that trades: "the operand is kept to 2^-22 |x| (worst case;
+4e-8 rms) instead of exactly", relative to its row's bound.  The weights' planes are rebuilt on every call, so in-place parameter
+updates (optimizer, polyak) are always followed; shapes the kernel does not take run the "fp32" chain.  The heads, the sampling and
+the per-row counters are the same launches either way.
+
 The noise of the fused path is this build's counter-based generator (seed, global row = row_offset + row, per-row draw counter),
 not torch's Philox: sampled actions differ from the reference's draw for the same torch seed, their distribution and
 log-probabilities do not.  The per-row counters are a plain device tensor (not a buffer: state_dict keys stay the reference's),
@@ -26,7 +34,7 @@ import torch
 import torch.nn as nn
 
 from .... import _lib
-from ..ddpg.module import fused_mlp_forward, fused_q_backup, fused_q_forward, mlp
+from ..ddpg.module import LAYERS, _Split16Owner, fused_mlp_forward, fused_q_backup, fused_q_forward, mlp, split16_hidden
 
 LOG_STD_MAX = 2
 LOG_STD_MIN = -20
@@ -38,9 +46,10 @@ def _draw_seed():
     return int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
-class SquashedGaussianMLPActor(nn.Module):
-    def __init__(self, obs_dim, act_dim, hidden_sizes, activation, act_limit, seed=None, row_offset=0):
+class SquashedGaussianMLPActor(_Split16Owner, nn.Module):
+    def __init__(self, obs_dim, act_dim, hidden_sizes, activation, act_limit, seed=None, row_offset=0, layers="fp32"):
         super().__init__()
+        self._init_layers(layers)          # "f16x2": `net` through split16_hidden (module docstring)
         self.net = mlp([obs_dim] + list(hidden_sizes), activation, activation)
         self.mu_layer = nn.Linear(hidden_sizes[-1], act_dim)
         self.log_std_layer = nn.Linear(hidden_sizes[-1], act_dim)
@@ -83,7 +92,13 @@ class SquashedGaussianMLPActor(nn.Module):
     def _fused(self, obs, deterministic, with_logprob, epsilon):
         """The forward through mms_linear2_act + mms_sac_heads_act; None where the hidden layers do not qualify."""
         lead = obs.shape[:-1]
-        hidden = fused_mlp_forward(self.net, obs.reshape(-1, obs.shape[-1]))
+        x = obs.reshape(-1, obs.shape[-1])
+        hidden = None
+        if self.layers == "f16x2":
+            hs = split16_hidden([self.net], x, self._split16_scratch)
+            hidden = None if hs is None else hs[0]
+        if hidden is None:
+            hidden = fused_mlp_forward(self.net, x)
         if hidden is None:
             return None
         N, A = hidden.shape[0], self.mu_layer.out_features
@@ -127,11 +142,12 @@ class SquashedGaussianMLPActor(nn.Module):
         return self.torch_forward(obs, deterministic, with_logprob, epsilon)
 
 
-class MLPQFunction(nn.Module):
-    def __init__(self, obs_dim, act_dim, hidden_sizes, activation, fused_q=True):
+class MLPQFunction(_Split16Owner, nn.Module):
+    def __init__(self, obs_dim, act_dim, hidden_sizes, activation, fused_q=True, layers="fp32"):
         super().__init__()
         self.q = mlp([obs_dim + act_dim] + list(hidden_sizes) + [1], activation)
         self.fused_q = bool(fused_q)       # False: torch always
+        self._init_layers(layers)          # "f16x2": the fused paths' hidden layers through split16_hidden on (obs, act), no cat
 
     def forward(self, obs, act):
         out = fused_q_forward([self], obs, act) if self.fused_q else None      # no gradient wanted on the HIP device: ddpg.module
@@ -141,14 +157,17 @@ class MLPQFunction(nn.Module):
 
 
 class MLPActorCritic(nn.Module):
-    def __init__(self, observation_space, action_space, hidden_sizes=(256, 256), activation=nn.ELU, seed=None, row_offset=0, fused_q=True):
+    def __init__(self, observation_space, action_space, hidden_sizes=(256, 256), activation=nn.ELU, seed=None, row_offset=0, layers="fp32", fused_q=True):
         super().__init__()
+        if layers not in LAYERS:
+            raise ValueError("layers must be one of %s, not %r" % (LAYERS, layers))
+        self.layers = layers               # handed down to the actor and both critics
         obs_dim, act_dim = observation_space.shape[0], action_space.shape[0]
         act_limit = action_space.high[0]
-        self.pi = SquashedGaussianMLPActor(obs_dim, act_dim, hidden_sizes, activation, act_limit, seed=0, row_offset=row_offset)
+        self.pi = SquashedGaussianMLPActor(obs_dim, act_dim, hidden_sizes, activation, act_limit, seed=0, row_offset=row_offset, layers=layers)
         self.fused_q = bool(fused_q)
-        self.q1 = MLPQFunction(obs_dim, act_dim, hidden_sizes, activation, self.fused_q)
-        self.q2 = MLPQFunction(obs_dim, act_dim, hidden_sizes, activation, self.fused_q)
+        self.q1 = MLPQFunction(obs_dim, act_dim, hidden_sizes, activation, self.fused_q, layers)
+        self.q2 = MLPQFunction(obs_dim, act_dim, hidden_sizes, activation, self.fused_q, layers)
         self.pi.seed = _draw_seed() if seed is None else int(seed)  # after every layer: initialisation identical to the reference's
 
     def q_backup(self, o2, a2, r, d, gamma, alpha=None, logp=None):

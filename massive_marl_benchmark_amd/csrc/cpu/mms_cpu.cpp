@@ -560,6 +560,48 @@ MMS_API int mms_split_planes16_group(int device, int32_t groups, int64_t rows, i
     return 0;
 }
 
+// The same for rows that are the concatenation of two sources (include/mms.h): split_planes16_rows' statement with element k of a row read
+// from x0 (k < K0) or x1 -- operation by operation what it does on the materialised concatenation, hence the same bits.
+MMS_API int mms_split_planes16_cat(int device, int64_t rows, int32_t K0, int32_t pitch0, const float* x0, int32_t K1, int32_t pitch1, const float* x1,
+                                   void* planes, float* scale, float* inv, int32_t nchains, int32_t L, const float* chain, float* chain_scale,
+                                   float* chain_inv, void*) {
+    if (cpu_only(device)) return 1;
+    if (pitch0 == 0) pitch0 = K0;
+    if (pitch1 == 0) pitch1 = K1;
+    if (refused(check_split_planes16_cat(rows, K0, pitch0, x0, K1, pitch1, x1, planes, nchains, L, chain, chain_scale, chain_inv))) return 1;
+    const int K = K0 + K1, KC = (K + 31) / 32;
+    uint16_t* out = (uint16_t*)planes;
+#pragma omp parallel for schedule(static)
+    for (int64_t r = 0; r < rows; r++) {
+        float big = 0.f;
+        for (int k = 0; k < K0; k++) big = fmaxf(big, fabsf(x0[r * pitch0 + k]));
+        for (int k = 0; k < K1; k++) big = fmaxf(big, fabsf(x1[r * pitch1 + k]));
+        float sc, iv;
+        pow2_scale(big, sc, iv);
+        for (int kc = 0; kc < KC; kc++) {
+            uint16_t* c = out + (r * KC + kc) * 64;
+            for (int j = 0; j < 32; j++) {
+                const int k = kc * 32 + j;
+                const float v = k < K0 ? x0[r * pitch0 + k] : (k < K ? x1[r * pitch1 + (k - K0)] : 0.f);
+                split2(v * sc, c + j, c + 32 + j);
+            }
+        }
+        if (scale) scale[r] = sc;
+        if (inv) inv[r] = iv;
+        for (int c = 0; c < nchains; c++) {
+            float bound = big;
+            for (int l = 0; l < L; l++) {
+                bound = (chain[((size_t)c * L + l) * 2] * bound + chain[((size_t)c * L + l) * 2 + 1]) * 1.001f;
+                float s2, i2;
+                pow2_scale(bound, s2, i2);
+                chain_scale[((size_t)c * L + l) * rows + r] = s2;
+                chain_inv[((size_t)c * L + l) * rows + r] = i2;
+            }
+        }
+    }
+    return 0;
+}
+
 // The device-side refresh of the weights' planes and of the bound chain (include/mms.h).  l1 follows the kernel's summation order
 // (split16_planes_kernel: P lanes per row walk the row's 8-element pieces p = lane, lane + P, ...; xor butterfly over the lanes), so
 // that the bound -- and with it every hidden activation's power-of-two scale -- is the same number on both builds.

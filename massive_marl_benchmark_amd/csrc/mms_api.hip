@@ -422,6 +422,23 @@ __attribute__((visibility("default"))) int mms_split_planes16_group(int device, 
     return 0;
 }
 
+// ... of one matrix whose rows are [x0 row | x1 row], read where the two halves lie (a critic's cat(obs, act))
+__attribute__((visibility("default"))) int mms_split_planes16_cat(int device, int64_t rows, int32_t K0, int32_t pitch0, const float* x0, int32_t K1,
+                                                                  int32_t pitch1, const float* x1, void* planes, float* scale, float* inv,
+                                                                  int32_t nchains, int32_t L, const float* chain, float* chain_scale, float* chain_inv,
+                                                                  void* s) {
+    MMS_DEV(device)
+    if (pitch0 == 0) pitch0 = K0;
+    if (pitch1 == 0) pitch1 = K1;
+    if (refused(check_split_planes16_cat(rows, K0, pitch0, x0, K1, pitch1, x1, planes, nchains, L, chain, chain_scale, chain_inv))) return 1;
+    mms::Split16CatArgs a = {};
+    a.x0 = x0; a.x1 = x1; a.planes = planes; a.scale = scale; a.inv = inv;
+    if (nchains > 0) { a.chain = chain; a.chain_scale = chain_scale; a.chain_inv = chain_inv; }
+    a.rows = rows; a.K0 = K0; a.pitch0 = pitch0; a.K1 = K1; a.pitch1 = pitch1; a.nchains = nchains; a.L = nchains > 0 ? L : 0;
+    MMS_FREE(mms::launch_split16_planes_cat(a, (hipStream_t)s));
+    return 0;
+}
+
 // The weights' side of the split16 layers, refreshed on the device after every parameter update: planes, row scales and row 1-norms of
 // `groups` weight matrices of ANY shapes in one launch ...
 __attribute__((visibility("default"))) int mms_weight_planes16_group(int device, int32_t groups, const int64_t* N, const int32_t* K, const float* const* w,

@@ -472,6 +472,18 @@ static inline std::string check_split_planes16_group(int32_t groups, int64_t row
     return {};
 }
 
+// (pitch0 / pitch1 as the entry resolved them: 0 has become the source's own K)
+static inline std::string check_split_planes16_cat(int64_t rows, int32_t K0, int32_t pitch0, const float* x0, int32_t K1, int32_t pitch1, const float* x1,
+                                                   const void* planes, int32_t nchains, int32_t L, const float* chain, const float* chain_scale,
+                                                   const float* chain_inv) {
+    if (rows < 0 || K0 < 1 || K1 < 1 || (int64_t)K0 + K1 > 0x7fffffe0 || pitch0 < K0 || pitch1 < K1 || nchains < 0 || L < 0 ||
+        (nchains > 0 && (L < 1 || !chain || !chain_scale || !chain_inv)))
+        return "mms_split_planes16_cat: bad arguments (rows >= 0; K0, K1 >= 1; pitch0 >= K0, pitch1 >= K1; nchains > 0 needs L >= 1, chain, chain_scale, chain_inv)";
+    if (!x0 || !x1 || !planes || (addr(planes) & 15) != 0 || ((addr(x0) | addr(x1)) & 3) != 0)
+        return "mms_split_planes16_cat: null or misaligned pointer (x0, x1 4-byte aligned, planes 16-byte aligned)";
+    return {};
+}
+
 static inline std::string check_weight_planes16_group(int32_t groups, const int64_t* N, const int32_t* K, const float* const* w, void* const* planes,
                                                       float* const* scale, float* const* inv) {
     std::string bad = check_groups("mms_weight_planes16_group", groups);

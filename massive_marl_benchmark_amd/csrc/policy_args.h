@@ -176,6 +176,22 @@ struct Split16PlanesArgs {
     int K_g[kMaxGroups];
 };
 
+// The same planes, scales and chain scales of ONE matrix whose rows are the concatenation [x0[r, 0:K0] | x1[r, 0:K1]] of two sources
+// (row pitches pitch0 / pitch1 floats), read where they lie (mms_split_planes16_cat: an off-policy critic's cat(obs, act)).
+struct Split16CatArgs {
+    const float* x0;
+    const float* x1;
+    void* planes;
+    float* scale;                           // optional
+    float* inv;                             // optional
+    const float* chain;
+    float* chain_scale;
+    float* chain_inv;
+    int64_t rows;
+    int K0, pitch0, K1, pitch1;
+    int nchains, L;
+};
+
 // The bound chain refreshed on the device (no atomics, no host synchronisation: graph-capturable): entry e = c * L + l of the chain is
 // (max_i l1[e][i], max_i |bias[e][i]|), i < n[e] -- layer l of chain c's (mult, add) pair from the row 1-norms its weight split left
 // (Split16PlanesArgs::l1) and its bias; written to chain[e * 2 + {0, 1}] by block 0.  rows > 0: every block also evaluates the chain's
@@ -224,6 +240,7 @@ struct FoldScalesArgs {
 hipError_t launch_fold_planes16(const FoldPlanesArgs& a, int groups, hipStream_t s);
 hipError_t launch_fold_scales16(const FoldScalesArgs& a, int groups, hipStream_t s);
 hipError_t launch_split16_planes_group(const Split16PlanesArgs& a, int groups, hipStream_t s);
+hipError_t launch_split16_planes_cat(const Split16CatArgs& a, hipStream_t s);
 hipError_t launch_chain_refresh16(const ChainRefreshArgs& a, hipStream_t s);
 hipError_t launch_linear_split16(const Split16LinearArgs& a, int groups, hipStream_t s);
 void set_split16_clock_probe(uint64_t* out, int slots);   // mms_layer_clock_probe

@@ -212,6 +212,103 @@ hipError_t launch_split16_planes_group(const Split16PlanesArgs& a, int groups, h
     return hipGetLastError();
 }
 
+// ---- the same for a row that is the concatenation of two sources: [x0[r, 0:K0] | x1[r, 0:K1]] -> H32 planes of [rows, K0 + K1] --------
+// An off-policy critic's input cat(obs, act), never written (mms_split_planes16_cat).  The lane layout and the two passes of
+// split16_planes_kernel (a sibling, so that kernel's code stays what it is); no statistics, no 1-norm.  An 8-element piece that lies
+// wholly inside one source whose rows are 16-byte aligned (A0 / A1: base address, pitch % 4 and, for the second source, K0 % 4 -- decided
+// by the launcher, uniform for the launch) takes two float4 loads; a piece across the seam or the tail, or of an unaligned source,
+// takes guarded scalar loads.  Same arithmetic per element and the same bound (a max: order-free) as the plain kernel on the
+// materialised concatenation: bit-identical outputs.  No LDS, no atomics.
+template <bool A0, bool A1>
+__global__ void __launch_bounds__(256) split16_cat_kernel(Split16CatArgs a, int KC, int P) {
+    uint8_t* __restrict__ out = reinterpret_cast<uint8_t*>(a.planes);
+    const int lane = threadIdx.x & 63;
+    const int K0 = a.K0, K = a.K0 + a.K1;
+    const int64_t rows = a.rows;
+    const int sub = lane & (P - 1), rpw = 64 / P;
+    const int64_t row_raw = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * rpw + lane / P;
+    const bool live = row_raw < rows;
+    const int64_t row = live ? row_raw : rows - 1;                      // (idle lanes stay in the shuffles, on a valid row)
+    const float* __restrict__ s0 = a.x0 + row * (int64_t)a.pitch0;
+    const float* __restrict__ s1 = a.x1 + row * (int64_t)a.pitch1;
+    const int pieces = KC * 4;                                          // 8-element pieces of the row
+    auto load8 = [&](int p, float* v) {
+        const int k0 = p * 8;
+        const float* q = nullptr;
+        if (A0 && k0 + 8 <= K0) q = s0 + k0;
+        else if (A1 && k0 >= K0 && k0 + 8 <= K) q = s1 + (k0 - K0);
+        if (q) {
+            const float4 q0 = *reinterpret_cast<const float4*>(q), q1 = *reinterpret_cast<const float4*>(q + 4);
+            v[0] = q0.x; v[1] = q0.y; v[2] = q0.z; v[3] = q0.w; v[4] = q1.x; v[5] = q1.y; v[6] = q1.z; v[7] = q1.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const int k = k0 + j;
+                v[j] = k < K0 ? s0[k] : (k < K ? s1[k - K0] : 0.f);
+            }
+        }
+    };
+    float big = 0.f;
+    for (int p = sub; p < pieces; p += P) {
+        float v[8];
+        load8(p, v);
+#pragma unroll
+        for (int j = 0; j < 8; j++) big = fmaxf(big, fabsf(v[j]));
+    }
+    for (int m = P >> 1; m >= 1; m >>= 1) big = fmaxf(big, __shfl_xor(big, m, 64));
+    float scale, inv;
+    pow2_scale(big, scale, inv);
+    for (int p = sub; p < pieces; p += P) {
+        float v[8];
+        load8(p, v);
+        f16x8 hi, lo;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const float t = v[j] * scale;
+            hi[j] = (_Float16)t;
+            lo[j] = (_Float16)((t - (float)hi[j]) * kLoScale);
+        }
+        if (live) {
+            uint8_t* dst = out + (row * KC + (p >> 2)) * (int64_t)kChunk16 + (p & 3) * 16;
+            *reinterpret_cast<f16x8*>(dst) = hi;
+            *reinterpret_cast<f16x8*>(dst + 64) = lo;
+        }
+    }
+    if (sub == 0 && live) {
+        if (a.scale) a.scale[row] = scale;
+        if (a.inv) a.inv[row] = inv;
+    }
+    // the scales of the layers behind this input: one chain per lane of the row
+    if (live)
+        for (int c = sub; c < a.nchains; c += P) {
+            const float* ch = a.chain + (size_t)c * a.L * 2;
+            float bound = big;
+            for (int l = 0; l < a.L; l++) {
+                bound = (ch[2 * l] * bound + ch[2 * l + 1]) * 1.001f;   // (as split16_planes_kernel)
+                float sc, iv;
+                pow2_scale(bound, sc, iv);
+                a.chain_scale[((size_t)c * a.L + l) * rows + row] = sc;
+                a.chain_inv[((size_t)c * a.L + l) * rows + row] = iv;
+            }
+        }
+}
+
+hipError_t launch_split16_planes_cat(const Split16CatArgs& a, hipStream_t s) {
+    if (a.rows == 0) return hipSuccess;
+    const int KC = (a.K0 + a.K1 + 31) / 32;
+    const bool a0 = (a.pitch0 % 4) == 0 && (reinterpret_cast<uintptr_t>(a.x0) & 15) == 0;
+    const bool a1 = (a.pitch1 % 4) == 0 && (a.K0 % 4) == 0 && (reinterpret_cast<uintptr_t>(a.x1) & 15) == 0;
+    int P = 1;
+    while (P < KC * 4 && P < 64) P <<= 1;                               // lanes per row
+    const int64_t rows_per_block = 4 * (64 / P);
+    const dim3 grid((unsigned)((a.rows + rows_per_block - 1) / rows_per_block));
+    if (a0 && a1) hipLaunchKernelGGL((split16_cat_kernel<true, true>), grid, dim3(256), 0, s, a, KC, P);
+    else if (a0) hipLaunchKernelGGL((split16_cat_kernel<true, false>), grid, dim3(256), 0, s, a, KC, P);
+    else if (a1) hipLaunchKernelGGL((split16_cat_kernel<false, true>), grid, dim3(256), 0, s, a, KC, P);
+    else hipLaunchKernelGGL((split16_cat_kernel<false, false>), grid, dim3(256), 0, s, a, KC, P);
+    return hipGetLastError();
+}
+
 // ---- the bound chain, refreshed on the device ----------------------------------------------------------------------------------
 // Entry e = c L + l of the chain = (largest weight-row 1-norm, largest |bias|) of layer l of chain c, from the row norms the weight
 // split left: every block reduces all entries (a few thousand floats: cheaper than a second launch and a dependency), block 0 stores

@@ -16,7 +16,11 @@ lines behind it (sac.py:379-382: both target critics, the min, the Bellman backu
 sac.py gets) and `fused_backup` (actor_critic_targ.q_backup).  `--target-only` skips the timed collection loops (the ring is filled by
 the warm-up steps alone): the run to put under a kernel trace.
 
-    python tools/bench_offpolicy_collect.py [--algo ddpg|sac] [--num-envs 8192] [--steps 512] [--target-only]
+`--layers f16x2` builds the modules with `layers="f16x2"` (the hidden layers of every fused path on the two-plane fp16 kernel,
+ddpg.module.split16_hidden): the collection series and the `fused*` paths of target_pi / target_q then run it, and a copy of the same
+modules set back to "fp32" joins the same alternating rounds as `fused_fp32` / `fused_backup_fp32` -- the A/B inside one process.
+
+    python tools/bench_offpolicy_collect.py [--algo ddpg|sac] [--layers fp32|f16x2] [--num-envs 8192] [--steps 512] [--target-only]
 """
 import argparse
 import json
@@ -39,6 +43,7 @@ def main():
     ap.add_argument("--env-spacing", type=float, default=None,
                     help="override env.envSpacing (0: every env at the origin, the helicopters fly; default: the reference's grid, where every env away "
                          "from the origin resets on every step -- positions and goals are global-frame, multi_ingenuity.py:381-453)")
+    ap.add_argument("--layers", choices=("fp32", "f16x2"), default="fp32", help="the modules' `layers` keyword (hidden layers of the fused paths)")
     ap.add_argument("--target-only", action="store_true", help="--algo sac: only the target_pi / target_q series (no timed collection loop, no graph)")
     args = ap.parse_args()
     import numpy as np
@@ -53,6 +58,7 @@ def main():
     torch.manual_seed(0)
     out = {"task": args.task, "num_envs": N, "replay_size": args.replay_size, "actor": "library" if args.library_actor else "mms_linear2_act",
            "env_spacing": "reference default" if args.env_spacing is None else args.env_spacing}
+    out["layers"] = args.layers
     if args.algo == "sac":
         out = {"algo": "sac", **out, "actor": "library" if args.library_actor else "mms_linear2_act + mms_sac_heads_act", "hidden": [1024, 1024, 1024]}
     from massive_marl_benchmark_amd.model import default_cfg
@@ -65,13 +71,13 @@ def main():
         W, AD = eng.obs_dim, eng.num_actions
         if args.algo == "sac":
             ac = SACActorCritic(spaces.Box(-np.inf * np.ones(W), np.inf * np.ones(W)), spaces.Box(-np.ones(AD), np.ones(AD)),
-                                hidden_sizes=[1024, 1024, 1024]).cuda()                # cfg/sac/config.yaml: hidden_nodes 1024 x 3, ELU
+                                hidden_sizes=[1024, 1024, 1024], layers=args.layers).cuda()                # cfg/sac/config.yaml: hidden_nodes 1024 x 3, ELU
             if args.library_actor:
                 ac.pi.forward = ac.pi.torch_forward
             ac.pi.reserve_counters(8 * N, torch.device("cuda:0"))     # the graph below pins them; pi(o2) later runs on 8 N rows
         else:
             ac = MLPActorCritic(spaces.Box(-np.inf * np.ones(W), np.inf * np.ones(W)), spaces.Box(-np.ones(AD), np.ones(AD)), 0.1, "cuda:0",
-                                hidden_sizes=[256, 256, 256]).cuda()                   # cfg/ddpg/config.yaml: hidden_nodes 256 x 3
+                                hidden_sizes=[256, 256, 256], layers=args.layers).cuda()                   # cfg/ddpg/config.yaml: hidden_nodes 256 x 3
             if args.library_actor:
                 ac.pi.forward = lambda obs, _pi=ac.pi: _pi.act_limit * _pi.pi(obs)
         buf = ReplayBuffer(N, args.replay_size, 64, 8, (W,), (0,), (AD,), "cuda:0")
@@ -146,12 +152,25 @@ def main():
     print(json.dumps(out), flush=True)
 
 
+def with_layers(module, layers):
+    """A deepcopy of `module` with every sub-module's `layers` set (the same parameters' values on the other layer kernel)."""
+    import copy
+    m = copy.deepcopy(module)
+    for sub in m.modules():
+        if hasattr(sub, "layers"):
+            sub.layers = layers
+    return m
+
+
 def time_target_pi(ac, buf, steps):
     """pi(o2) under no_grad with logp on an [8, N, W] gather of the ring (sac.py:374-376), fused and library alternating (5 rounds)."""
     import torch
     pi = ac.pi
     o2 = buf.next_observations[torch.arange(8, device=buf.next_observations.device)]
     paths = {"fused": lambda x: type(pi).forward(pi, x), "library": pi.torch_forward}     # (whatever --library-actor set for the loop)
+    if pi.layers != "fp32":
+        pi32 = with_layers(pi, "fp32")
+        paths["fused_fp32"] = lambda x: type(pi32).forward(pi32, x)
     res = {k: [] for k in paths}
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     reps = max(8, steps // 8)
@@ -172,7 +191,10 @@ def time_target_pi(ac, buf, steps):
     for k, v in res.items():
         out[k + "_ms_per_call"] = float(np.median(v))
         out[k + "_ms_rounds"] = v
+        out[k + "_ms_spread"] = float(max(v) - min(v))
     out["speedup"] = out["library_ms_per_call"] / out["fused_ms_per_call"]
+    if "fused_fp32" in res:
+        out["speedup_over_fused_fp32"] = out["fused_fp32_ms_per_call"] / out["fused_ms_per_call"]
     return out
 
 
@@ -201,6 +223,9 @@ def time_target_q(ac, buf, steps, gamma=0.99, alpha=0.2):
         return f
 
     paths = {"library": four_lines(lib), "fused_separate": four_lines(targ), "fused_backup": lambda: targ.q_backup(o2, a2, r, d, gamma, alpha, logp_a2)}
+    if targ.layers != "fp32":
+        targ32 = with_layers(targ, "fp32")
+        paths["fused_backup_fp32"] = lambda: targ32.q_backup(o2, a2, r, d, gamma, alpha, logp_a2)
     res = {k: [] for k in paths}
     last = {}
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -222,7 +247,7 @@ def time_target_q(ac, buf, steps, gamma=0.99, alpha=0.2):
     scale = float(1 + last["library"].abs().max())
     out = {"shape": list(o2.shape), "rows": M, "hidden": [l.out_features for l in list(targ.q1.q)[:-2:2]], "dones_dtype": str(d.dtype).replace("torch.", ""),
            "calls_per_round": reps, "finite": bool(all(torch.isfinite(v).all() for v in last.values())),
-           "max_diff_vs_library": {k: float((last[k] - last["library"]).abs().max()) / scale for k in ("fused_separate", "fused_backup")},
+           "max_diff_vs_library": {k: float((last[k] - last["library"]).abs().max()) / scale for k in last if k != "library"},
            # what mms_q_heads_backup must move: both hidden activations, r (4) + d (1) + logp (4) in and the backup (4) out per row, the weights once
            "tail_kernel_bytes": 4 * G * M * H + 13 * M + 4 * G * (H + 1)}
     for k, v in res.items():
@@ -231,6 +256,8 @@ def time_target_q(ac, buf, steps, gamma=0.99, alpha=0.2):
         out[k + "_ms_spread"] = float(max(v) - min(v))
     out["speedup_fused_backup"] = out["library_ms_per_call"] / out["fused_backup_ms_per_call"]
     out["speedup_fused_separate"] = out["library_ms_per_call"] / out["fused_separate_ms_per_call"]
+    if "fused_backup_fp32" in res:
+        out["speedup_over_fused_backup_fp32"] = out["fused_backup_fp32_ms_per_call"] / out["fused_backup_ms_per_call"]
     return out
 
 
