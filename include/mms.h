@@ -46,6 +46,8 @@
  *     (algorithms/rl/trpo/trpo.py:290) and the create_graph=True
  *     gradient of the KL (:427)
  *   TRPO double backward of the KL's Hessian-vector product (:431)      mms_mlp_grad_rop
+ *   HATRPO.fisher_vector_product / trpo_update's actor gradient         mms_ln_mlp_grad, mms_ln_mlp_jvp
+ *     (algorithms/marl/hatrpo_trainer.py:170-179, :236)
  *   PPO.update's loss head: KL, clipped surrogate, value loss, entropy  mms_ppo_loss
  *     and their backward (algorithms/rl/ppo/ppo.py:270-302)
  *   MAPPO / HAPPO ppo_update's loss head: surrogate, entropy, PopArt /   mms_marl_ppo_loss
@@ -586,6 +588,51 @@ int mms_mlp_grad(int device, int32_t layers, int64_t M, const int32_t* dims, con
 int mms_mlp_grad_rop(int device, int32_t layers, int64_t M, const int32_t* dims, const float* x, const float* const* h, const float* const* w,
                      const float* const* v, const float* const* c, const float* g, const float* const* d, const float* const* e, float* rmu,
                      float* const* rdw, float* const* rdb, void* workspace, int64_t* ws_bytes, void* hip_stream);
+
+/* ---- HATRPO's Fisher-vector product: J^T g and J v of a LayerNorm-ELU MLP (csrc/ln_mlp_kernels.hip) ------------------------------------
+ * The network is the MARL actor's mean (agents/algorithms/utils/mlp.py:6-66 and fc_mean), L = blocks >= 1 hidden blocks:
+ *   u_0 = LN(x; g_0, t_0)                                    (feature_norm)
+ *   a_l = u_{l-1} W_l^T + b_l, h_l = ELU(a_l), u_l = LN(h_l; g_l, t_l)        l = 1..L
+ *   mu  = u_L W_m^T + b_m
+ * dims[0..L+1]: the input width, the L hidden widths and A.  LN(v; g, t) = g (v - mean) rstd + t with the biased variance and eps
+ * inside the root; one eps serves every level.  Index conventions: ln_g / ln_t [L+1] hold g_l, t_l of level l = 0..L ([dims[l]]);
+ * w [L+1] holds W_1..W_L and W_m at index L (torch's Linear layout, w[l-1] is [dims[l], dims[l-1]]); h [L] holds h_l [M, dims[l]] at
+ * index l-1, the ELU outputs BEFORE their LayerNorm, as the forward left them; x [M, dims[0]].  All f32 and contiguous.  xhat_l, u_l and
+ * ELU's f' = h + 1 (h <= 0) | 1 are re-derived from x and h_l: no a_l, u_l or normalised copy is an input, and the biases are not read.
+ * Row statistics are RECOMPUTED by every call in the two-pass form (mean, then the mean of squared deviations, over the true width);
+ * there is no caller-supplied statistics argument.
+ * The GEMMs run on the split-operand core of the TRPO section (fp32 operands as three bf16 planes, fp32 accumulation); sums of two
+ * products are concatenated along k; u_{l-1} is evaluated by the operand split from h_{l-1}; weight gradients are deterministic
+ * row-split sums, the bias and affine gradients per-block column sums in double added in block order: no atomics, results are
+ * bit-identical run to run.  Rows past M and columns past a width are neither read from caller memory nor written to it.
+ * Limits: 1 <= blocks <= MMS_LN_MLP_MAX_BLOCKS, widths dims[0..L] in 1..MMS_LN_MLP_MAX_WIDTH, A = dims[L+1] in 1..MMS_LN_MLP_MAX_A,
+ * 1 <= M <= 2097024, eps >= 0.
+ * workspace / ws_bytes: mms_mlp_grad's convention (NULL stores the bytes needed and returns 0 -- nothing else is read; 256-byte aligned;
+ * a smaller one is an error).  The CPU build keeps its row statistics there ((L + 1) M 16 bytes, rounded up to 256).  The workspace
+ * needs no initialisation.  Bad arguments return non-zero with mms_last_error(NULL) and write nothing.
+ *
+ * mms_ln_mlp_grad: J^T g for g [M, A] -- the gradient of sum(g . mu) with respect to every parameter but the biases' own trivial part:
+ *   dW_m = g^T u_L, db_m = sum_rows g, du_L = g W_m;  for l = L..0:  dg_l = sum_rows du_l xhat_l, dt_l = sum_rows du_l, q = du_l g_l,
+ *   dh_l = rstd_l (q - mean(q) - xhat_l mean(q xhat_l)), da_l = dh_l f'(h_l), dW_l = da_l^T u_{l-1}, db_l = sum_rows da_l,
+ *   du_{l-1} = da_l W_l  (level 0 ends with dg_0, dt_0: the input has no gradient output).
+ *   dln_g / dln_t [L+1] receive dg_l, dt_l; dw / db [L+1] receive dW_l, db_l at index l-1 and dW_m, db_m at index L. */
+#define MMS_LN_MLP_MAX_BLOCKS 7
+#define MMS_LN_MLP_MAX_WIDTH 4096
+#define MMS_LN_MLP_MAX_A 128
+int mms_ln_mlp_grad(int device, int32_t blocks, int64_t M, const int32_t* dims, float eps, const float* x, const float* const* h,
+                    const float* const* ln_g, const float* const* ln_t, const float* const* w, const float* g, float* const* dln_g,
+                    float* const* dln_t, float* const* dw, float* const* db, void* workspace, int64_t* ws_bytes, void* hip_stream);
+
+/* mms_ln_mlp_jvp: J v, the directional derivative of mu along a direction with one tensor per parameter: vg / vt [L+1] = (G_l, T_l)
+ * shaped like g_l, t_l; vw / vc [L+1] = (V_l, c_l) shaped like W_l, b_l, with (V_m, c_m) at index L:
+ *   Ru_0 = G_0 xhat_0 + T_0;  Ra_l = Ru_{l-1} W_l^T + u_{l-1} V_l^T + c_l, Rh_l = f'(h_l) Ra_l,
+ *   Ru_l = g_l rstd_l (Rh_l - mean(Rh_l) - xhat_l mean(Rh_l xhat_l)) + G_l xhat_l + T_l;  rmu = Ru_L W_m^T + u_L V_m^T + c_m
+ * rmu [M, A].  col_scale [A] (or NULL) multiplies column j of rmu on the way out: with 1 / (M std_j^2) there, a Fisher-vector product
+ * of the Gaussian policy's KL is this call followed by mms_ln_mlp_grad with g = rmu. */
+int mms_ln_mlp_jvp(int device, int32_t blocks, int64_t M, const int32_t* dims, float eps, const float* x, const float* const* h,
+                   const float* const* ln_g, const float* const* ln_t, const float* const* w, const float* const* vg, const float* const* vt,
+                   const float* const* vw, const float* const* vc, const float* col_scale, float* rmu, void* workspace, int64_t* ws_bytes,
+                   void* hip_stream);
 
 /* ---- The PPO update's loss head and its gradients in one call (csrc/ppo_loss_kernels.hip) ------------------------------------------
  * What agents/algorithms/rl/ppo/ppo.py:270-302 evaluates per minibatch behind ActorCritic.evaluate, as seven advanced-index gathers and

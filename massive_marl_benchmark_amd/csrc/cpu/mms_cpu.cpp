@@ -1058,6 +1058,149 @@ MMS_API int mms_mlp_grad_rop(int device, int32_t L, int64_t M, const int32_t* di
     return 0;
 }
 
+// ---- HATRPO's Fisher-vector product (include/mms.h: mms_ln_mlp_grad, mms_ln_mlp_jvp): plain loops ------------------------------------
+// Every sum (row statistics, row means, products, column sums) accumulates in double and rounds once; what passes from one level to the
+// next (da_l, du_l, Ru_l) is stored in float, as the HIP build stores it.  The workspace holds the row statistics in double.
+struct LnLevel {
+    const float* v;      // the level's saved activation
+    const float *g, *t;
+    const double* st;    // [M, 2]
+    int K;
+    double xhat(int64_t m, int k) const { return ((double)v[m * K + k] - st[2 * m]) * st[2 * m + 1]; }
+    double u(int64_t m, int k) const { return (double)g[k] * xhat(m, k) + (double)t[k]; }
+};
+
+static void ln_stats(int64_t M, int K, const float* v, float eps, double* st) {
+#pragma omp parallel for schedule(static)
+    for (int64_t m = 0; m < M; m++) {
+        double s = 0.0, q = 0.0;
+        for (int k = 0; k < K; k++) s += v[m * K + k];
+        const double mean = s / K;
+        for (int k = 0; k < K; k++) q += ((double)v[m * K + k] - mean) * ((double)v[m * K + k] - mean);
+        st[2 * m] = mean;
+        st[2 * m + 1] = 1.0 / sqrt(q / K + (double)eps);
+    }
+}
+
+static LnLevel ln_level(int l, int64_t M, const int32_t* dims, const float* x, const float* const* h, const float* const* ln_g, const float* const* ln_t,
+                        float eps, void* workspace) {
+    double* st = static_cast<double*>(workspace) + (size_t)l * M * 2;
+    const float* v = l == 0 ? x : h[l - 1];
+    ln_stats(M, dims[l], v, eps, st);
+    return LnLevel{v, ln_g[l], ln_t[l], st, dims[l]};
+}
+
+MMS_API int mms_ln_mlp_grad(int device, int32_t L, int64_t M, const int32_t* dims, float eps, const float* x, const float* const* h,
+                            const float* const* ln_g, const float* const* ln_t, const float* const* w, const float* g, float* const* dln_g,
+                            float* const* dln_t, float* const* dw, float* const* db, void* workspace, int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    const int64_t need = check_ln_mlp_shapes("mms_ln_mlp_grad", L, M, dims, ws_bytes).empty() ? ln_mlp_cpu_ws_bytes(L, M) : 0;
+    if (refused(check_ln_mlp_grad(L, M, dims, eps, x, h, ln_g, ln_t, w, g, dln_g, dln_t, dw, db, workspace, ws_bytes, need))) return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }               // the size query
+    std::vector<float> d(g, g + M * dims[L + 1]), du, da;
+    for (int j = L + 1; j >= 1; j--) {
+        const int N = dims[j], K = dims[j - 1];
+        const LnLevel lv = ln_level(j - 1, M, dims, x, h, ln_g, ln_t, eps, workspace);
+#pragma omp parallel for schedule(static)
+        for (int n = 0; n < N; n++)                                // dW_j = d_j^T u_{j-1}
+            for (int k = 0; k < K; k++) {
+                double s = 0.0;
+                for (int64_t m = 0; m < M; m++) s += (double)d[m * N + n] * lv.u(m, k);
+                dw[j - 1][(int64_t)n * K + k] = (float)s;
+            }
+        mlp_colsum(M, N, d.data(), db[j - 1]);
+        du.assign((size_t)M * K, 0.f);
+#pragma omp parallel for schedule(static)
+        for (int64_t m = 0; m < M; m++)                            // du_{j-1} = d_j W_j
+            for (int k = 0; k < K; k++) {
+                double s = 0.0;
+                for (int n = 0; n < N; n++) s += (double)d[m * N + n] * w[j - 1][(int64_t)n * K + k];
+                du[m * K + k] = (float)s;
+            }
+        for (int k = 0; k < K; k++) {
+            double sg = 0.0, st = 0.0;
+            for (int64_t m = 0; m < M; m++) {
+                sg += (double)du[m * K + k] * lv.xhat(m, k);
+                st += (double)du[m * K + k];
+            }
+            dln_g[j - 1][k] = (float)sg;
+            dln_t[j - 1][k] = (float)st;
+        }
+        if (j == 1) break;
+        da.assign((size_t)M * K, 0.f);
+#pragma omp parallel for schedule(static)
+        for (int64_t m = 0; m < M; m++) {
+            double m1 = 0.0, m2 = 0.0;
+            for (int k = 0; k < K; k++) {
+                const double q = (double)du[m * K + k] * lv.g[k];
+                m1 += q;
+                m2 += q * lv.xhat(m, k);
+            }
+            m1 /= K;
+            m2 /= K;
+            for (int k = 0; k < K; k++) {
+                const double q = (double)du[m * K + k] * lv.g[k];
+                da[m * K + k] = (float)(lv.st[2 * m + 1] * (q - m1 - lv.xhat(m, k) * m2) * elu_d1(lv.v[m * K + k]));
+            }
+        }
+        d.swap(da);
+    }
+    return 0;
+}
+
+MMS_API int mms_ln_mlp_jvp(int device, int32_t L, int64_t M, const int32_t* dims, float eps, const float* x, const float* const* h,
+                           const float* const* ln_g, const float* const* ln_t, const float* const* w, const float* const* vg,
+                           const float* const* vt, const float* const* vw, const float* const* vc, const float* col_scale, float* rmu,
+                           void* workspace, int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    const int64_t need = check_ln_mlp_shapes("mms_ln_mlp_jvp", L, M, dims, ws_bytes).empty() ? ln_mlp_cpu_ws_bytes(L, M) : 0;
+    if (refused(check_ln_mlp_jvp(L, M, dims, eps, x, h, ln_g, ln_t, w, vg, vt, vw, vc, rmu, workspace, ws_bytes, need))) return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }               // the size query
+    std::vector<float> ru, ra;
+    for (int l = 0; l <= L + 1; l++) {
+        if (l >= 1) {                                              // Ra_l = Ru_{l-1} W_l^T + u_{l-1} V_l^T + c_l
+            const int N = dims[l], K = dims[l - 1];
+            const LnLevel below{l == 1 ? x : h[l - 2], ln_g[l - 1], ln_t[l - 1], static_cast<double*>(workspace) + (size_t)(l - 1) * M * 2, K};
+            ra.assign((size_t)M * N, 0.f);
+#pragma omp parallel for schedule(static)
+            for (int64_t m = 0; m < M; m++)
+                for (int n = 0; n < N; n++) {
+                    double s = vc[l - 1][n];
+                    for (int k = 0; k < K; k++)
+                        s += (double)ru[m * K + k] * w[l - 1][(int64_t)n * K + k] + below.u(m, k) * vw[l - 1][(int64_t)n * K + k];
+                    ra[m * N + n] = (float)s;
+                }
+        }
+        if (l == L + 1) break;
+        const int K = dims[l];
+        const LnLevel lv = ln_level(l, M, dims, x, h, ln_g, ln_t, eps, workspace);
+        ru.assign((size_t)M * K, 0.f);
+#pragma omp parallel for schedule(static)
+        for (int64_t m = 0; m < M; m++) {
+            double m1 = 0.0, m2 = 0.0;
+            if (l >= 1) {
+                for (int k = 0; k < K; k++) {
+                    const double rh = elu_d1(lv.v[m * K + k]) * ra[m * K + k];
+                    m1 += rh;
+                    m2 += rh * lv.xhat(m, k);
+                }
+                m1 /= K;
+                m2 /= K;
+            }
+            for (int k = 0; k < K; k++) {
+                const double xh = lv.xhat(m, k);
+                double o = (double)vg[l][k] * xh + (double)vt[l][k];
+                if (l >= 1) o += (double)lv.g[k] * lv.st[2 * m + 1] * (elu_d1(lv.v[m * K + k]) * ra[m * K + k] - m1 - xh * m2);
+                ru[m * K + k] = (float)o;
+            }
+        }
+    }
+    const int A = dims[L + 1];
+    for (int64_t m = 0; m < M; m++)
+        for (int j = 0; j < A; j++) rmu[m * A + j] = col_scale ? ra[m * A + j] * col_scale[j] : ra[m * A + j];
+    return 0;
+}
+
 // ---- the PPO update's loss head (include/mms.h: mms_ppo_loss) over ../ppo_loss_lane.h -----------------------------------------------
 // Rows in at most 1024 chunks of at least 256 (OpenMP over chunks): a row's logp and KL term summed in double over ascending columns,
 // a chunk's partials in double over ascending rows, the chunks added in ascending order and rounded once -- the result does not depend

@@ -9,6 +9,7 @@
 #include "policy_args.h"
 #include "step_args.h"
 #include "trpo_plan.h"
+#include "ln_mlp_plan.h"
 
 namespace mms {
 hipError_t launch_step(const StepArgs& a, int task, hipStream_t stream);
@@ -675,6 +676,43 @@ __attribute__((visibility("default"))) int mms_mlp_grad_rop(int device, int32_t 
     const int ws = mlp_workspace("mms_mlp_grad_rop", layers, M, dims, true, workspace, ws_bytes, &P);
     if (ws != 0) return ws == 2 ? 0 : 1;
     MMS_FREE(mms::mlp_grad_rop(P, x, h, w, v, c, g, d, e, rmu, rdw, rdb, static_cast<uint8_t*>(workspace), (hipStream_t)s));
+    return 0;
+}
+
+// ---- HATRPO's Fisher-vector product: J^T g and J v of the LayerNorm-ELU actor (ln_mlp_kernels.hip) ------------------------------------
+
+__attribute__((visibility("default"))) int mms_ln_mlp_grad(int device, int32_t blocks, int64_t M, const int32_t* dims, float eps, const float* x,
+                                                           const float* const* h, const float* const* ln_g, const float* const* ln_t,
+                                                           const float* const* w, const float* g, float* const* dln_g, float* const* dln_t,
+                                                           float* const* dw, float* const* db, void* workspace, int64_t* ws_bytes, void* s) {
+    MMS_DEV(device)
+    mms::LnMlpPlan Q;
+    int64_t need = 0;
+    if (check_ln_mlp_shapes("mms_ln_mlp_grad", blocks, M, dims, ws_bytes).empty()) {
+        if (!mms::ln_mlp_plan(blocks, M, dims, &Q)) return fail(nullptr, "mms_ln_mlp_grad: no plan for these shapes");
+        need = (int64_t)Q.total;
+    }
+    if (refused(check_ln_mlp_grad(blocks, M, dims, eps, x, h, ln_g, ln_t, w, g, dln_g, dln_t, dw, db, workspace, ws_bytes, need))) return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }                // the size query
+    MMS_FREE(mms::ln_mlp_grad(Q, eps, x, h, ln_g, ln_t, w, g, dln_g, dln_t, dw, db, static_cast<uint8_t*>(workspace), (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_ln_mlp_jvp(int device, int32_t blocks, int64_t M, const int32_t* dims, float eps, const float* x,
+                                                          const float* const* h, const float* const* ln_g, const float* const* ln_t,
+                                                          const float* const* w, const float* const* vg, const float* const* vt,
+                                                          const float* const* vw, const float* const* vc, const float* col_scale, float* rmu,
+                                                          void* workspace, int64_t* ws_bytes, void* s) {
+    MMS_DEV(device)
+    mms::LnMlpPlan Q;
+    int64_t need = 0;
+    if (check_ln_mlp_shapes("mms_ln_mlp_jvp", blocks, M, dims, ws_bytes).empty()) {
+        if (!mms::ln_mlp_plan(blocks, M, dims, &Q)) return fail(nullptr, "mms_ln_mlp_jvp: no plan for these shapes");
+        need = (int64_t)Q.total;
+    }
+    if (refused(check_ln_mlp_jvp(blocks, M, dims, eps, x, h, ln_g, ln_t, w, vg, vt, vw, vc, rmu, workspace, ws_bytes, need))) return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }                // the size query
+    MMS_FREE(mms::ln_mlp_jvp(Q, eps, x, h, ln_g, ln_t, w, vg, vt, vw, vc, col_scale, rmu, static_cast<uint8_t*>(workspace), (hipStream_t)s));
     return 0;
 }
 

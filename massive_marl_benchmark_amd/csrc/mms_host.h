@@ -653,3 +653,50 @@ static inline std::string check_mlp_grad_rop(int32_t layers, int64_t M, const in
         return "mms_mlp_grad_rop: null pointer (x, g, rmu, h / d / e[layers-1], w / v / c / rdw / rdb[layers])";
     return {};
 }
+
+// mms_ln_mlp_grad and mms_ln_mlp_jvp: the shapes, then (workspace NULL is the size query: nothing else is read) the operands, then the
+// workspace against `need`, which is each build's own.
+static inline std::string check_ln_mlp_shapes(const char* entry, int32_t blocks, int64_t M, const int32_t* dims, const int64_t* ws_bytes) {
+    bool ok = dims && ws_bytes && blocks >= 1 && blocks <= MMS_LN_MLP_MAX_BLOCKS && M >= 1 && M <= mms::kMlpMaxRows;
+    for (int l = 0; ok && l <= blocks; l++) ok = dims[l] >= 1 && dims[l] <= MMS_LN_MLP_MAX_WIDTH;
+    ok = ok && dims[blocks + 1] >= 1 && dims[blocks + 1] <= MMS_LN_MLP_MAX_A;
+    if (ok) return {};
+    return std::string(entry) + ": bad arguments (1 <= blocks <= " + std::to_string(MMS_LN_MLP_MAX_BLOCKS) + ", 1 <= M <= " + std::to_string(mms::kMlpMaxRows) +
+           ", dims[0..blocks] in 1.." + std::to_string(MMS_LN_MLP_MAX_WIDTH) + ", dims[blocks+1] in 1.." + std::to_string(MMS_LN_MLP_MAX_A) +
+           ", ws_bytes required)";
+}
+
+static inline std::string check_ln_mlp_workspace(const char* entry, const void* workspace, const int64_t* ws_bytes, int64_t need) {
+    if (*ws_bytes < need) return std::string(entry) + ": workspace too small (" + std::to_string(*ws_bytes) + " bytes, needs " + std::to_string(need) + ")";
+    if (addr(workspace) & 255) return std::string(entry) + ": workspace must be 256-byte aligned";
+    return {};
+}
+
+// the CPU build's workspace: the row statistics (mean, rstd) of every level, in double
+static inline int64_t ln_mlp_cpu_ws_bytes(int32_t blocks, int64_t M) { return (((int64_t)(blocks + 1) * M * 2 * 8) + 255) / 256 * 256; }
+
+static inline std::string check_ln_mlp_grad(int32_t blocks, int64_t M, const int32_t* dims, float eps, const float* x, const float* const* h,
+                                            const float* const* ln_g, const float* const* ln_t, const float* const* w, const float* g,
+                                            float* const* dln_g, float* const* dln_t, float* const* dw, float* const* db, const void* workspace,
+                                            const int64_t* ws_bytes, int64_t need) {
+    std::string bad = check_ln_mlp_shapes("mms_ln_mlp_grad", blocks, M, dims, ws_bytes);
+    if (!bad.empty() || !workspace) return bad;
+    if (!(eps >= 0.f)) return "mms_ln_mlp_grad: eps must not be negative";
+    if (!x || !g || !all_set(blocks, h) || !all_set(blocks + 1, ln_g) || !all_set(blocks + 1, ln_t) || !all_set(blocks + 1, w) ||
+        !all_set(blocks + 1, dln_g) || !all_set(blocks + 1, dln_t) || !all_set(blocks + 1, dw) || !all_set(blocks + 1, db))
+        return "mms_ln_mlp_grad: null pointer (x, g, h[blocks], ln_g / ln_t / w / dln_g / dln_t / dw / db[blocks+1])";
+    return check_ln_mlp_workspace("mms_ln_mlp_grad", workspace, ws_bytes, need);
+}
+
+static inline std::string check_ln_mlp_jvp(int32_t blocks, int64_t M, const int32_t* dims, float eps, const float* x, const float* const* h,
+                                           const float* const* ln_g, const float* const* ln_t, const float* const* w, const float* const* vg,
+                                           const float* const* vt, const float* const* vw, const float* const* vc, const float* rmu,
+                                           const void* workspace, const int64_t* ws_bytes, int64_t need) {
+    std::string bad = check_ln_mlp_shapes("mms_ln_mlp_jvp", blocks, M, dims, ws_bytes);
+    if (!bad.empty() || !workspace) return bad;
+    if (!(eps >= 0.f)) return "mms_ln_mlp_jvp: eps must not be negative";
+    if (!x || !rmu || !all_set(blocks, h) || !all_set(blocks + 1, ln_g) || !all_set(blocks + 1, ln_t) || !all_set(blocks + 1, w) ||
+        !all_set(blocks + 1, vg) || !all_set(blocks + 1, vt) || !all_set(blocks + 1, vw) || !all_set(blocks + 1, vc))
+        return "mms_ln_mlp_jvp: null pointer (x, rmu, h[blocks], ln_g / ln_t / w / vg / vt / vw / vc[blocks+1])";
+    return check_ln_mlp_workspace("mms_ln_mlp_jvp", workspace, ws_bytes, need);
+}

@@ -20,11 +20,13 @@
 // weight gradients, run as 2 S groups into the same reduction.  The elementwise factors (. f', the f'' term) are applied by the split
 // kernels while they read the fp32 operand, so the GEMM epilogue stays the plain store.  Every dimension is zero-padded to what the
 // core takes (rows and output columns multiples of 128, k multiples of 32).  Workspace comes from the caller (mlp_plan sizes it).
+// The operand forms and the launchers below are declared in mlp_core.h: ln_mlp_kernels.hip builds its two passes from them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "policy_args.h"
 #include "trpo_plan.h"
+#include "mlp_core.h"
 
 namespace mms {
 
@@ -32,19 +34,9 @@ hipError_t launch_linear_split(const SplitLinearArgs& a, int groups, hipStream_t
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int kChunk = 192;                      // one row's three planes of 32 k
-
-// The fp32 operand of a split, evaluated at (m, k):  op 0: x;  op 1: x . f'(h);  op 2: x . f'(h) + e . f''(h) . r
-struct OperandArgs {
-    const float* x;
-    const float* h;
-    const float* e;
-    const float* r;
-    int ldx, ldh, lde, ldr, op;
-};
-
 __device__ __forceinline__ float operand_at(const OperandArgs& o, int64_t m, int k) {
     float v = o.x[m * o.ldx + k];
+    if (o.op == 3) return (v - o.st[2 * m]) * o.st[2 * m + 1] * o.ga[k] + o.be[k];
     if (o.op >= 1) {
         const float hv = o.h[m * o.ldh + k];
         const float fp = hv > 0.f ? 1.f : hv + 1.f;
@@ -204,13 +196,7 @@ bool mlp_plan(int L, int64_t M, const int32_t* dims, bool rop, MlpPlan* p) {
     return true;
 }
 
-static OperandArgs operand(const float* x, int ldx, int op = 0, const float* h = nullptr, int ldh = 0, const float* e = nullptr, int lde = 0,
-                           const float* r = nullptr, int ldr = 0) {
-    OperandArgs o = {x, h, e, r, ldx, ldh, lde, ldr, op};
-    return o;
-}
-
-static hipError_t psplit(const OperandArgs& o, int64_t rows, int K, int64_t rows_pad, int pitch, int coff, uint8_t* dst, hipStream_t s) {
+hipError_t psplit(const OperandArgs& o, int64_t rows, int K, int64_t rows_pad, int pitch, int coff, uint8_t* dst, hipStream_t s) {
     PlainSplitArgs a = {o, (int)rows, K, (int)rows_pad, (K + 31) / 32, pitch, coff, dst};
     const int64_t threads = rows_pad * a.KC * 4;
     hipLaunchKernelGGL(mlp_split_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a);
@@ -218,16 +204,16 @@ static hipError_t psplit(const OperandArgs& o, int64_t rows, int K, int64_t rows
 }
 
 // A [rows, cols] -> planes of A^T; MC = chunks over A's rows (all parts), MCs per part
-static hipError_t tsplit(const OperandArgs& o, int64_t rows, int cols, int MC, int MCs, int rows_pad, int pitch, int coff, uint8_t* dst,
-                         float* out, int ldo, float* colp, int ldc, hipStream_t s) {
+hipError_t tsplit(const OperandArgs& o, int64_t rows, int cols, int MC, int MCs, int rows_pad, int pitch, int coff, uint8_t* dst,
+                  float* out, int ldo, float* colp, int ldc, hipStream_t s) {
     TransSplitArgs a = {o, (int)rows, cols, MCs, rows_pad, pitch, coff, dst, out, ldo, colp, ldc};
     hipLaunchKernelGGL(mlp_tsplit_kernel, dim3((unsigned)(rows_pad / 64), (unsigned)MC), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 // y_g = x_g w_g^T (+ b), g < groups, operands in planes (groups consecutive in memory at the given strides)
-static hipError_t gemm(int groups, int64_t M, int N, int KC, const uint8_t* x, size_t xs, const uint8_t* w, size_t ws, const float* b, float* y,
-                       size_t ys, hipStream_t s) {
+hipError_t gemm(int groups, int64_t M, int N, int KC, const uint8_t* x, size_t xs, const uint8_t* w, size_t ws, const float* b, float* y,
+                size_t ys, hipStream_t s) {
     SplitLinearArgs a = {};
     for (int g = 0; g < groups; g++) {
         a.x[g] = x + g * xs;
@@ -243,18 +229,21 @@ static hipError_t gemm(int groups, int64_t M, int N, int KC, const uint8_t* x, s
     return launch_linear_split(a, groups, s);
 }
 
-static hipError_t copy2d(const float* src, int64_t rs, int cs, int lds, float* dst, int64_t rd, int cd, int ldd, hipStream_t s) {
+hipError_t copy2d(const float* src, int64_t rs, int cs, int lds, float* dst, int64_t rd, int cd, int ldd, hipStream_t s) {
     const int64_t n = rd * cd;
     hipLaunchKernelGGL(mlp_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, rs, cs, lds, dst, rd, cd, ldd);
     return hipGetLastError();
 }
 
 template <typename Acc>
-static hipError_t reduce(const float* part, int groups, size_t stride, int ldp, int N, int K, float* out, hipStream_t s) {
+hipError_t reduce(const float* part, int groups, size_t stride, int ldp, int N, int K, float* out, hipStream_t s) {
     const int64_t n = (int64_t)N * K;
     hipLaunchKernelGGL(mlp_reduce_kernel<Acc>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, groups, stride, ldp, N, K, out);
     return hipGetLastError();
 }
+
+template hipError_t reduce<float>(const float*, int, size_t, int, int, int, float*, hipStream_t);
+template hipError_t reduce<double>(const float*, int, size_t, int, int, int, float*, hipStream_t);
 
 #define MMS_TRY(call)                                       \
     do {                                                    \
@@ -262,7 +251,7 @@ static hipError_t reduce(const float* part, int groups, size_t stride, int ldp, 
     } while (0)
 
 // dW_l (and db_l) of one layer from the transposed planes already in ta (S parts per product, `prods` products) and tb
-static hipError_t weight_grad(const MlpPlan& P, int l, int prods, uint8_t* ws, float* dw, float* db, hipStream_t s) {
+hipError_t weight_grad(const MlpPlan& P, int l, int prods, uint8_t* ws, float* dw, float* db, hipStream_t s) {
     const int S = P.S[l], MCs = P.MC / S, G = prods * S;
     const size_t xs = (size_t)P.np[l] * MCs * kChunk, wsz = (size_t)P.np[l - 1] * MCs * kChunk, ys = (size_t)P.np[l] * P.np[l - 1];
     float* part = reinterpret_cast<float*>(ws + P.part);
@@ -273,8 +262,8 @@ static hipError_t weight_grad(const MlpPlan& P, int l, int prods, uint8_t* ws, f
 }
 
 // tsplit into product q's S parts of ta / tb for layer l (contraction over the M rows)
-static hipError_t tsplit_rows(const MlpPlan& P, int l_rows, int S, int q, const OperandArgs& o, bool into_a, uint8_t* ws, float* out, int ldo,
-                              bool colsum, hipStream_t s) {
+hipError_t tsplit_rows(const MlpPlan& P, int l_rows, int S, int q, const OperandArgs& o, bool into_a, uint8_t* ws, float* out, int ldo,
+                       bool colsum, hipStream_t s) {
     const int cols = P.n[l_rows], rows_pad = P.np[l_rows], MCs = P.MC / S;
     uint8_t* dst = ws + (into_a ? P.ta : P.tb) + (size_t)q * S * rows_pad * MCs * kChunk;
     return tsplit(o, P.M, cols, P.MC, MCs, rows_pad, MCs, 0, dst, out, ldo, colsum ? reinterpret_cast<float*>(ws + P.colp) : nullptr, rows_pad, s);
