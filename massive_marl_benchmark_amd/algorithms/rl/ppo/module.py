@@ -514,6 +514,8 @@ class ActorCritic(nn.Module):
         if self._split_applies(M, a_lin[:-1]) and ha.data_ptr() % 16 == 0 and hc.data_ptr() % 16 == 0:
             out = self._split_hidden([a_lin[:-1], c_lin[:-1]], [ha, hc], "act", planes)
             return out[0], out[1]
+        # (the split path checks for itself; here the fused head's tiled copy of the actor's last layer is what has to follow the parameters)
+        self._ensure_fresh()
         # activations of the hidden layers: allocated once per (batch, device) and reused -- the eager path would otherwise take an
         # allocator round trip per layer and call
         key = (M, str(dev))

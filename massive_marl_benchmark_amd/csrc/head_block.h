@@ -51,6 +51,65 @@ __device__ __forceinline__ void ppo_sample_row(const float* mean_row, const floa
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// Four terms of the critic's dot product, contracted explicitly (y's product first, then x, z, w folded in): the expression is compiled
+// in two places (the head's own waves, the staging waves of the step kernel's prologue) and must round the same way in both.  The sum
+// over k around it (`part += ppo_dot4(...)`, `part + ppo_dot4(...)`) stays a plain addition in both places only because the kernels are
+// built with -fno-associative-math (csrc/Makefile: KERNEL_FLAGS); with reassociation allowed the two sites could be folded differently.
+__device__ __forceinline__ float ppo_dot4(const float4 h4, const float4 w4) {
+    return __builtin_fmaf(h4.w, w4.w, __builtin_fmaf(h4.z, w4.z, __builtin_fmaf(h4.x, w4.x, h4.y * w4.y)));
+}
+
+// The critic's last layer for all ROWS rows of a block by SWAVES waves that have no part in the head's matrix phase (the staged
+// schedule: ppo_head_block with SWAVES > 0; the caller runs this on those waves in front of the call).  ROWS / SWAVES rows per wave with
+// the rows' loads in flight together, two k trips at a time, `vweight` loaded once per trip; per row the same lane -> k map, the same sum
+// over k and the same xor tree as in ppo_head_block, so the value is the same bit for bit.  The computing wave stores the value slot.
+// st: the thread's index among the 64 SWAVES staging threads.
+template <int ROWS, int SWAVES>
+__device__ __forceinline__ void ppo_head_stage_values(const int st, const int64_t r0, const float* __restrict__ vhidden, const float* __restrict__ vweight,
+                                                      const float* __restrict__ vbias, int VH, float* value_slot, int64_t N) {
+    constexpr int RPS = ROWS / SWAVES;
+    static_assert(ROWS % SWAVES == 0, "whole rows per staging wave");
+    if (!vhidden) return;
+    const int lane = st & 63, sw = st >> 6;
+    float part[RPS];
+    const float* hv[RPS];
+#pragma unroll
+    for (int q = 0; q < RPS; q++) {
+        const int64_t row = r0 + sw * RPS + q;
+        hv[q] = vhidden + (row < N ? row : N - 1) * (int64_t)VH;
+        part[q] = 0.f;
+    }
+    // two trips of the k loop per pass, the second one from a clamped address and added only where it exists: k ascends per lane as in
+    // the plain loop
+    for (int k = lane * 4; k < VH; k += 512) {
+        const bool two = k + 256 < VH;
+        const int k2 = two ? k + 256 : k;
+        const float4 w4 = *reinterpret_cast<const float4*>(vweight + k), w4b = *reinterpret_cast<const float4*>(vweight + k2);
+        float4 h4[RPS], h4b[RPS];
+#pragma unroll
+        for (int q = 0; q < RPS; q++) { h4[q] = *reinterpret_cast<const float4*>(hv[q] + k); h4b[q] = *reinterpret_cast<const float4*>(hv[q] + k2); }
+#pragma unroll
+        for (int q = 0; q < RPS; q++) {
+            part[q] += ppo_dot4(h4[q], w4);
+            const float second = part[q] + ppo_dot4(h4b[q], w4b);
+            part[q] = two ? second : part[q];
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+        for (int q = 0; q < RPS; q++) part[q] += __shfl_xor(part[q], m, 64);
+    }
+    if (value_slot && lane == 0) {
+        const float vb = vbias[0];
+#pragma unroll
+        for (int q = 0; q < RPS; q++) {
+            const int64_t row = r0 + sw * RPS + q;
+            if (row < N) value_slot[row] = part[q] + vb;
+        }
+    }
+}
+
 // The actor's last Linear layer folded in: mean = hidden @ W^T + b on the matrix cores, then the sampling.
 // A block owns 16 RT rows; its WAVES (8 when H is a multiple of 512, else 4 / 2 / 1) waves split K = H evenly and each accumulates the 16 x A tile of its share with
 // v_mfma_f32_16x16x4_f32 (exact fp32 products and sums).  Operand lane map: lane l supplies A[l & 15][k = l >> 4] and
@@ -69,7 +128,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // CONTIGUOUS memory.  From the row-major [A][H] matrix the same load touches 16 rows x 64 B with the four lanes of a row 16 lanes apart:
 // 64 separate cache-line accesses per instruction, and the 160 KB every workgroup needs of it arrive at ~40 GB/s (measured: the fused
 // step kernel 38.4-39.2 us against 40.4-41.4, the rollout step 0.1391 against 0.1410 ms).  The values and their order are the same.
-template <int NCT, int WAVES, int RT, int UB = 4, bool TILED = false>
+// SWAVES > 0: the staged schedule, for a block with SWAVES waves beside the head's WAVES (the step kernel's prologue): those waves have
+// evaluated the critic's values and stored the value slots IN FRONT OF THE CALL (ppo_head_stage_values), so the head's waves start with
+// their operand loads instead of the critic's four dependent round trips.  Everything else is the schedule described above; every output
+// keeps its sequence of products and sums.  SWAVES = 0: the stand-alone kernel, which has no idle waves.
+template <int NCT, int WAVES, int RT, int UB = 4, bool TILED = false, int SWAVES = 0>
 __device__ __forceinline__ void ppo_head_block(float* s_part, const int tid, const bool active, const int64_t r0,
                                                const float* __restrict__ hidden, const float* __restrict__ weight,
                                                const float* __restrict__ bias, int H, const float* __restrict__ value,
@@ -79,6 +142,7 @@ __device__ __forceinline__ void ppo_head_block(float* s_part, const int tid, con
                                                int64_t row_offset, int ref_scale, const PpoActOut& o, int64_t N, int A,
                                                const float* __restrict__ weight_tiles = nullptr) {
     constexpr int AP = NCT * 16, ROWS = 16 * RT;
+    constexpr bool STAGED = SWAVES > 0;
     constexpr int RPW = ROWS / WAVES;                                        // rows sampled per wave (WAVES in 1, 2, 4, 8)
 #if MMS_HEAD_STAMP   // phase probe (timing experiments only): 100-MHz ticks of block 0 / wave 0 into sigma_slot[0..5]
     uint64_t st[6];
@@ -115,12 +179,12 @@ __device__ __forceinline__ void ppo_head_block(float* s_part, const int tid, con
 #pragma unroll
         for (int q = 0; q < RPW; q++) {
             const int64_t row = r0 + wave * RPW + q;
-            if (vhidden && row < N) {
+            if (!STAGED && vhidden && row < N) {
                 const float* hv = vhidden + row * (int64_t)VH;
                 float part = 0.f;
                 for (int k = lane * 4; k < VH; k += 256) {
                     const float4 h4 = *reinterpret_cast<const float4*>(hv + k), w4 = *reinterpret_cast<const float4*>(vweight + k);
-                    part += h4.x * w4.x + h4.y * w4.y + h4.z * w4.z + h4.w * w4.w;
+                    part += ppo_dot4(h4, w4);
                 }
 #pragma unroll
                 for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
@@ -190,7 +254,10 @@ __device__ __forceinline__ void ppo_head_block(float* s_part, const int tid, con
             const int r = wave * RPW + q;
             const int64_t row = r0 + r;
             if (row >= N) continue;
-            ppo_sample_row(s_mean + r * AP, value, log_std, seed, counters, row_offset, ref_scale, o, row, A, lane, vhidden != nullptr, v_rows[q]);
+            if constexpr (STAGED)                                            // (the value slot was stored by the staging wave)
+                ppo_sample_row(s_mean + r * AP, vhidden ? nullptr : value, log_std, seed, counters, row_offset, ref_scale, o, row, A, lane);
+            else
+                ppo_sample_row(s_mean + r * AP, value, log_std, seed, counters, row_offset, ref_scale, o, row, A, lane, vhidden != nullptr, v_rows[q]);
         }
     }
 #if MMS_HEAD_STAMP

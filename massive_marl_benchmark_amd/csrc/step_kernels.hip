@@ -171,9 +171,12 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 64 ? MMS_WAVES_PER_EU : ((BLOC
     // The block's 16 envs are the 16 rows of one heads-kernel block: waves 0-7 run head_block.h's body (the same instruction sequence as
     // mms_ppo_heads_act: K = 512 split over eight waves, v_mfma_f32_16x16x4_f32, partial sums in wave order, sampling by row) in the
     // kinematics parking space (partials [8][16][80], means [16][80], the block's sampled actions [16][80]: free until the inward pass).
-    // Waves 8-11 have no part in it but its barriers: they stage the block's inputs meanwhile -- the root slice, the config block, the
-    // leg constants, the caches -- which the other instantiations do with all twelve waves further down; the HBM round trip of the
-    // staging then lies under the head's.  Every ant lane takes its two actions into registers before the space is reused.
+    // Waves 8-11 have no part in its matrix phase: they stage the block's inputs meanwhile -- the root slice, the config block, the leg
+    // constants, the caches -- which the other instantiations do with all twelve waves further down, and evaluate the critic's values
+    // (head_block.h: ppo_head_stage_values), which waves 0-7 would otherwise compute in front of their operand loads.  Every ant lane
+    // takes its two actions into registers before the space is reused.
+    // s_stage - env_lds for the compile-time layouts (the run-time pointers are formed below; the assert there keeps the two together)
+    constexpr int kStageOff = ((kRedOff + (RP_STRIDE + 6) * (AT > 0 ? AT : 1) + 3) & ~3) + ((kObsAT + 3) & ~3);
     if constexpr (HEAD) {
         static_assert(BLOCK == 768 && EPB == 16 && AT == 10 && TASK == MMS_TASK_TEN_ANT && kStage, "the fused head assumes 16 rows x 80 actions per block");
         float* s_head = lds_lanes;
@@ -181,27 +184,44 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 64 ? MMS_WAVES_PER_EU : ((BLOC
         static_assert((9 + 1) * 16 * 80 <= 6 * 4 * BLOCK, "the head's LDS must fit the parking space");
         if (threadIdx.x >= 512) {
             const int t = (int)threadIdx.x - 512;
-            const float4* src = reinterpret_cast<const float4*>(a.root_states + (size_t)blockIdx.x * root_floats);   // (num_envs % 16 == 0: no partial block)
-            for (int i = t; i < root_floats / 4; i += 256) reinterpret_cast<float4*>(s_root)[i] = src[i];
-            for (int i = t; i < (int)(sizeof(mms_config) / 4); i += 256) lds[i] = reinterpret_cast<const float*>(Cg)[i];
-            if (t < 4) s_leg[t] = load_leg_const(&Cg->model, t);
-            constexpr int kStageOff = ((kRedOff + (RP_STRIDE + 6) * AT + 3) & ~3) + ((kObsAT + 3) & ~3);          // s_stage - env_lds
-            for (int i = t; i < EPB * prev_dim; i += 256) {
-                const int e = i / prev_dim, k = i - e * prev_dim;
-                (lds_envs + (size_t)e * env_stride + kStageOff)[k] = a.prev[((size_t)blockIdx.x * EPB + e) * prev_dim + k];
+            // Straight-line code: every load is issued before the first of them is waited for -- one round trip for all of it, where a
+            // loop per array waits for each array and trip in a basic block of its own (six dependent trips as the loops were compiled).
+            // Indices are clamped instead of tested: a thread past the end of an array fetches its last element and stores it once more.
+            // Those duplicate stores are write-write races by design: harmless only because every such thread stores the SAME value to the
+            // same address.
+            constexpr int kRoot4 = EPB * (AT + 1) * 13 / 4, kPrev = EPB * kPrevAT, kCfgWords = (int)(sizeof(mms_config) / 4);
+            static_assert(kRoot4 <= 768 && kPrev <= 768 && kCfgWords <= 256, "three trips of the 256 staging threads");
+            const float4* src = reinterpret_cast<const float4*>(a.root_states + (size_t)blockIdx.x * (4 * kRoot4));   // (num_envs % 16 == 0: no partial block)
+            const float* psrc = a.prev + (size_t)blockIdx.x * kPrev;           // the caches of the block's envs are contiguous in HBM
+            float4 rv[3];
+            float pv[3];
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                rv[j] = src[min(t + 256 * j, kRoot4 - 1)];
+                pv[j] = psrc[min(t + 256 * j, kPrev - 1)];
             }
+            const float cw = reinterpret_cast<const float*>(Cg)[min(t, kCfgWords - 1)];
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                reinterpret_cast<float4*>(s_root)[min(t + 256 * j, kRoot4 - 1)] = rv[j];
+                const int i = min(t + 256 * j, kPrev - 1), e = i / kPrevAT, k = i - e * kPrevAT;
+                (lds_envs + (size_t)e * env_stride + kStageOff)[k] = pv[j];
+            }
+            lds[min(t, kCfgWords - 1)] = cw;
+            if (t < 4) s_leg[t] = load_leg_const(&Cg->model, t);
+            ppo_head_stage_values<16, 4>(t, (int64_t)blockIdx.x * 16, a.head.vhidden, a.head.vweight, a.head.vbias, a.head.VH, a.head.value_slot, a.num_envs);
         }
         PpoActOut o{a.head.actions_out, a.head.act_slot, a.head.logp_slot, a.head.value_slot, a.head.mu_slot, a.head.sigma_slot};
         o.lds_actions = s_head_actions;
         o.lds_row0 = (int64_t)blockIdx.x * 16;
         if (a.head.weight_tiles)                                     // (uniform: the tiled copy of the head's weights, head_block.h)
-            ppo_head_block<5, 8, 1, 4, true>(s_head, (int)threadIdx.x, threadIdx.x < 512, (int64_t)blockIdx.x * 16, a.head.hidden, a.head.weight, a.head.bias, a.head.H, nullptr,
-                                             a.head.vhidden, a.head.vweight, a.head.vbias, a.head.VH, a.head.log_std, a.head.seed, a.head.counters, a.head.row_offset,
-                                             a.head.reference_scale, o, a.num_envs, 8 * AT, a.head.weight_tiles);
+            ppo_head_block<5, 8, 1, 4, true, 4>(s_head, (int)threadIdx.x, threadIdx.x < 512, (int64_t)blockIdx.x * 16, a.head.hidden, a.head.weight, a.head.bias, a.head.H, nullptr,
+                                                a.head.vhidden, a.head.vweight, a.head.vbias, a.head.VH, a.head.log_std, a.head.seed, a.head.counters, a.head.row_offset,
+                                                a.head.reference_scale, o, a.num_envs, 8 * AT, a.head.weight_tiles);
         else
-            ppo_head_block<5, 8, 1, 4>(s_head, (int)threadIdx.x, threadIdx.x < 512, (int64_t)blockIdx.x * 16, a.head.hidden, a.head.weight, a.head.bias, a.head.H, nullptr,
-                                       a.head.vhidden, a.head.vweight, a.head.vbias, a.head.VH, a.head.log_std, a.head.seed, a.head.counters, a.head.row_offset,
-                                       a.head.reference_scale, o, a.num_envs, 8 * AT);
+            ppo_head_block<5, 8, 1, 4, false, 4>(s_head, (int)threadIdx.x, threadIdx.x < 512, (int64_t)blockIdx.x * 16, a.head.hidden, a.head.weight, a.head.bias, a.head.H, nullptr,
+                                                 a.head.vhidden, a.head.vweight, a.head.vbias, a.head.VH, a.head.log_std, a.head.seed, a.head.counters, a.head.row_offset,
+                                                 a.head.reference_scale, o, a.num_envs, 8 * AT);
         __syncthreads();                                             // the sampled actions are in LDS
         if (threadIdx.x < 16 * 4 * AT) ac_head = reinterpret_cast<const float2*>(s_head_actions)[threadIdx.x];   // lane (env e, ant lane t) = thread 40 e + t: actions 80 e + 2 t
         // (no barrier behind the reads: nothing writes the parking space before the first substep's inward pass, which sits behind the
@@ -277,8 +297,11 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 64 ? MMS_WAVES_PER_EU : ((BLOC
         si[0] = (int)(pr & 0xffffffff); si[1] = (int)(pr >> 32); si[2] = (int)(rc & 0xffffffff); si[3] = (int)(rc >> 32);
     }
     if (is_ant) {
-        s_act[0] = clampf(ac.x, -Cg->clip_actions, Cg->clip_actions);     // vec_task.py:127
-        s_act[1] = clampf(ac.y, -Cg->clip_actions, Cg->clip_actions);
+        // (HEAD: the LDS copy of the config block is valid behind the head's barriers -- no global fetch here; it is also what keeps this
+        //  instantiation's scratch at 16 B: with the global read the allocator takes 20)
+        const float clip_a = (HEAD ? C : Cg)->clip_actions;
+        s_act[0] = clampf(ac.x, -clip_a, clip_a);                         // vec_task.py:127
+        s_act[1] = clampf(ac.y, -clip_a, clip_a);
     }
     if (kStage) __syncthreads();
     if (kStage && is_ant) {                                          // this lane's torso from the staged slice
