@@ -204,7 +204,11 @@ int mms_bind_actions(mms_handle h, const float* src);
  *   [9..16] joint damping scale, [17..24] lower-limit offset, [25..32] upper-limit offset (rad), joints in DOF order;
  * mms_set_dr(h, 1) makes mms_step use it (a separate kernel instantiation: the nominal path carries none of it).  The
  * observations keep the nominal limits, as the reference's do (ten_ant.py:588-599 reads them once at construction).
- * DOF stiffness is not a parameter of this path: the tasks drive the joints in effort mode (ten_ant.py:274). */
+ * DOF stiffness is not a parameter of this path: the tasks drive the joints in effort mode (ten_ant.py:274).
+ * DR and a bound policy head exclude each other in both directions and in both builds (the fused head's step kernel has no DR form):
+ * mms_bind_policy_head fails while DR is on, and mms_set_dr(h, 1) while a head is bound returns non-zero with a message that names
+ * mms_bind_policy_head and changes nothing -- the head stays bound for the next mms_step, DR stays off.  mms_set_dr(h, 0) always
+ * succeeds. */
 int mms_set_dr(mms_handle h, int32_t enable);
 
 /* Which of the engine-owned observation rows mms_step writes: "obs" (raw, = task.obs_buf of the reference) and "obs_clipped"
@@ -307,7 +311,10 @@ int mms_ppo_heads_act(int device, const float* hidden, const float* weight, cons
  * step that consumes it clears it (the slot pointers move with every rollout step).  Available where the step kernel runs its 16-envs-
  * per-workgroup TenAnt layout (num_agents 10, num_envs a multiple of 16 and >= 16 per CU, no physical DR) with H a multiple of 512 and
  * A = 80; anywhere else the call fails and the caller launches mms_ppo_heads_act.  Fields as the arguments of mms_ppo_heads_act;
- * actions_out may name the engine's "actions" buffer (kept for task.actions) or be NULL. */
+ * actions_out may name the engine's "actions" buffer (kept for task.actions) or be NULL.
+ * actions_out = NULL: every other slot is written as usual and the physics follows the sampled actions (what act_slot receives).  What
+ * the engine's own "actions" buffer holds after such a step is UNSPECIFIED: the HIP build leaves it as it was (the actions travel through
+ * LDS), the CPU build stores the sampled actions there.  A caller that wants them reads act_slot, or hands in actions_out. */
 typedef struct mms_policy_head {
     const float* hidden; const float* weight; const float* bias;        /* actor: last hidden activations [N, H], last layer [A, H], [A] */
     const float* vhidden; const float* vweight; const float* vbias;     /* critic: [N, VH], [VH], [1] */

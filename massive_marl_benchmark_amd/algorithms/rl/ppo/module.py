@@ -91,8 +91,8 @@ class ActorCritic(nn.Module):
 
     # Hidden layers of both networks through mms_linear2_act (own fp32-MFMA GEMM, bias + ELU in the epilogue, one launch per layer
     # for both networks) and both last layers inside the sampling kernel (mms_ppo_heads_act): five launches per `act`.  Used when
-    # the networks qualify (fp32, ELU, actor and critic of the same hidden shapes, last hidden width a multiple of 64); otherwise
-    # the library path below.  Rollout step at 4096 envs: 350 us, against 361 us for the library GEMMs + separate ELU passes with the
+    # the networks qualify (fp32, ELU, actor and critic of the same hidden shapes, last hidden width a multiple of 64); two fp32 ELU
+    # networks of DIFFERENT hidden shapes run one mms_linear2_act launch per layer and network instead; otherwise the library path below.  Rollout step at 4096 envs: 350 us, against 361 us for the library GEMMs + separate ELU passes with the
     # critic on a second stream (profiles/r01_v12_bench.json, r01_v12_bench_library_gemms.json).  With fuse_layers off, fuse_head alone puts only the actor's last layer into
     # the sampling kernel (no gain next to the critic's GEMMs: 371.8 us against 365.5 us, profiles/r01_v8_rollout_ab.txt).
     fuse_layers = True
@@ -141,6 +141,15 @@ class ActorCritic(nn.Module):
                       and la.bias is not None and lc.bias is not None for la, lc in zip(a_lin[:-1], c_lin[:-1])))
         self._qualify = (dt, ok)
         return ok
+
+    @staticmethod
+    def _fp32_net_qualifies(net):
+        """mms_linear2_act applies to ONE network (its form with the second problem NULL: _hidden_one): an fp32 ELU network, hidden layers
+        with biases and input widths that are multiples of 4."""
+        lin = [m for m in net if isinstance(m, nn.Linear)]
+        acts = [m for m in net if not isinstance(m, nn.Linear)]
+        return (len(lin) >= 2 and all(isinstance(m, nn.ELU) and m.alpha == 1.0 for m in acts)
+                and all(l.weight.dtype == torch.float32 and l.in_features % 4 == 0 and l.bias is not None for l in lin[:-1]))
 
     # -- split-operand layers ------------------------------------------------------------------
     @staticmethod
@@ -535,10 +544,11 @@ class ActorCritic(nn.Module):
         p = lambda t: ctypes.c_void_p(t.data_ptr())
         M = x.shape[0]
         key = (M, str(x.device), id(net))
-        if self._one_bufs is None or self._one_bufs[0] != key:
-            self._one_bufs = (key, [torch.empty(M, l.out_features, device=x.device) for l in lin])
+        if self._one_bufs is None or key not in self._one_bufs:      # (per network: actor and critic may both come through here)
+            self._one_bufs = {k: v for k, v in (self._one_bufs or {}).items() if k[:2] == key[:2]}
+            self._one_bufs[key] = [torch.empty(M, l.out_features, device=x.device) for l in lin]
         h = x
-        for l, y in zip(lin, self._one_bufs[1]):
+        for l, y in zip(lin, self._one_bufs[key]):
             _lib.check(L.mms_linear2_act(idx, M, l.out_features, l.in_features, p(h), p(l.weight.detach()), p(l.bias.detach()), p(y),
                                          None, None, None, None, 1, stream), None, "mms_linear2_act", L)
             h = y
@@ -633,6 +643,12 @@ class ActorCritic(nn.Module):
             critic_in = (states if self.asymmetric else observations).to(dtype)
             if self.fuse_layers and observations.is_cuda and dtype == torch.float32 and not self.defer_value:
                 hidden = self._fused_hidden(observations, critic_in, None if self.asymmetric else obs_planes)
+                if hidden is None and self._fp32_net_qualifies(self.actor) and self._fp32_net_qualifies(self.critic):
+                    # actor and critic of DIFFERENT hidden shapes (no grouped launch takes both): each network's hidden layers on their
+                    # own, one mms_linear2_act launch per layer, so that the heads still run in the sampling kernel -- or, with a step
+                    # engine bound, in the step's prologue (mms_bind_policy_head takes any VH that is a multiple of 4)
+                    self._ensure_fresh()
+                    hidden = self._hidden_one(self.actor, observations.contiguous()), self._hidden_one(self.critic, critic_in.contiguous())
                 if hidden is not None:
                     ha, hc = hidden
                     la, lc = self.actor[-1], self.critic[-1]

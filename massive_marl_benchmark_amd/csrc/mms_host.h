@@ -255,6 +255,11 @@ static inline int host_bind_policy_head(mms_host_state* h, const mms_policy_head
 static inline int host_set_dr(mms_host_state* h, int32_t enable) {
     if (null_handle(h, "mms_set_dr")) return 1;
     if (enable && h->cfg.task == MMS_TASK_MULTI_INGENUITY) return fail(h, "mms_set_dr: the helicopter task has no randomised physical parameters");
+    // the other half of mms_bind_policy_head's "no physical DR": the fused head's step kernel has no DR form, so DR cannot come on between
+    // a bind and the step that consumes it (nothing changes: the head stays bound, DR stays off)
+    if (enable && h->head_on)
+        return fail(h, "mms_set_dr: a policy head is bound (mms_bind_policy_head) and its step has no physical DR -- step first, or unbind with "
+                       "mms_bind_policy_head(h, NULL)");
     h->dr_enabled = enable != 0;
     return 0;
 }

@@ -102,5 +102,27 @@ def check_head_bind_errors(device, num_envs):
     fails(head(hidden=p(hidden) + 4), "aligned")
     assert L.mms_bind_policy_head(h, ctypes.byref(head(weight_tiles=p(tiles)))) == 0
     assert L.mms_bind_policy_head(h, None) == 0
+    # DR under a bound head (include/mms.h, mms_set_dr): refused in words that name the bind, and nothing changes -- DR stays off (a head
+    # can still be bound, which mms_bind_policy_head refuses while DR is on) and the head stays bound: the next step consumes it (the
+    # draw counters advance, the value slot receives vbias) and clears the binding (the step after it draws nothing)
+    value = torch.full((N,), float("nan"), device=dev)
+    vbias.fill_(0.25)
+    assert L.mms_bind_policy_head(h, ctypes.byref(head(value_slot=p(value)))) == 0
+    rc = L.mms_set_dr(h, 1)
+    msg = _lib.last_error(h, L)
+    assert rc != 0 and "mms_set_dr" in msg and "mms_bind_policy_head" in msg, (rc, msg)
+    assert L.mms_set_dr(h, 0) == 0
+    assert L.mms_bind_policy_head(h, ctypes.byref(head(value_slot=p(value)))) == 0, _lib.last_error(h, L)
+    assert L.mms_set_dr(h, 1) != 0
+    eng.reset_all()
+    eng.step()
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    assert bool((counters == 1).all()) and bool((value == 0.25).all()), "the step behind a refused mms_set_dr must consume the bound head"
+    eng.step()
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    assert bool((counters == 1).all())
+    assert L.mms_set_dr(h, 1) == 0 and L.mms_set_dr(h, 0) == 0                       # (no head bound any more: DR is the caller's choice again)
     eng.close()
     return True

@@ -85,9 +85,9 @@ def _ratio(err, tol):
     return float(np.where(err > 0, err / np.maximum(tol, 1e-300), 0.0).max())
 
 
-def report(tdev, name, **ratios):
-    print("%s/ppo_rollout/%s: %s" % (_where(tdev), name, ", ".join("%s %.3g" % kv for kv in sorted(ratios.items()))))
-    parity.record("%s/ppo_rollout/%s" % (_where(tdev), name), **ratios)
+def report(tdev, name, group="ppo_rollout", **ratios):
+    print("%s/%s/%s: %s" % (_where(tdev), group, name, ", ".join("%s %.3g" % kv for kv in sorted(ratios.items()))))
+    parity.record("%s/%s/%s" % (_where(tdev), group, name), **ratios)
 
 
 def _bits(a):
@@ -285,6 +285,8 @@ def gate_sample(pr, o, entry, *, N, row0=0, ref_scale=1, seed, row_offset=0, cou
         ref = vh.astype(np.float64) @ vw.astype(np.float64) + float(vb[0])
         if mutation == "value_from_value":
             ref = pr["value"][rows].astype(np.float64)
+        if mutation == "value_drop_tail":                            # the last four floats of every vhidden row dropped
+            ref = ref - vh[:, -4:].astype(np.float64) @ vw[-4:].astype(np.float64)
         tol = 2.0 * (-(-pr["VH"] // 256) + 11) * U * (np.abs(vh).astype(np.float64) @ np.abs(vw).astype(np.float64) + abs(float(vb[0])))
         yard = _ratio(np.abs(value_head_f32(vh, vw, vb) - vh.astype(np.float64) @ vw.astype(np.float64) - float(vb[0])), tol)
         assert yard <= 0.5, ("value head yardstick", pr["VH"], yard)

@@ -4,6 +4,8 @@ critic's values.  Everything the fused launch leaves is compared BIT FOR BIT, st
 leave -- the stand-alone heads kernel keeps the unstaged schedule of the same body.
 
 Sizes: 16 envs = one block, 48 = three blocks (layout forced with MMS_STEP_BLOCK16), and 4096 once in the layout the engine picks itself.
+Hidden sizes: [256, 512] for both networks, and once at 48 envs an actor of [256, 1024] beside a critic of [256, 384] (H = 1024, VH = 384;
+the widths one at a time: tests/test_head_shapes_gpu.py).  Every fused run also proves that the module bound a head at every step.
 Ten steps over a RolloutStorage of four cross two rollout boundaries (`refresh`); the parameters move in place in the middle; reset flags
 are raised by hand in front of two steps with a bound head, in the first and the last block (an env that is reset under a bound head); the value slots are pre-filled with NaN before every step (a row the staging waves skip stays NaN)."""
 import pytest
@@ -24,7 +26,10 @@ def torch_cuda():
     return torch
 
 
-def _run(torch, num_envs, fused):
+HIDDEN = ([256, 512], [256, 512])      # (pi_hid_sizes, vf_hid_sizes) of the cases that do not name their own
+
+
+def _run(torch, num_envs, fused, hidden=HIDDEN):
     """Ten steps; returns per step a dict of clones (the slot the step wrote, the draw counters, the engine's state behind it)."""
     from massive_marl_benchmark_amd.algorithms.rl.ppo.module import ActorCritic
     from massive_marl_benchmark_amd.algorithms.rl.ppo.storage import RolloutStorage
@@ -33,12 +38,15 @@ def _run(torch, num_envs, fused):
     eng = Engine("TenAnt", num_envs=num_envs, device=0, seed=11, clip_obs=5.0)
     assert eng.takes_policy_head(), "the engine does not take a bound policy head at this size"
     torch.manual_seed(4)
-    ac = ActorCritic((eng.obs_dim,), (0,), (eng.num_actions,), 0.8, {"pi_hid_sizes": [256, 512], "vf_hid_sizes": [256, 512], "activation": "elu"},
+    ac = ActorCritic((eng.obs_dim,), (0,), (eng.num_actions,), 0.8, {"pi_hid_sizes": list(hidden[0]), "vf_hid_sizes": list(hidden[1]), "activation": "elu"},
                      seed=21).to(dev)
     ac.split_min_tiles = 0
     storage = RolloutStorage(num_envs, SLOTS, (eng.obs_dim,), (0,), (eng.num_actions,), device=str(dev))
     ac.bind_rollout(storage, eng.tensor("actions"), step_engine=eng if fused else None)
     assert (ac._step_engine is not None) == fused
+    bound = []                                                       # the heads the module hands to the engine: one per step when fused
+    bind = eng.bind_policy_head
+    eng.bind_policy_head = lambda head: (bound.append(head), bind(head))[1]
     states = torch.zeros(num_envs, 0, device=dev)
     flagged = torch.tensor(sorted({1, 5, num_envs - 1}), device=dev)
     eng.reset_all()
@@ -69,13 +77,14 @@ def _run(torch, num_envs, fused):
             rec["eng/" + k] = eng.tensor(k).clone()
         out.append(rec)
     torch.cuda.synchronize()
+    assert len(bound) == (STEPS if fused else 0) and None not in bound, "the module did not take the fused launch: %d heads bound in %d steps" % (len(bound), STEPS)
     eng.bind_rollout_out(None, None)
     eng.close()
     return out, flagged
 
 
-def _compare(torch, num_envs):
-    (plain, flagged), (fused, _) = _run(torch, num_envs, False), _run(torch, num_envs, True)
+def _compare(torch, num_envs, hidden=HIDDEN):
+    (plain, flagged), (fused, _) = _run(torch, num_envs, False, hidden), _run(torch, num_envs, True, hidden)
     for t, (a, b) in enumerate(zip(plain, fused)):
         bad = ["%s (%d of %d elements, first at %d)" % (k, int((a[k] != b[k]).sum()), a[k].numel(), int((a[k] != b[k]).flatten().nonzero()[0]))
                for k in a if not torch.equal(a[k], b[k])]
@@ -97,6 +106,14 @@ def test_staged_head_equals_separate_launches(torch_cuda, monkeypatch, num_envs)
     """One block and three blocks of the <768, 16> layout (forced: the engine would pick four envs per block at these sizes)."""
     monkeypatch.setenv("MMS_STEP_BLOCK16", "1")
     _compare(torch_cuda, num_envs)
+
+
+@pytest.mark.parametrize("pi_hid,vf_hid", [([256, 1024], [256, 384])])
+def test_staged_head_equals_separate_launches_unequal_widths(torch_cuda, monkeypatch, pi_hid, vf_hid):
+    """Three blocks with a critic narrower than the actor: VH = 384 puts the staging waves' second k trip on lanes 0-31 only, H = 1024
+    gives every head wave two 64-k trips and goes through the module's tiled copy of the actor's last layer."""
+    monkeypatch.setenv("MMS_STEP_BLOCK16", "1")
+    _compare(torch_cuda, 48, (pi_hid, vf_hid))
 
 
 def test_staged_head_equals_separate_launches_4096(torch_cuda, monkeypatch):
