@@ -53,6 +53,9 @@
  *   MAPPO / HAPPO ppo_update's loss head: surrogate, entropy, PopArt /   mms_marl_ppo_loss
  *     Huber value loss, masks and their backward
  *     (algorithms/marl/mappo_trainer.py:63-179, happo_trainer.py:48-170)
+ *   MADDPG: every agent's deterministic actor head, exploration noise    mms_det_heads_act_group
+ *     and the joint action row (algorithms/marl/maddpg/module.py:36-46,
+ *     :165-175); every agent's Q target tail (:218-219)                  mms_q_heads_backup_group
  *
  * Ownership: the engine owns every buffer it reports through mms_get_tensor for the lifetime of the
  * handle; callers wrap them as NON-owning views and must keep the handle alive while any view exists.
@@ -407,6 +410,41 @@ int mms_linear2_act(int device, int64_t M, int32_t N, int32_t K, const float* x0
 int mms_linear_group_act(int device, int32_t groups, int64_t M, int32_t N, int32_t K, const float* const* x, const float* const* w,
                          const float* const* b, float* const* y, int32_t act, const float* const* ln_s, const float* const* ln_stat_in,
                          float* const* ln_part_out, void* hip_stream);
+
+/* ---- MADDPG: the no-gradient tails of all agents' networks per launch --------------------------------------------------------
+ * The last layer of up to MMS_MAX_GROUPS deterministic actors (algorithms/marl/maddpg/module.py:36-46, MLPActLayer.forward from the
+ * last hidden activation on), the exploration noise of MADDPG_policy.act (:165-175) and the stores, in one launch:
+ *   a_g[i,k] = act_limit[g] * tanh(dot(h_g[i,:], w_g[k,:]) + b_g[k])                        g < groups, k < A
+ *   sigma > 0:  a_g[i,k] = clamp(a_g[i,k] + sigma * z, -act_limit[g], act_limit[g]),
+ *               z ~ N(0,1): counter-based (seed, global row = row_offset + i, counters[i], (agent0 + g) * A + k), the stream of
+ *               mms_ppo_act; counters[i] += 1 once per call (behind the draws, on the same stream)
+ *   sigma == 0: nothing is drawn, no clamp, counters untouched (may be NULL)
+ * h, w, b, act_out: HOST arrays of `groups` device pointers; h_g [M,H] f32 (the output of the last hidden activation), w_g [A,H] and
+ * b_g [A] torch's Linear parameters, read in place on every call; act_limit: a HOST array of `groups` floats.  Destinations: act_out
+ * (NULL, or per group NULL: no store) -- act_out[g] [M,A] at act_pitch floats per row, e.g. a ring row of agent g's replay buffer --
+ * and joint_out (NULL: no store) at joint_pitch floats per row, where agent g's actions go to
+ * joint_out[i * joint_pitch + (agent0 + g) * A + k]; every group needs at least one of the two.  agent0 >= 0 lets a caller with more
+ * than MMS_MAX_GROUPS agents chunk the call, or refresh one agent's columns with groups = 1.  On the matrix cores
+ * (v_mfma_f32_16x16x4_f32: exact fp32 products and sums); the order of the sum over k is a function of H and A alone and there are
+ * no atomics: with sigma = 0, a_g[i,:] is a function of row i and network g's parameters only, not of M, groups, agent0, the pitches
+ * or where the row sits.  H a positive multiple of 64, 1 <= A <= 128, h_g and w_g 16-byte aligned, act_pitch >= A (when act_out is
+ * given), joint_pitch >= (agent0 + groups) * A (when joint_out is given), M >= 0 (M == 0 succeeds and touches nothing).  Rows past M
+ * and columns past A are never written.  Bad arguments return non-zero with mms_last_error(NULL) and write nothing. */
+int mms_det_heads_act_group(int device, int32_t groups, int64_t M, int32_t H, int32_t A, int32_t agent0,
+                            const float* const* h, const float* const* w, const float* const* b, const float* act_limit,
+                            float sigma, uint64_t seed, int64_t* counters, int64_t row_offset,
+                            float* const* act_out, int64_t act_pitch, float* joint_out, int64_t joint_pitch, void* hip_stream);
+
+/* mms_q_heads_backup with ONE critic per group for up to MMS_MAX_GROUPS groups in one launch (cal_value_loss, module.py:218-219):
+ *   q_g[i]      = dot(h_g[i,:], w_g) + b_g[0]
+ *   backup_g[i] = reward_g[i] + gamma * (1 - done_g[i]) * q_g[i]
+ * h, w, b, q_out, reward, done, backup: HOST arrays of `groups` device pointers (q_out, reward, done, backup may be NULL as a
+ * whole); q_out[g] and backup[g] may be NULL per group with at least one destination overall; backup[g] needs reward[g] and done[g]
+ * (uint8).  The limits of the ungrouped entry (H a positive multiple of 64 up to MMS_Q_MAX_H, h_g and w_g 16-byte aligned, M >= 0).
+ * Per group the results are bit-identical to mms_q_heads_backup called for that network alone (one network, logp NULL). */
+int mms_q_heads_backup_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* h, const float* const* w,
+                             const float* const* b, float* const* q_out, const float* const* reward, const uint8_t* const* done,
+                             float gamma, float* const* backup, void* hip_stream);
 
 /* stat_g[r] = (mean, 1 / sqrt(var + eps)) of row r from the `slots` partial (sum, sum of squares) pairs of mms_linear_group_act's
  * ln_part_out (width = that layer's N; biased variance, as nn.LayerNorm). */

@@ -21,6 +21,7 @@
 #include "../ppo_loss_lane.h"
 #include "../marl_loss_lane.h"
 #include "../q_lane.h"
+#include "../maddpg_lane.h"
 #include "../sac_lane.h"
 #include "lane_step.h"
 
@@ -331,6 +332,50 @@ MMS_API int mms_q_heads_backup(int device, int64_t M, int32_t H, const float* h0
         if (backup) {
             const float qm = G == 2 ? mms::q_min(q[0], q[1]) : q[0];
             backup[row] = mms::q_backup(reward[row], done[row], qm, logp != nullptr, logp ? logp[row] : 0.f, gamma, alpha);
+        }
+    }
+    return 0;
+}
+MMS_API int mms_det_heads_act_group(int device, int32_t groups, int64_t M, int32_t H, int32_t A, int32_t agent0, const float* const* h,
+                                    const float* const* w, const float* const* b, const float* act_limit, float sigma, uint64_t seed,
+                                    int64_t* counters, int64_t row_offset, float* const* act_out, int64_t act_pitch, float* joint_out,
+                                    int64_t joint_pitch, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_det_heads_act_group(groups, M, H, A, agent0, h, w, b, act_limit, sigma, counters, act_out, act_pitch, joint_out, joint_pitch))) return 1;
+    const bool noisy = sigma > 0.f;
+#pragma omp parallel for schedule(static)
+    for (int64_t row = 0; row < M; row++) {
+        const int64_t c = noisy ? counters[row] : 0;
+        for (int g = 0; g < groups; g++) {
+            const float* x = h[g] + row * (int64_t)H;
+            float* out = act_out ? act_out[g] : nullptr;
+            const int64_t jcol0 = (int64_t)(agent0 + g) * A;
+            for (int k = 0; k < A; k++) {
+                float s = 0.f;
+                for (int j = 0; j < H; j++) s = fmaf(x[j], w[g][(int64_t)k * H + j], s);
+                float act = mms::det_action(s + b[g][k], act_limit[g]);
+                if (noisy) act = mms::det_explore(act, sigma, seed, (uint64_t)(row_offset + row), (uint64_t)c, (uint32_t)(jcol0 + k), act_limit[g]);
+                if (out) out[row * act_pitch + k] = act;
+                if (joint_out) joint_out[row * joint_pitch + jcol0 + k] = act;
+            }
+        }
+        if (noisy) counters[row] = c + 1;
+    }
+    return 0;
+}
+MMS_API int mms_q_heads_backup_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* h, const float* const* w,
+                                     const float* const* b, float* const* q_out, const float* const* reward, const uint8_t* const* done,
+                                     float gamma, float* const* backup, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_q_heads_backup_group(groups, M, H, h, w, b, q_out, reward, done, backup))) return 1;
+#pragma omp parallel for schedule(static)
+    for (int64_t row = 0; row < M; row++) {
+        for (int g = 0; g < groups; g++) {
+            float s = 0.f;                  // mms_q_heads_backup's chain for one network
+            for (int k = 0; k < H; k++) s = fmaf(h[g][row * (int64_t)H + k], w[g][k], s);
+            const float q = mms::q_value(s, b[g][0]);
+            if (q_out && q_out[g]) q_out[g][row] = q;
+            if (backup && backup[g]) backup[g][row] = mms::q_backup(reward[g][row], done[g][row], q, false, 0.f, gamma, 0.f);
         }
     }
     return 0;

@@ -10,6 +10,7 @@
 #include "step_args.h"
 #include "trpo_plan.h"
 #include "ln_mlp_plan.h"
+#include "maddpg_args.h"
 
 namespace mms {
 hipError_t launch_step(const StepArgs& a, int task, hipStream_t stream);
@@ -348,6 +349,42 @@ __attribute__((visibility("default"))) int mms_q_heads_backup(int device, int64_
     const float* b[2] = {b0, b1};
     float* q[2] = {q0_out, q1_out};
     MMS_FREE(mms::launch_q_heads_backup(h1 ? 2 : 1, M, H, h, w, b, q, reward, done, backup ? logp : nullptr, gamma, alpha, backup, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_det_heads_act_group(int device, int32_t groups, int64_t M, int32_t H, int32_t A, int32_t agent0,
+                                                                   const float* const* h, const float* const* w, const float* const* b,
+                                                                   const float* act_limit, float sigma, uint64_t seed, int64_t* counters,
+                                                                   int64_t row_offset, float* const* act_out, int64_t act_pitch, float* joint_out,
+                                                                   int64_t joint_pitch, void* s) {
+    MMS_DEV(device)
+    if (refused(check_det_heads_act_group(groups, M, H, A, agent0, h, w, b, act_limit, sigma, counters, act_out, act_pitch, joint_out, joint_pitch))) return 1;
+    mms::DetHeadsArgs a = {};
+    for (int g = 0; g < groups; g++) {
+        a.h[g] = h[g]; a.w[g] = w[g]; a.b[g] = b[g]; a.act_out[g] = act_out ? act_out[g] : nullptr; a.act_limit[g] = act_limit[g];
+    }
+    a.joint_out = joint_out; a.counters = counters; a.seed = seed; a.M = M; a.row_offset = row_offset; a.act_pitch = act_pitch;
+    a.joint_pitch = joint_pitch; a.H = H; a.A = A; a.agent0 = agent0; a.sigma = sigma;
+    MMS_FREE(mms::launch_det_heads_act(a, groups, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_q_heads_backup_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* h,
+                                                                    const float* const* w, const float* const* b, float* const* q_out,
+                                                                    const float* const* reward, const uint8_t* const* done, float gamma,
+                                                                    float* const* backup, void* s) {
+    MMS_DEV(device)
+    if (refused(check_q_heads_backup_group(groups, M, H, h, w, b, q_out, reward, done, backup))) return 1;
+    mms::QGroupArgs a = {};
+    for (int g = 0; g < groups; g++) {
+        a.h[g] = h[g]; a.w[g] = w[g]; a.b[g] = b[g];
+        a.q_out[g] = q_out ? q_out[g] : nullptr;
+        a.backup[g] = backup ? backup[g] : nullptr;
+        a.reward[g] = a.backup[g] ? reward[g] : nullptr;
+        a.done[g] = a.backup[g] ? done[g] : nullptr;
+    }
+    a.gamma = gamma; a.M = M; a.H = H;
+    MMS_FREE(mms::launch_q_heads_backup_group(a, groups, (hipStream_t)s));
     return 0;
 }
 

@@ -367,6 +367,46 @@ static inline std::string check_q_heads_backup(int64_t M, int32_t H, const float
     return {};
 }
 
+static inline std::string check_det_heads_act_group(int32_t groups, int64_t M, int32_t H, int32_t A, int32_t agent0, const float* const* h,
+                                                    const float* const* w, const float* const* b, const float* act_limit, float sigma,
+                                                    const int64_t* counters, float* const* act_out, int64_t act_pitch, const float* joint_out,
+                                                    int64_t joint_pitch) {
+    std::string bad = check_groups("mms_det_heads_act_group", groups);
+    if (!bad.empty()) return bad;
+    if (!h || !w || !b || !act_limit || M < 0 || A <= 0 || A > 128 || H <= 0 || (H % 64) != 0 || agent0 < 0 || !(sigma >= 0.f))
+        return "mms_det_heads_act_group: bad arguments (A must be in 1..128, H a positive multiple of 64, M >= 0, agent0 >= 0, sigma >= 0)";
+    if (sigma > 0.f && !counters) return "mms_det_heads_act_group: sigma > 0 needs counters";
+    bool any_act = false;
+    for (int g = 0; g < groups; g++) {
+        if (!h[g] || !w[g] || !b[g]) return "mms_det_heads_act_group: null pointer in a group";
+        if ((addr(h[g]) | addr(w[g])) & 15) return "mms_det_heads_act_group: hidden activations and weights must be 16-byte aligned";
+        const bool act = act_out && act_out[g];
+        any_act = any_act || act;
+        if (!act && !joint_out) return "mms_det_heads_act_group: no destination (act_out[g] and joint_out both NULL)";
+    }
+    if (any_act && act_pitch < A) return "mms_det_heads_act_group: act_pitch below A";
+    if (joint_out && joint_pitch < ((int64_t)agent0 + groups) * A) return "mms_det_heads_act_group: joint_pitch below (agent0 + groups) * A";
+    return {};
+}
+
+static inline std::string check_q_heads_backup_group(int32_t groups, int64_t M, int32_t H, const float* const* h, const float* const* w,
+                                                     const float* const* b, float* const* q_out, const float* const* reward,
+                                                     const uint8_t* const* done, float* const* backup) {
+    std::string bad = check_groups("mms_q_heads_backup_group", groups);
+    if (!bad.empty()) return bad;
+    if (!h || !w || !b || M < 0 || H <= 0 || (H % 64) != 0 || H > MMS_Q_MAX_H)
+        return "mms_q_heads_backup_group: bad arguments (h, w, b required, M >= 0, H a positive multiple of 64 up to " + std::to_string(MMS_Q_MAX_H) + ")";
+    bool any = false;
+    for (int g = 0; g < groups; g++) {
+        if (!h[g] || !w[g] || !b[g]) return "mms_q_heads_backup_group: null pointer in a group";
+        if ((addr(h[g]) | addr(w[g])) & 15) return "mms_q_heads_backup_group: hidden activations and weights must be 16-byte aligned";
+        if (backup && backup[g] && (!reward || !done || !reward[g] || !done[g])) return "mms_q_heads_backup_group: the backup needs reward and done";
+        any = any || (q_out && q_out[g]) || (backup && backup[g]);
+    }
+    if (!any) return "mms_q_heads_backup_group: no destination (every q_out[g] and backup[g] NULL)";
+    return {};
+}
+
 // mms_ppo_loss: the shapes, then (workspace NULL is the size query: nothing else is read) the operands and the workspace against
 // `need`, the bytes this build's plan asks for (the CPU build's: 0).
 static inline std::string check_ppo_loss(int64_t M, int32_t A, const float* mu, const float* log_std, const float* value, const float* actions,
