@@ -56,6 +56,9 @@
  *   MADDPG: every agent's deterministic actor head, exploration noise    mms_det_heads_act_group
  *     and the joint action row (algorithms/marl/maddpg/module.py:36-46,
  *     :165-175); every agent's Q target tail (:218-219)                  mms_q_heads_backup_group
+ *   clip_grad_norm_ + Adam.step() + the polyak loop of every learner     mms_param_step
+ *     (rl/sac/sac.py:325-349, rl/ppo/ppo.py, marl/mappo_trainer.py,
+ *     marl/maddpg/module.py:280-292)
  *
  * Ownership: the engine owns every buffer it reports through mms_get_tensor for the lifetime of the
  * handle; callers wrap them as NON-owning views and must keep the handle alive while any view exists.
@@ -768,6 +771,56 @@ int mms_marl_ppo_loss(int device, int64_t M, int32_t A, const float* mu, const f
                       int32_t use_huber, int32_t clipped_value, int32_t policy_masks, int32_t value_masks, int32_t use_norm,
                       const float* norm_mean, const float* norm_var, float* out, float* dmu, float* dstd, float* dvalue, float* row_logp,
                       void* workspace, int64_t* ws_bytes, void* hip_stream);
+
+/* ---- the parameter step: gradient-norm clip + Adam + polyak in two launches ---------------------------------------------------
+ * What every learner ends a minibatch with -- nn.utils.clip_grad_norm_, torch.optim.Adam.step() and, off-policy, the per-parameter
+ * polyak loop (algorithms/rl/sac/sac.py:325-349, rl/ppo/ppo.py's update, marl/mappo_trainer.py, marl/maddpg/module.py:280-292) -- for
+ * up to MMS_PARAM_MAX_TENSORS tensors per call.  numel, param, grad, exp_avg, exp_avg_sq, target: HOST arrays of `tensors` entries
+ * (element counts / device pointers, all f32); a pointer array may be NULL as a whole (= every entry NULL), and per tensor:
+ *   grad[t]    NULL: no Adam for this tensor (torch skips p.grad is None) and no share in the norm
+ *   param[t]   NULL with grad[t] given: the tensor takes part in the norm ONLY (the reference's SAC clips over
+ *              actor_critic.parameters() while it steps only the Q or only the pi parameters)
+ *   exp_avg[t], exp_avg_sq[t]: Adam's moments, both or neither; required where param[t] and grad[t] are given
+ *   target[t]  NULL: no polyak; given (it needs param[t]): averaged towards the NEW parameter, also where grad[t] is NULL
+ * Norm:   total = sqrt(sum over tensors with a grad of sum g^2); coef = min(1, max_norm / (total + 1e-6)), or 1 with max_norm <= 0:
+ *         clip_grad_norm_ with the L2 norm.  norm_out (a device float, or NULL: not stored) receives total, the UNCLIPPED norm, as
+ *         clip_grad_norm_ / get_gard_norm return it.  The gradients are NOT rewritten in place: grad is only read.
+ * Adam:   torch.optim.Adam's default rule (no amsgrad, no maximize), with g' = coef g + weight_decay p (weight_decay == 0: coef g):
+ *           m += (g' - m) (1 - beta1);   v = beta2 v + (1 - beta2) g'^2
+ *           p -= (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ *         step >= 1 is the step number AFTER this call, by value (a captured graph would replay the same number); the bias
+ *         corrections and 1 - beta are formed in double on the host and rounded once, as torch does with its Python scalars.
+ * Polyak: target = target polyak + (1 - polyak) p_new, rounded as the reference's two statements round --
+ *         fl(fl(t (float)polyak) + fl(c p)), c = (float)(1.0 - polyak), no fused multiply-add: bit-identical to
+ *         p_targ.mul_(polyak); p_targ.add_((1 - polyak) * p).
+ * The hyperparameters are doubles because the reference holds them as Python floats: (float)(1.0 - 0.995) is not 1.f - 0.995f.
+ * Arithmetic: IEEE fp32 division and square root, no contraction, no finite-math assumption -- a non-finite gradient reaches the
+ * norm and the parameters exactly as it does through torch (an inf makes total inf, coef 0 and that element NaN).  Device code
+ * flushes subnormals to zero (an exp_avg_sq below 1.2e-38 becomes 0).
+ * Two launches on hip_stream, no atomics, no grid-wide wait, no host synchronisation, no table copy (the tensor table travels in
+ * the kernel arguments).  Each tensor is cut into chunks of MMS_PARAM_CHUNK elements, one workgroup per chunk.  Launch 1 leaves one
+ * double per chunk of every tensor with a grad in `partials` (fixed order inside the workgroup); launch 2's workgroups each add ALL
+ * partials in one fixed order -- every workgroup forms the same coef -- and stream their chunk: read p, g, m, v, target, write p, m,
+ * v, target.  Results are bit-identical run to run; with max_norm <= 0 a tensor's results do not depend on the other tensors of
+ * the call.  Launch 1 is skipped when no norm is asked for (max_norm <= 0 and norm_out == NULL); partials may then be NULL.
+ * (The CPU build walks the same chunk tables; it adds a chunk's squares one after another where the device adds per thread and then
+ * across the workgroup, so the two builds' norms can differ in the last bit; the element rule is the same source.)
+ * partials: a device workspace of mms_param_step_partials(tensors, numel) doubles = sum over t of ceil(numel[t] / MMS_PARAM_CHUNK)
+ * (at least 1), 8-byte aligned, no initialisation needed.
+ * Any 4-byte-aligned pointer is taken (parameters are often views into larger storages): where a tensor's pointers share their
+ * offset within 16 bytes the chunk is streamed in 16-byte accesses behind a scalar head and in front of a scalar tail, otherwise
+ * element by element.  Elements past numel[t] are never touched.  The arrays of one call must not overlap one another.
+ * numel[t] == 0 and tensors == 0 succeed and touch nothing.  flags: reserved, must be 0.
+ * Non-zero with mms_last_error(NULL), and nothing written, for: tensors outside 0..MMS_PARAM_MAX_TENSORS, step < 1, a beta outside
+ * [0, 1), negative or non-finite lr / eps / weight_decay, flags != 0, negative numel, more than 2^31 - 1 chunks, exp_avg[t] without
+ * exp_avg_sq[t] or the reverse, param[t] and grad[t] without moments, target[t] without param[t], a pointer that is not 4-byte
+ * aligned, and a norm asked for with partials NULL or not 8-byte aligned. */
+#define MMS_PARAM_MAX_TENSORS 48
+#define MMS_PARAM_CHUNK 4096
+int64_t mms_param_step_partials(int32_t tensors, const int64_t* numel);
+int mms_param_step(int device, int32_t tensors, const int64_t* numel, float* const* param, const float* const* grad, float* const* exp_avg,
+                   float* const* exp_avg_sq, float* const* target, double lr, double beta1, double beta2, double eps, double weight_decay,
+                   int64_t step, double max_norm, double polyak, int32_t flags, double* partials, float* norm_out, void* hip_stream);
 
 const char* mms_last_error(mms_handle h);   /* h may be NULL: error of the last failed mms_create */
 int mms_abi_version(void);

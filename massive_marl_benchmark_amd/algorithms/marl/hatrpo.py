@@ -43,6 +43,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import _lib
+from ...optim import FusedAdam
 from .loss import HALF_LOG_2PI, _p, _workspace, marl_ppo_loss
 from .trainer import _base, get_grad_norm
 from .utils.valuenorm import ValueNorm
@@ -311,11 +312,14 @@ class HATRPO:
         value_loss = info["value_loss"]
         self.policy.critic_optimizer.zero_grad()
         objective.backward()                                           # mu and std carry no graph: value_loss_coef value_loss alone
-        if self._use_max_grad_norm:
-            critic_grad_norm = nn.utils.clip_grad_norm_(critic.parameters(), self.max_grad_norm)
+        if isinstance(self.policy.critic_optimizer, FusedAdam):        # clip + step as one mms_param_step (optim.py); None: the norm only
+            critic_grad_norm = self.policy.critic_optimizer.clip_and_step(self.max_grad_norm if self._use_max_grad_norm else None)
         else:
-            critic_grad_norm = get_grad_norm(critic.parameters())
-        self.policy.critic_optimizer.step()
+            if self._use_max_grad_norm:
+                critic_grad_norm = nn.utils.clip_grad_norm_(critic.parameters(), self.max_grad_norm)
+            else:
+                critic_grad_norm = get_grad_norm(critic.parameters())
+            self.policy.critic_optimizer.step()
 
         # actor update: the surrogate's gradient
         tail = (actions, old_logp, adv, factor, active_masks)

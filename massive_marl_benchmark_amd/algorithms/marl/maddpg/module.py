@@ -49,6 +49,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .... import _lib
+from ....optim import FusedAdam
 from .storage import round_up4
 
 _ACT_CODES = {nn.Identity: 0, nn.ELU: 1, nn.ReLU: 2, nn.Tanh: 3}
@@ -130,8 +131,10 @@ class MADDPG_policy:
         self.critic = Critic(self.share_obs_space, self.share_act_space, self.hidden_size, self.activation, self.device)
         self.actor_targ = deepcopy(self.actor)
         self.critic_targ = deepcopy(self.critic)
-        self.actor_optimizer = torch.optim.Adam(self.actor.pi.parameters(), lr=self.lr)
-        self.critic_optimizer = torch.optim.Adam(self.critic.q.parameters(), lr=self.lr)
+        # config "fused_step" (not the reference's; default False): FusedAdam (optim.py), whose clip_and_step MADDPG.ddpg_update then calls
+        Adam = FusedAdam if config.get("fused_step", False) else torch.optim.Adam
+        self.actor_optimizer = Adam(self.actor.pi.parameters(), lr=self.lr)
+        self.critic_optimizer = Adam(self.critic.q.parameters(), lr=self.lr)
 
     def get_actions(self, obs, deterministic=False):
         return self.actor.act(obs).detach()
@@ -441,6 +444,11 @@ class MADDPG():
         return -q_pi.mean()
 
     def ddpg_update(self, samples):
+        """With FusedAdam optimizers on every policy (config "fused_step"): per agent ONE clip_and_step for the critic and one for the
+        actor -- clip + Adam + that network's polyak average, one mms_param_step each -- in place of two clips, two steps and the polyak
+        loop.  The critic's target is then averaged right behind the critic's step instead of behind the actor's (nothing in between
+        reads it); agent id's target actor is refreshed behind its polyak as before."""
+        fused_step = all(isinstance(po.critic_optimizer, FusedAdam) and isinstance(po.actor_optimizer, FusedAdam) for po in self.policy)
         value_loss = []
         policy_loss = []
         tin = self._target_inputs(samples)              # every target actor once; None: the reference's per-agent evaluation
@@ -448,8 +456,11 @@ class MADDPG():
             self.policy[id].critic_optimizer.zero_grad()
             loss_q = self.cal_value_loss(samples, id, tin) if tin is not None else self.cal_value_loss(samples, id)
             loss_q.backward()
-            nn.utils.clip_grad_norm_(self.policy[id].critic.parameters(), self.max_grad_norm)
-            self.policy[id].critic_optimizer.step()
+            if fused_step:
+                self.policy[id].critic_optimizer.clip_and_step(self.max_grad_norm, targets=self.policy[id].critic_targ.q.parameters(), polyak=self.polyak)
+            else:
+                nn.utils.clip_grad_norm_(self.policy[id].critic.parameters(), self.max_grad_norm)
+                self.policy[id].critic_optimizer.step()
             value_loss.append(loss_q)
 
             for p in self.policy[id].critic.q.parameters():
@@ -457,19 +468,23 @@ class MADDPG():
             self.policy[id].actor_optimizer.zero_grad()
             loss_pi = self.cal_pi_loss(samples, id)
             loss_pi.backward()
-            nn.utils.clip_grad_norm_(self.policy[id].actor.parameters(), self.max_grad_norm)
-            self.policy[id].actor_optimizer.step()
+            if fused_step:
+                self.policy[id].actor_optimizer.clip_and_step(self.max_grad_norm, targets=self.policy[id].actor_targ.pi.parameters(), polyak=self.polyak)
+            else:
+                nn.utils.clip_grad_norm_(self.policy[id].actor.parameters(), self.max_grad_norm)
+                self.policy[id].actor_optimizer.step()
             policy_loss.append(loss_pi)
             for p in self.policy[id].critic.q.parameters():
                 p.requires_grad = True
 
-            with torch.no_grad():
-                for p, p_targ in zip(self.policy[id].critic.q.parameters(), self.policy[id].critic_targ.q.parameters()):
-                    p_targ.data.mul_(self.polyak)
-                    p_targ.data.add_((1 - self.polyak) * p.data)
-                for p, p_targ in zip(self.policy[id].actor.pi.parameters(), self.policy[id].actor_targ.pi.parameters()):
-                    p_targ.data.mul_(self.polyak)
-                    p_targ.data.add_((1 - self.polyak) * p.data)
+            if not fused_step:
+                with torch.no_grad():
+                    for p, p_targ in zip(self.policy[id].critic.q.parameters(), self.policy[id].critic_targ.q.parameters()):
+                        p_targ.data.mul_(self.polyak)
+                        p_targ.data.add_((1 - self.polyak) * p.data)
+                    for p, p_targ in zip(self.policy[id].actor.pi.parameters(), self.policy[id].actor_targ.pi.parameters()):
+                        p_targ.data.mul_(self.polyak)
+                        p_targ.data.add_((1 - self.polyak) * p.data)
             if tin is not None and id + 1 < self.num_agents:
                 self._refresh_target_action(tin, id)     # the agents behind see this target actor as updated (the reference's ordering)
         return value_loss, policy_loss

@@ -39,6 +39,7 @@ import math
 import torch
 import torch.nn as nn
 
+from ...optim import FusedAdam
 from .loss import marl_ppo_loss
 from .utils.valuenorm import ValueNorm
 
@@ -127,6 +128,13 @@ class _Trainer:
         self.policy.actor_optimizer.zero_grad()
         self.policy.critic_optimizer.zero_grad()
         objective.backward()
+        if isinstance(self.policy.actor_optimizer, FusedAdam) and isinstance(self.policy.critic_optimizer, FusedAdam):
+            # clip + step as one mms_param_step per network (optim.py; each optimizer holds its network's parameters, as the policies
+            # build them); max_norm None: the norm is still computed and reported, nothing is clipped
+            max_norm = self.max_grad_norm if self._use_max_grad_norm else None
+            actor_grad_norm = self.policy.actor_optimizer.clip_and_step(max_norm)
+            critic_grad_norm = self.policy.critic_optimizer.clip_and_step(max_norm)
+            return info["value_loss"], critic_grad_norm, info["policy_loss"], info["dist_entropy"], actor_grad_norm, info["ratio"]
         if self._use_max_grad_norm:
             actor_grad_norm = nn.utils.clip_grad_norm_(actor.parameters(), self.max_grad_norm)
             critic_grad_norm = nn.utils.clip_grad_norm_(critic.parameters(), self.max_grad_norm)

@@ -13,6 +13,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -376,6 +377,53 @@ MMS_API int mms_q_heads_backup_group(int device, int32_t groups, int64_t M, int3
             const float q = mms::q_value(s, b[g][0]);
             if (q_out && q_out[g]) q_out[g][row] = q;
             if (backup && backup[g]) backup[g][row] = mms::q_backup(reward[g][row], done[g][row], q, false, 0.f, gamma, 0.f);
+        }
+    }
+    return 0;
+}
+MMS_API int64_t mms_param_step_partials(int32_t tensors, const int64_t* numel) { return param_step_partials(tensors, numel); }
+// The HIP build's two passes over its chunk tables (param_step_args.h), a chunk per loop iteration: the partials are added in index
+// order, so the result does not depend on the number of threads.
+MMS_API int mms_param_step(int device, int32_t tensors, const int64_t* numel, float* const* param, const float* const* grad, float* const* exp_avg,
+                           float* const* exp_avg_sq, float* const* target, double lr, double beta1, double beta2, double eps, double weight_decay,
+                           int64_t step, double max_norm, double polyak, int32_t flags, double* partials, float* norm_out, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_param_step(tensors, numel, param, grad, exp_avg, exp_avg_sq, target, lr, beta1, beta2, eps, weight_decay, step, max_norm, polyak, flags,
+                                 partials, norm_out)))
+        return 1;
+    if (tensors == 0) return 0;
+    const mms::ParamArgs a = build_param_args(tensors, numel, param, grad, exp_avg, exp_avg_sq, target, lr, beta1, beta2, eps, weight_decay, step, max_norm,
+                                              polyak, partials, norm_out);
+    const int norm_chunks = a.norm_first[mms::kParamMaxTensors], step_chunks = a.step_first[mms::kParamMaxTensors];
+    float coef = 1.f;
+    if (a.use_norm) {
+#pragma omp parallel for schedule(static)
+        for (int k = 0; k < norm_chunks; k++) {
+            const int t = mms::param_chunk_tensor(a, false, k);
+            const int64_t lo = (int64_t)(k - a.norm_first[t]) * mms::kParamChunk, hi = std::min(a.numel[t], lo + mms::kParamChunk);
+            double s = 0.0;
+            for (int64_t e = lo; e < hi; e++) s += (double)a.g[t][e] * (double)a.g[t][e];
+            partials[k] = s;
+        }
+        double sum = 0.0;
+        for (int k = 0; k < norm_chunks; k++) sum += partials[k];
+        const float total = (float)sqrt(sum);
+        coef = mms::param_clip_coef(total, a.max_norm);
+        if (norm_out) *norm_out = total;
+    }
+#pragma omp parallel for schedule(static)
+    for (int k = 0; k < step_chunks; k++) {
+        const int t = mms::param_chunk_tensor(a, true, k);
+        const int64_t lo = (int64_t)(k - a.step_first[t]) * mms::kParamChunk, hi = std::min(a.numel[t], lo + mms::kParamChunk);
+        float *p = a.p[t], *m = a.m[t], *v = a.v[t], *tg = a.t[t];
+        const float* g = a.g[t];
+        for (int64_t e = lo; e < hi; e++) {
+            float P = p[e];
+            if (m) {
+                mms::param_adam(P, g[e], m[e], v[e], coef, a.c);
+                p[e] = P;
+            }
+            if (tg) tg[e] = mms::param_polyak(tg[e], P, a.c);
         }
     }
     return 0;

@@ -34,6 +34,7 @@ hipError_t launch_ppo_loss(int64_t, int, const float*, const float*, const float
 int64_t marl_loss_ws_bytes(int64_t, int);
 hipError_t launch_marl_ppo_loss(int64_t, int, const float*, const float*, const float*, const int64_t*, const mms_marl_loss_fields&, float, float, float,
                                 float, int, int, int, int, int, const float*, const float*, float*, float*, float*, float*, float*, void*, hipStream_t);
+hipError_t launch_param_step(const ParamArgs&, hipStream_t);
 struct MlpPlan;
 }  // namespace mms
 
@@ -385,6 +386,23 @@ __attribute__((visibility("default"))) int mms_q_heads_backup_group(int device, 
     }
     a.gamma = gamma; a.M = M; a.H = H;
     MMS_FREE(mms::launch_q_heads_backup_group(a, groups, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int64_t mms_param_step_partials(int32_t tensors, const int64_t* numel) { return param_step_partials(tensors, numel); }
+
+__attribute__((visibility("default"))) int mms_param_step(int device, int32_t tensors, const int64_t* numel, float* const* param, const float* const* grad,
+                                                          float* const* exp_avg, float* const* exp_avg_sq, float* const* target, double lr, double beta1,
+                                                          double beta2, double eps, double weight_decay, int64_t step, double max_norm, double polyak,
+                                                          int32_t flags, double* partials, float* norm_out, void* s) {
+    MMS_DEV(device)
+    if (refused(check_param_step(tensors, numel, param, grad, exp_avg, exp_avg_sq, target, lr, beta1, beta2, eps, weight_decay, step, max_norm, polyak, flags,
+                                 partials, norm_out)))
+        return 1;
+    if (tensors == 0) return 0;
+    const mms::ParamArgs a = build_param_args(tensors, numel, param, grad, exp_avg, exp_avg_sq, target, lr, beta1, beta2, eps, weight_decay, step, max_norm,
+                                              polyak, partials, norm_out);
+    MMS_FREE(mms::launch_param_step(a, (hipStream_t)s));
     return 0;
 }
 

@@ -5,6 +5,7 @@
 // what the HIP build refuses the CPU build refuses in the same words (the CPU build is the stand-in for the HIP boundary on
 // machines without a GPU).  What stays different between the builds on purpose is listed in DESIGN.md section 1.
 #pragma once
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "../../include/mms.h"
+#include "param_step_args.h"
 
 namespace mms {
 constexpr int kMlpMaxLayers = 8;
@@ -744,4 +746,88 @@ static inline std::string check_ln_mlp_jvp(int32_t blocks, int64_t M, const int3
         !all_set(blocks + 1, vg) || !all_set(blocks + 1, vt) || !all_set(blocks + 1, vw) || !all_set(blocks + 1, vc))
         return "mms_ln_mlp_jvp: null pointer (x, rmu, h[blocks], ln_g / ln_t / w / vg / vt / vw / vc[blocks+1])";
     return check_ln_mlp_workspace("mms_ln_mlp_jvp", workspace, ws_bytes, need);
+}
+
+// ---- mms_param_step ---------------------------------------------------------------------------------------------------------------
+
+static inline int64_t param_chunks(int64_t numel) { return (numel + mms::kParamChunk - 1) / mms::kParamChunk; }
+
+// mms_param_step_partials: the doubles of the `partials` workspace (0 for bad arguments; at least 1 otherwise)
+static inline int64_t param_step_partials(int32_t tensors, const int64_t* numel) {
+    if (tensors < 0 || tensors > MMS_PARAM_MAX_TENSORS || (tensors > 0 && !numel)) return 0;
+    int64_t n = 0;
+    for (int t = 0; t < tensors; t++) {
+        if (numel[t] < 0) return 0;
+        n += param_chunks(numel[t]);
+    }
+    return n > 0 ? n : 1;
+}
+
+// all checks before any work
+static inline std::string check_param_step(int32_t tensors, const int64_t* numel, float* const* param, const float* const* grad, float* const* exp_avg,
+                                           float* const* exp_avg_sq, float* const* target, double lr, double beta1, double beta2, double eps,
+                                           double weight_decay, int64_t step, double max_norm, double polyak, int32_t flags, const double* partials,
+                                           const float* norm_out) {
+    if (tensors < 0 || tensors > MMS_PARAM_MAX_TENSORS) return "mms_param_step: tensors must be 0.." + std::to_string(MMS_PARAM_MAX_TENSORS);
+    if (step < 1) return "mms_param_step: step must be >= 1 (the step number after this call)";
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return "mms_param_step: beta1 and beta2 must lie in [0, 1)";
+    if (!(lr >= 0.0 && lr <= DBL_MAX) || !(eps >= 0.0 && eps <= DBL_MAX) || !(weight_decay >= 0.0 && weight_decay <= DBL_MAX))
+        return "mms_param_step: lr, eps and weight_decay must be finite and not negative";
+    if (flags != 0) return "mms_param_step: flags is reserved and must be 0";
+    if (tensors > 0 && !numel) return "mms_param_step: numel required";
+    int64_t chunks = 0;
+    bool any_target = false;
+    for (int t = 0; t < tensors; t++) {
+        const float* p = param ? param[t] : nullptr;
+        const float* g = grad ? grad[t] : nullptr;
+        const float* m = exp_avg ? exp_avg[t] : nullptr;
+        const float* v = exp_avg_sq ? exp_avg_sq[t] : nullptr;
+        const float* tg = target ? target[t] : nullptr;
+        if (numel[t] < 0) return "mms_param_step: negative numel";
+        chunks += param_chunks(numel[t]);
+        if (chunks > 0x7fffffff) return "mms_param_step: more than 2^31 - 1 chunks";
+        if ((m != nullptr) != (v != nullptr)) return "mms_param_step: exp_avg and exp_avg_sq go together (both, or both NULL)";
+        if (p && g && !m) return "mms_param_step: a tensor with param and grad needs its moments (exp_avg, exp_avg_sq)";
+        if (tg && !p) return "mms_param_step: a target needs its param";
+        if ((addr(p) | addr(g) | addr(m) | addr(v) | addr(tg)) & 3) return "mms_param_step: pointers must be 4-byte aligned";
+        any_target = any_target || tg;
+    }
+    if (any_target && !(polyak == polyak)) return "mms_param_step: polyak is NaN";
+    if (max_norm > 0.0 || norm_out) {
+        if (!partials) return "mms_param_step: a norm (max_norm > 0 or norm_out) needs the partials workspace";
+        if (addr(partials) & 7) return "mms_param_step: partials must be 8-byte aligned";
+    }
+    if (addr(norm_out) & 3) return "mms_param_step: norm_out must be 4-byte aligned";
+    return {};
+}
+
+// The argument block of a checked call: the pointers (NULL arrays resolved, moments cleared where there is no Adam step), the two
+// chunk tables and the scalars.  norm_first / step_first [tensors] are the launches' chunk counts.
+static inline mms::ParamArgs build_param_args(int32_t tensors, const int64_t* numel, float* const* param, const float* const* grad, float* const* exp_avg,
+                                              float* const* exp_avg_sq, float* const* target, double lr, double beta1, double beta2, double eps,
+                                              double weight_decay, int64_t step, double max_norm, double polyak, double* partials, float* norm_out) {
+    mms::ParamArgs a = {};
+    a.tensors = tensors;
+    a.use_norm = (max_norm > 0.0 || norm_out) ? 1 : 0;
+    int32_t nf = 0, sf = 0;
+    for (int t = 0; t < tensors; t++) {
+        a.p[t] = param ? param[t] : nullptr;
+        a.g[t] = grad ? grad[t] : nullptr;
+        const bool adam = a.p[t] && a.g[t];
+        a.m[t] = adam ? exp_avg[t] : nullptr;
+        a.v[t] = adam ? exp_avg_sq[t] : nullptr;
+        a.t[t] = target ? target[t] : nullptr;
+        a.numel[t] = numel[t];
+        a.norm_first[t] = nf;
+        a.step_first[t] = sf;
+        const int32_t chunks = (int32_t)param_chunks(numel[t]);
+        if (a.use_norm && a.g[t]) nf += chunks;
+        if (a.p[t] && (adam || a.t[t])) sf += chunks;
+    }
+    for (int t = tensors; t <= mms::kParamMaxTensors; t++) { a.norm_first[t] = nf; a.step_first[t] = sf; }
+    a.c = mms::param_coef(lr, beta1, beta2, eps, weight_decay, step, polyak);
+    a.max_norm = (float)max_norm;
+    a.partials = partials;
+    a.norm_out = norm_out;
+    return a;
 }
