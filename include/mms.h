@@ -38,6 +38,8 @@
  *     (algorithms/marl/actor_critic.py:43-69, 137-155; runner.py:186-216)  mms_row_stats_group, mms_marl_heads_act
  *   SquashedGaussianMLPActor heads + rsample + log-probability          mms_sac_heads_act
  *     (algorithms/rl/sac/module.py:23-61; sac.py:166, 374-376)
+ *   autograd's backward of that head's epilogue in compute_loss_pi      mms_sac_heads_grad
+ *     (sac.py:392-403)
  *   MLPQFunction last layer + min + Bellman backup (Q target)           mms_q_heads_backup
  *     (rl/sac/sac.py:379-382; td3/td3.py:370-373; ddpg/ddpg.py:368-369)
  *   MLPQFunction's torch.cat([obs, act]) in front of the two-plane      mms_split_planes16_cat
@@ -358,6 +360,35 @@ int mms_sac_heads_act(int device, const float* hidden, int32_t H,
                       float* actions_out, float* act_slot, float* logp_slot,
                       float* u_slot, float* mu_slot, float* log_std_slot,
                       int64_t N, int32_t A, void* hip_stream);
+
+/* The backward of that head's epilogue (csrc/sac_grad_kernels.hip): the gradient of SAC's policy loss (compute_loss_pi, sac.py:392-403)
+ * with respect to the OUTPUTS of mu_layer and log_std_layer (the latter before its clamp) and the two bias gradients, from what a
+ * mms_sac_heads_act call stored -- what torch autograd evaluates as the mirror image of about fifteen element-wise launches.  The
+ * three products behind it (grad_hidden = dy @ [W_mu; W_ls], [gW_mu; gW_ls] = dy^T @ hidden) are left to the caller's GEMM library.
+ *   u, mu, log_std [N,A]: the forward's u_slot, mu_slot and log_std_slot (clamped);  grad_action [N,A] or NULL, grad_logp [N] or NULL:
+ *   d loss / d (action, logp), at least one of them.  Per element, with L = act_limit, g_a = grad_action_ij or 0, g_l = grad_logp_i or 0:
+ *     t = tanh(u);  s = 1 - t^2
+ *     G    = L s g_a + g_l 2 t s / (s + epsilon)                 d/du of L tanh(u) and of -log(1 - tanh(u)^2 + epsilon)
+ *     dmu  = G
+ *     dls  = (-20 < log_std && log_std < 2) ? G (u - mu) - g_l : 0    du/dlog_std = exp(log_std) z = u - mu; the -log_std term of logp
+ *   dy [N, 2A]: dmu in columns [0, A), dls in [A, 2A);  dbias [2A] or NULL (not computed): dbias_c = sum_i dy[i, c].
+ * There is no `deterministic` flag: a deterministic forward stores u == mu, so G (u - mu) = 0.  The clamp mask is read from the stored,
+ * clamped log_std, because the forward clamps exactly to the bound (one measure-zero difference from torch.clamp's gradient: where the
+ * layer's raw output EQUALS a bound torch passes the gradient, this gives none).
+ * A row of dy depends on that row and the scalars alone, not on N or on where the row sits.  dbias: per-workgroup partials in double
+ * in the workspace, then one pass that adds them in a fixed order and rounds once -- no atomics, bit-identical run to run.  At most
+ * two launches on hip_stream, no host synchronisation.  16-byte accesses where u, mu, log_std, grad_action and dy are 16-byte aligned
+ * (any A), element by element otherwise, with the same results.
+ * workspace / ws_bytes: mms_ppo_loss's convention (NULL stores the bytes needed and returns 0 -- nothing else is read; 256-byte aligned;
+ * a smaller one is an error; the CPU build needs 0 and runs on any aligned non-NULL workspace).  The workspace needs no initialisation.
+ * 0 <= N <= 0x7fffffff (N == 0 succeeds and writes nothing), 1 <= A <= 128.  Inputs are taken to be finite.  Bad arguments -- both
+ * gradients NULL, u, mu, log_std or dy NULL, A or N out of range, a small or misaligned workspace -- return non-zero with
+ * mms_last_error(NULL) and write nothing. */
+int mms_sac_heads_grad(int device, int64_t N, int32_t A, float act_limit, float epsilon,
+                       const float* u, const float* mu, const float* log_std,
+                       const float* grad_action, const float* grad_logp,
+                       float* dy, float* dbias,
+                       void* workspace, int64_t* ws_bytes, void* hip_stream);
 
 /* The tail of the off-policy Q target in ONE launch: the last layer of one or two critics (MLPQFunction's Linear(H, 1),
  * algorithms/rl/{ddpg,td3,sac}/module.py `q.q.<last>`), the min of the two and the Bellman backup -- what sac.py:379-382,

@@ -24,6 +24,7 @@
 #include "../q_lane.h"
 #include "../maddpg_lane.h"
 #include "../sac_lane.h"
+#include "../sac_grad_lane.h"
 #include "lane_step.h"
 
 #define MMS_API extern "C" __attribute__((visibility("default")))
@@ -379,6 +380,44 @@ MMS_API int mms_q_heads_backup_group(int device, int32_t groups, int64_t M, int3
             if (backup && backup[g]) backup[g][row] = mms::q_backup(reward[g][row], done[g][row], q, false, 0.f, gamma, 0.f);
         }
     }
+    return 0;
+}
+// The backward of the head's epilogue (include/mms.h: mms_sac_heads_grad) over ../sac_grad_lane.h.  Rows in at most 1024 chunks of at
+// least 256 (OpenMP over chunks): a chunk's column sums in double over ascending rows, the chunks added in ascending order and rounded
+// once -- the result does not depend on the number of threads.  No workspace.
+MMS_API int mms_sac_heads_grad(int device, int64_t N, int32_t A, float act_limit, float epsilon, const float* u, const float* mu, const float* log_std,
+                               const float* grad_action, const float* grad_logp, float* dy, float* dbias, void* workspace, int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_sac_heads_grad(N, A, u, mu, log_std, grad_action, grad_logp, dy, workspace, ws_bytes, 0))) return 1;
+    if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query
+    if (N == 0) return 0;
+    const int C = 2 * A;
+    int64_t chunk = (N + 1023) / 1024;
+    chunk = chunk < 256 ? 256 : chunk;
+    const int64_t nchunks = (N + chunk - 1) / chunk;
+    std::vector<double> part(dbias ? (size_t)nchunks * C : 0, 0.0);
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < nchunks; c++) {
+        double* p = dbias ? part.data() + c * C : nullptr;
+        const int64_t end = (c + 1) * chunk < N ? (c + 1) * chunk : N;
+        for (int64_t row = c * chunk; row < end; row++) {
+            const float g_l = grad_logp ? grad_logp[row] : 0.f;
+            for (int j = 0; j < A; j++) {
+                const int64_t e = row * A + j;
+                float dmu, dls;
+                mms::sac_grad_one(u[e], mu[e], log_std[e], grad_action ? grad_action[e] : 0.f, g_l, act_limit, epsilon, dmu, dls);
+                dy[row * C + j] = dmu;
+                dy[row * C + A + j] = dls;
+                if (p) { p[j] += (double)dmu; p[A + j] += (double)dls; }
+            }
+        }
+    }
+    if (dbias)
+        for (int q = 0; q < C; q++) {
+            double s = 0.0;
+            for (int64_t c = 0; c < nchunks; c++) s += part[c * C + q];
+            dbias[q] = (float)s;
+        }
     return 0;
 }
 MMS_API int64_t mms_param_step_partials(int32_t tensors, const int64_t* numel) { return param_step_partials(tensors, numel); }

@@ -35,6 +35,9 @@ int64_t marl_loss_ws_bytes(int64_t, int);
 hipError_t launch_marl_ppo_loss(int64_t, int, const float*, const float*, const float*, const int64_t*, const mms_marl_loss_fields&, float, float, float,
                                 float, int, int, int, int, int, const float*, const float*, float*, float*, float*, float*, float*, void*, hipStream_t);
 hipError_t launch_param_step(const ParamArgs&, hipStream_t);
+int64_t sac_grad_ws_bytes(int64_t, int);
+hipError_t launch_sac_heads_grad(int64_t, int, float, float, const float*, const float*, const float*, const float*, const float*, float*, float*, void*,
+                                 hipStream_t);
 struct MlpPlan;
 }  // namespace mms
 
@@ -336,6 +339,20 @@ __attribute__((visibility("default"))) int mms_sac_heads_act(int device, const f
     if (refused(check_sac_heads_act(hidden, H, mu_weight, mu_bias, ls_weight, ls_bias, deterministic, counters, N, A))) return 1;
     MMS_FREE(mms::launch_sac_head_act(hidden, H, mu_weight, mu_bias, ls_weight, ls_bias, act_limit, epsilon, deterministic, seed, counters, row_offset,
                                       actions_out, act_slot, logp_slot, u_slot, mu_slot, log_std_slot, N, A, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_sac_heads_grad(int device, int64_t N, int32_t A, float act_limit, float epsilon, const float* u,
+                                                              const float* mu, const float* log_std, const float* grad_action,
+                                                              const float* grad_logp, float* dy, float* dbias, void* workspace, int64_t* ws_bytes,
+                                                              void* s) {
+    MMS_DEV(device)
+    const bool shapes = N >= 0 && N <= 0x7fffffff && A >= 1 && A <= 128;
+    const int64_t need = shapes ? mms::sac_grad_ws_bytes(N, A) : 0;
+    if (refused(check_sac_heads_grad(N, A, u, mu, log_std, grad_action, grad_logp, dy, workspace, ws_bytes, need))) return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }                // the size query
+    if (N == 0) return 0;
+    MMS_FREE(mms::launch_sac_heads_grad(N, A, act_limit, epsilon, u, mu, log_std, grad_action, grad_logp, dy, dbias, workspace, (hipStream_t)s));
     return 0;
 }
 

@@ -356,6 +356,22 @@ static inline std::string check_sac_heads_act(const float* hidden, int32_t H, co
     return {};
 }
 
+// mms_sac_heads_grad: the shapes, then (workspace NULL is the size query: nothing else is read; N == 0: nothing to do, nothing else
+// is read) the operands and the workspace against `need`, the bytes this build's plan asks for (the CPU build's: 0).
+static inline std::string check_sac_heads_grad(int64_t N, int32_t A, const float* u, const float* mu, const float* log_std, const float* grad_action,
+                                               const float* grad_logp, const float* dy, const void* workspace, const int64_t* ws_bytes,
+                                               int64_t need) {
+    if (!ws_bytes) return "mms_sac_heads_grad: ws_bytes required";
+    if (N < 0 || N > 0x7fffffff) return "mms_sac_heads_grad: N must be in 0..2147483647";
+    if (A < 1 || A > 128) return "mms_sac_heads_grad: A must be in 1..128";
+    if (!workspace || N == 0) return {};
+    if (!u || !mu || !log_std || !dy) return "mms_sac_heads_grad: null pointer (u, mu, log_std and dy are required)";
+    if (!grad_action && !grad_logp) return "mms_sac_heads_grad: no incoming gradient (grad_action and grad_logp both NULL)";
+    if (*ws_bytes < need) return "mms_sac_heads_grad: workspace too small (" + std::to_string(*ws_bytes) + " bytes, needs " + std::to_string(need) + ")";
+    if (addr(workspace) & 255) return "mms_sac_heads_grad: workspace must be 256-byte aligned";
+    return {};
+}
+
 // all checks before any work; G is 2 when the second network is given
 static inline std::string check_q_heads_backup(int64_t M, int32_t H, const float* h0, const float* w0, const float* b0, const float* q0_out,
                                                const float* h1, const float* w1, const float* b1, const float* q1_out, const float* reward,
