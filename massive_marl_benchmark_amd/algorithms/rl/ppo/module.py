@@ -576,6 +576,8 @@ class ActorCritic(nn.Module):
         if self._counters is None or self._counters.numel() != N or self._counters.device != dev:
             self._counters = torch.zeros(N, dtype=torch.int64, device=dev)
         storage, actions_out = self._bound if self._bound is not None else (None, None)
+        if storage is not None and storage.step >= storage.num_transitions_per_env:
+            storage = None        # the bootstrap `act` behind a full rollout (ppo.py:159) has no slot: new tensors, as without a binding
         # a bound rollout slot with both heads in the kernel (the rollout's hot path): the launch arguments of slot s are built once
         ckey = None
         if storage is not None and mean is None and value is None and hidden.is_contiguous() and (vhidden is None or vhidden.is_contiguous()):

@@ -1,7 +1,11 @@
 """MultiVecTask / MultiVecTaskPython (agents/tasks/agent_base/multi_vec_task.py:20-175): the MARL wrapper.
 The reference hard-codes 10 agents x 38 + 8 shared = 388; here the numbers come from the task (same
-defaults).  obs_all is produced by one HIP kernel; state_all / reward_all / done_all are stride-0
-expansions of the engine buffers (the reference materialises ten copies)."""
+defaults).  obs_all is produced by one HIP kernel.
+
+Freshness (tests/test_dropin_contract.py): every tensor `step()` and `reset()` return has storage of its own, as the reference's
+`torch.stack` results have -- its MADDPG runner holds `obs` / `share_obs` across `envs.step` and inserts them afterwards
+(marl/maddpg/runner.py:107-150).  obs_all is written by the kernel into a new tensor per call; state_all is a stride-0 expansion of
+one fresh [N, obs_dim] copy (the reference materialises ten); reward_all / done_all are new [N, A, 1] / [N, A] tensors."""
 import ctypes
 
 import numpy as np
@@ -34,8 +38,6 @@ class MultiVecTask:
                                         for _ in range(self.num_agents)]
         self.act_space = tuple([spaces.Box(low=np.ones(self.num_actions) * -clip_actions, high=np.ones(self.num_actions) * clip_actions)
                                 for _ in range(self.num_agents)])
-        self._obs_all = torch.empty((self.num_environments, self.num_agents, self.num_observations), dtype=torch.float32,
-                                    device=e.device)
 
     def step(self, actions):
         raise NotImplementedError
@@ -72,13 +74,18 @@ class MultiVecTaskPython(MultiVecTask):
         return torch.clamp(self.task.states_buf, -self.clip_obs, self.clip_obs).to(self.rl_device)
 
     def _views(self):
+        """(obs_all, state_all) of the step just taken, both in storage that no later engine call writes: the slicing kernel fills a
+        newly allocated [N, A, per + shared] tensor, and state_all is a stride-0 `expand` over ONE fresh [N, obs_dim] copy of the
+        clamped row (the reference materialises N x A x obs_dim, multi_vec_task.py:139; no caller of either tree writes it, and an
+        in-place write into an expanded tensor is refused by torch)."""
         t, e = self.task, self.task.engine
         L, idx, stream = _lib.for_device(e.device)
-        _lib.check(L.mms_marl_views(idx, ctypes.c_void_p(t.obs_buf_clipped.contiguous().data_ptr()),
-                                    ctypes.c_void_p(self._obs_all.data_ptr()), self.num_environments, self.num_agents,
-                                    self.num_ant_obs, self.shared_obs, stream), None, "mms_marl_views", L)
-        state_all = t.obs_buf_clipped.unsqueeze(1).expand(-1, self.num_agents, -1)
-        return self._obs_all.to(self.rl_device), state_all.to(self.rl_device)
+        clipped = t.obs_buf_clipped.contiguous()
+        obs_all = torch.empty((self.num_environments, self.num_agents, self.num_observations), dtype=torch.float32, device=e.device)
+        _lib.check(L.mms_marl_views(idx, ctypes.c_void_p(clipped.data_ptr()), ctypes.c_void_p(obs_all.data_ptr()), self.num_environments,
+                                    self.num_agents, self.num_ant_obs, self.shared_obs, stream), None, "mms_marl_views", L)
+        state_all = clipped.to(self.rl_device, copy=True).unsqueeze(1).expand(-1, self.num_agents, -1)
+        return obs_all.to(self.rl_device), state_all
 
     def step(self, actions):
         if isinstance(actions, (list, tuple)):                      # multi_vec_task.py:96-99
@@ -86,8 +93,10 @@ class MultiVecTaskPython(MultiVecTask):
         t = self.task
         t.step(actions)
         obs_all, state_all = self._views()
-        reward_all = t.rew_buf.view(-1, 1, 1).expand(-1, self.num_agents, 1).to(self.rl_device)
-        done_all = t.reset_buf.view(-1, 1).expand(-1, self.num_agents).to(self.rl_device)
+        # new [N, A, 1] / [N, A] tensors, as the reference's torch.stack makes them (multi_vec_task.py:138-141)
+        # (the clone of a stride-0 expansion is a dense tensor: one copy kernel each)
+        reward_all = t.rew_buf.to(self.rl_device).view(-1, 1, 1).expand(-1, self.num_agents, 1).clone()
+        done_all = t.reset_buf.to(self.rl_device).view(-1, 1).expand(-1, self.num_agents).clone()
         info_all = torch.zeros((self.num_agents, 0))
         return obs_all, state_all, reward_all, done_all, info_all, None
 

@@ -1,6 +1,12 @@
 """VecTask / VecTaskPython (agents/tasks/agent_base/vec_task.py:17-139): the OUTER drop-in boundary that
 agents/algorithms/rl/* call.  Same constructor, properties and return values; the clamps of
-vec_task.py:127,131 are done inside the step kernel (actions on load, observations into `obs_clipped`)."""
+vec_task.py:127,131 are done inside the step kernel (actions on load, observations into `obs_clipped`).
+
+Freshness (tests/test_dropin_contract.py): the observation `step()` and `reset()` return is a NEW tensor on every call, as the
+reference's `torch.clamp(...)` result is -- the learners hold `current_obs` across `vec_env.step` and store it afterwards
+(ppo.py:132-138, ddpg.py:154-160), and write into it (`current_obs.copy_(next_obs)`): no later engine call writes it, and a write
+into it reaches no engine buffer.  `rew` / `done` are `.to(rl_device)` of the task's buffers as in vec_task.py:131: on the engine's
+own device they ALIAS engine memory that the next step overwrites (the learners consume them before it)."""
 import numpy as np
 import torch
 
@@ -47,13 +53,17 @@ class VecTaskPython(VecTask):
     def get_state(self):
         return torch.clamp(self.task.states_buf, -self.clip_obs, self.clip_obs).to(self.rl_device)
 
+    def _fresh_obs(self):
+        """The clamped observation row in storage of its own (one [N, obs] copy: the engine keeps writing `obs_clipped` in place)."""
+        return self.task.obs_buf_clipped.to(self.rl_device, copy=True)
+
     def step(self, actions):
         self.task.step(actions)                                   # clamp to +-clip_actions happens in the kernel
         t = self.task
-        return (t.obs_buf_clipped.to(self.rl_device), t.rew_buf.to(self.rl_device), t.reset_buf.to(self.rl_device), t.extras)
+        return (self._fresh_obs(), t.rew_buf.to(self.rl_device), t.reset_buf.to(self.rl_device), t.extras)
 
     def reset(self):
         actions = 0.01 * (1 - 2 * torch.rand([self.task.num_envs, self.task.num_actions], dtype=torch.float32,
                                               device=self.rl_device))   # vec_task.py:134
         self.task.step(actions)
-        return self.task.obs_buf_clipped.to(self.rl_device)
+        return self._fresh_obs()

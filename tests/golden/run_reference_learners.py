@@ -19,6 +19,11 @@ Runs only where the reference tree exists.  Nothing of the reference is copied: 
 name-only stand-ins of tests/golden/_isaacgym_stub for `gym` / `isaacgym` and a name-only `torch.utils.tensorboard.SummaryWriter`
 (tensorboard is not installed).  Writes tests/golden/reference_learners_dropin.log.
 
+The single-agent learners run under a recorder (StoredIsSeen) that leaves them untouched and checks DATA, not only that the run ends:
+every row `storage.add_transitions` wrote is the observation `actor_critic.act` was given at that step, exactly, for every step of
+`PPO.run`, `DDPG.run` and `TD3.run`; each of these six entries carries the count, as do the two of run_reference_trpo.py: eight single-agent
+entries in all (tests/test_learners_dropin_log.py and tests/test_trpo_dropin_log.py read them).
+
     python tests/golden/run_reference_learners.py
 """
 import contextlib
@@ -79,6 +84,51 @@ def load(modname, relpath):
     return mod
 
 
+class StoredIsSeen:
+    """A recorder around an unmodified single-agent learner: `actor_critic.act` and `storage.add_transitions` are wrapped on the
+    INSTANCES (the learner's code and classes stay as they are), and after every add_transitions the row it wrote is compared,
+    exactly, with a clone of the observation the last `act` was given -- the contract of tests/test_dropin_contract.py, here for
+    every step of the reference's own `run`.  Off-policy: next_observations[k] is the tensor `step` returned and differs from
+    observations[k]; on-policy: the stored row differs from the observation the NEXT `act` is given."""
+
+    def __init__(self, learner, off_policy):
+        self.steps = self.same = self.differ = self.differ_of = 0
+        self.seen = self.pending = None
+        ac, st = learner.actor_critic, learner.storage
+        real_act, real_add = ac.act, st.add_transitions
+
+        def act(obs, *a, **k):
+            seen = obs.detach().clone()
+            if self.pending is not None:
+                self.differ_of += 1
+                self.differ += int(not torch.equal(self.pending, seen.view(self.pending.shape)))
+                self.pending = None
+            self.seen = seen
+            return real_act(obs, *a, **k)
+
+        def add(*a, **k):
+            nxt = a[4].detach().clone() if off_policy else None
+            real_add(*a, **k)
+            row = st.step - 1
+            stored = st.observations[row]
+            ok = torch.equal(stored, self.seen.view(stored.shape))
+            if off_policy:
+                ok = ok and torch.equal(st.next_observations[row], nxt.view(stored.shape))
+                self.differ_of += 1
+                self.differ += int(not torch.equal(stored, st.next_observations[row]))
+            else:
+                self.pending = stored.clone()
+            self.steps += 1
+            self.same += int(ok)
+        ac.act, st.add_transitions = act, add
+
+    def line(self):
+        assert self.steps > 0 and self.same == self.steps and self.differ_of >= self.steps - 1 and self.differ == self.differ_of, \
+            (self.same, self.steps, self.differ, self.differ_of)
+        return "    stored observations == observations acted on: %d/%d steps; observations != next_observations: %d/%d" % (
+            self.same, self.steps, self.differ, self.differ_of)
+
+
 def run_ppo(tmp):
     from massive_marl_benchmark_amd.model import default_cfg
     from massive_marl_benchmark_amd.tasks.agent_base.vec_task import VecTaskPython
@@ -104,6 +154,7 @@ def run_ppo(tmp):
         os.makedirs(os.path.join(tmp, "ppo"), exist_ok=True)            # (the real SummaryWriter creates its log_dir; PPO.save writes there)
         learner = ppo.PPO(vec_env=env, cfg_train=cfg_train, device="cpu", sampler=cfg_train["learn"].get("sampler", "sequential"),
                           log_dir=os.path.join(tmp, "ppo"), is_testing=False, print_log=True, apply_reset=False, asymmetric=False)
+        rec = StoredIsSeen(learner, off_policy=False)
         buf = io.StringIO()
         with contextlib.redirect_stdout(buf):
             learner.run(num_learning_iterations=2, log_interval=1)
@@ -112,6 +163,7 @@ def run_ppo(tmp):
         assert "Learning iteration 1/2" in out, out[-2000:]
         assert bool(torch.isfinite(learner.storage.returns).all()) and bool(torch.isfinite(task.obs_buf).all())
         say("PPO.run (reference agents/algorithms/rl/ppo/ppo.py, unmodified) x 2 iterations on OneAnt 64 envs, CPU build, %s: ok" % label)
+        say(rec.line())
         for l in lines[-4:]:
             say("    " + " ".join(l.split()))
         task.engine.close()
@@ -189,6 +241,7 @@ def run_offpolicy(tmp, algo):
         os.makedirs(os.path.join(tmp, algo), exist_ok=True)
         learner = cls(vec_env=env, cfg_train=cfg_train, device="cpu", sampler="random", log_dir=os.path.join(tmp, algo),
                       is_testing=False, print_log=True, apply_reset=False, asymmetric=False)
+        rec = StoredIsSeen(learner, off_policy=True)
         buf = io.StringIO()
         with contextlib.redirect_stdout(buf):
             learner.run(num_learning_iterations=3, log_interval=1)
@@ -198,6 +251,7 @@ def run_offpolicy(tmp, algo):
         assert all(bool(torch.isfinite(p).all()) for p in learner.actor_critic.parameters())
         say("%s.run (reference agents/algorithms/rl/%s/%s.py, unmodified) x 3 iterations on MultiIngenuity 64 envs, CPU build, %s: ok"
             % (algo.upper(), algo, algo, label))
+        say(rec.line())
         lines = [l.strip() for l in out.splitlines() if any(k in l for k in ("Learning iteration", "Value function loss", "Surrogate loss", "Mean reward/step"))]
         for l in lines[-4:]:
             say("    " + " ".join(l.split()))

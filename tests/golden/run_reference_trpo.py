@@ -4,7 +4,8 @@ imported in place and left unmodified, driven over this build's VecTaskPython on
 2 iterations on OneAnt with 64 envs -- once with the reference's own RolloutStorage / ActorCritic, once with this build's
 (massive_marl_benchmark_amd.algorithms.rl.trpo) patched into the reference module, with fused_grad=True so that the actor's gradient
 and every kl_hessian_times_vector go through mms_mlp_grad / mms_mlp_grad_rop.  Each run logs its losses and the number of
-line_search calls (noptepochs x nminibatches per iteration) and of failed line searches; tests/test_trpo_dropin_log.py checks the log.
+line_search calls (noptepochs x nminibatches per iteration) and of failed line searches, and -- under run_reference_learners.py's
+StoredIsSeen recorder -- for how many steps the stored observation is the one `act` was given; tests/test_trpo_dropin_log.py checks the log.
 
 Runs only where the reference tree exists; the import plumbing (name-only stubs, nothing copied) is run_reference_learners.py's.
 Writes tests/golden/reference_trpo_dropin.log.
@@ -64,6 +65,7 @@ def run_trpo(tmp):
         learner.line_search = counted
         fused = getattr(learner.actor_critic, "_grad_path_qualifies", None)
         fused = bool(fused and fused(torch.zeros(8, env.observation_space.shape[0])))
+        rec = rrl.StoredIsSeen(learner, off_policy=False)
         buf = io.StringIO()
         with contextlib.redirect_stdout(buf):
             learner.run(num_learning_iterations=2, log_interval=1)
@@ -74,6 +76,7 @@ def run_trpo(tmp):
         rrl.say("TRPO.run (reference agents/algorithms/rl/trpo/trpo.py, unmodified) x 2 iterations on OneAnt 64 envs, CPU build, %s: ok" % label)
         rrl.say("    line_search calls: %d, failed: %d, actor through mms_mlp_grad / mms_mlp_grad_rop: %s, losses finite: %s"
                 % (calls[0], out.count("linear search fail"), fused, all(map(lambda v: v == v and abs(v) != float("inf"), losses))))
+        rrl.say(rec.line())
         for l in [l.strip() for l in out.splitlines() if any(k in l for k in ("Learning iteration", "Value function loss", "Surrogate loss"))][-3:]:
             rrl.say("    " + " ".join(l.split()))
         task.engine.close()

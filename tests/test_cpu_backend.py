@@ -164,7 +164,7 @@ def test_one_ant_cpu_pipeline_ppo_plumbing():
             a, logp, v, mu, sigma = ac.act(obs, states)
             nxt, rew, done, info = env.step(a)
             st.add_transitions(obs, states, a, rew, done, v, logp, mu, sigma)
-            obs = nxt.clone()
+            obs.copy_(nxt)                       # ppo.py:138, as the reference writes it (the contract: test_dropin_contract.py)
             resets += int(done.sum())
         _, _, last, _, _ = ac.act(obs, states)
         st.compute_returns(last, 0.96, 0.95)

@@ -4,6 +4,8 @@ mms_mlp_grad / mms_mlp_grad_rop -- completed, with finite losses and the same nu
 import os
 import re
 
+from test_learners_dropin_log import check_contract_line
+
 LOG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_trpo_dropin.log")
 
 
@@ -21,5 +23,6 @@ def test_reference_trpo_dropin_log():
         losses = [float(x) for x in re.findall(r"(?:Value function|Surrogate) loss: (\S+)", r)]
         assert len(losses) == 2 and all(abs(x) < 1e30 for x in losses), r
         assert m.group(4) == "True"
+        check_contract_line(r, 2 * 8)                            # every stored observation is the one `act` was given: 2 iterations x nsteps 8
     assert stats[0][0] == stats[1][0] == str(2 * 5 * 4)          # 2 iterations x noptepochs 5 x nminibatches 4 (cfg/trpo)
     assert stats[0][2] == "False" and stats[1][2] == "True"      # the second run's actor took the kernels

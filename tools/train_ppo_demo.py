@@ -84,7 +84,7 @@ def train(args, log=print, on_minibatch=None):
         opt = torch.optim.Adam(ac.parameters(), lr=args.lr)
     lr = args.lr
     states = torch.zeros(N, 0, device=dev)
-    obs = env.reset().clone()
+    obs = env.reset()                                                   # a tensor of its own (ppo.py:100): the loop below writes into it
     ep_ret = torch.zeros(N, device=dev)
     ep_len = torch.zeros(N, device=dev)
     done_ret, done_len, done_cnt = 0.0, 0.0, 0
