@@ -36,6 +36,8 @@
  *                                                                        mms_marl_heads_finish
  *   Actor / Critic forward of every MAPPO / HAPPO agent                  mms_linear_group_act, mms_layernorm_group,
  *     (algorithms/marl/actor_critic.py:43-69, 137-155; runner.py:186-216)  mms_row_stats_group, mms_marl_heads_act
+ *   RNNLayer's single-step branch of every recurrent agent              mms_gru_group
+ *     (algorithms/utils/rnn.py:25-29; marl/actor_critic.py:64-65, 164-165)
  *   SquashedGaussianMLPActor heads + rsample + log-probability          mms_sac_heads_act
  *     (algorithms/rl/sac/module.py:23-61; sac.py:166, 374-376)
  *   autograd's backward of that head's epilogue in compute_loss_pi      mms_sac_heads_grad
@@ -431,7 +433,8 @@ int mms_linear2_act(int device, int64_t M, int32_t N, int32_t K, const float* x0
  * utils/distributions.py:94-117) = Linear mean head, std = sigmoid(log_std / std_x_coef) * std_y_coef, sample, summed
  * log-probability; v_out = Linear(hidden, 1).  The three operators below run one such stage for up to MMS_MAX_GROUPS networks
  * of the same shape at once (ten actors + ten critics of TenAnt's MAPPO: 20).  The pointer arguments are HOST arrays of
- * `groups` device pointers.  Recurrent policies (use_recurrent_policy) are not covered. */
+ * `groups` device pointers.  Recurrent policies (use_recurrent_policy: an RNNLayer between MLPBase and the head) take
+ * mms_gru_group below between the last block and mms_marl_heads_act. */
 #define MMS_MAX_GROUPS 32
 
 /* y_g = act(x_g @ w_g^T + b_g), g < groups: mms_linear2_act for any number of networks (same kernel, same shapes rules).
@@ -440,7 +443,11 @@ int mms_linear2_act(int device, int64_t M, int32_t N, int32_t K, const float* x0
  *   ln_part_out[g] [N/64, M, 2]: the epilogue also leaves per output row and per 64-column slot the sum and the sum of squares of
  *     the activations; mms_row_stats_group turns them into (mean, rstd) per row.  No atomics: the result does not depend on scheduling.
  *   ln_stat_in[g] [M, 2] + ln_s[g] [N]: x_g is the PRE-LayerNorm activation h and the layer W (LN(h) gamma + beta) + b is evaluated
- *     as rstd (W~ h - mean s) + c: the caller passes W~ = W diag(gamma) as w_g, s = W~ 1 as ln_s[g] and c = W beta + b as b_g. */
+ *     as rstd (W~ h - mean s) + c: the caller passes W~ = W diag(gamma) as w_g, s = W~ 1 as ln_s[g] and c = W beta + b as b_g.
+ * act + 16 asks for blocked summation over k where the shapes take the generic kernel (M or N not a multiple of its tiles): every 32 k
+ * are summed from zero and added to the running sum -- 16 + K / 32 roundings of partial sums per output instead of K / 2.  The
+ * recurrent policies' layers ask for it (their state carries a layer's error from step to step); elsewhere, and on the tiled fast
+ * paths and the LayerNorm folds, results are what they are without it.  The CPU build's dot products are blocked either way. */
 int mms_linear_group_act(int device, int32_t groups, int64_t M, int32_t N, int32_t K, const float* const* x, const float* const* w,
                          const float* const* b, float* const* y, int32_t act, const float* const* ln_s, const float* const* ln_stat_in,
                          float* const* ln_part_out, void* hip_stream);
@@ -512,6 +519,34 @@ int mms_marl_heads_act(int device, int32_t groups, int64_t M, int32_t H, const f
                        const float* const* beta, const float* const* w, const float* const* b, const int32_t* A, const float* const* std,
                        float* const* out, float* const* logp, const int32_t* out_pitch, int64_t* const* counters, uint64_t seed,
                        int64_t row_offset, float eps, void* hip_stream);
+
+/* One GRU cell step for up to MMS_MAX_GROUPS networks in one launch: one layer of the reference's RNNLayer in its single-step
+ * branch (algorithms/utils/rnn.py:25-29: nn.GRU on hxs * masks; built into every recurrent actor and critic at
+ * algorithms/marl/actor_critic.py:35-36, 64-65, 139-140, 164-165 and run agent by agent from runner.py:205-217).  With torch's
+ * parameters as they lie (gate order r, z, n): w_ih [3H, K], w_hh [3H, H], b_ih [3H], b_hh [3H], for g < groups and i < M:
+ *   hm = mask_g[i] * h_g[i, :]                            (mask == NULL: hm = h_g[i, :])
+ *   r  = sigmoid(x W_ir^T + b_ir + hm W_hr^T + b_hr)
+ *   z  = sigmoid(x W_iz^T + b_iz + hm W_hz^T + b_hz)
+ *   n  = tanh   (x W_in^T + b_in + r * (hm W_hn^T + b_hn))
+ *   h' = (1 - z) * n + z * hm
+ * x, h, mask, w_ih, w_hh, b_ih, b_hh, h_out, y: HOST arrays of `groups` device pointers; pitches in floats.  x_g [M, K] at x_pitch;
+ * h_g [M, H] at h_pitch, so that layer l of an [M, recurrent_N, H] state slot (or of agent k's part of an [N, agents, recurrent_N,
+ * H] slot) is read where it lies; mask_g [M] at mask_pitch (NULL as a whole: no mask); h_out_g [M, H] at h_out_pitch receives h',
+ * e.g. in the next step's slot; y (NULL as a whole, or per group) is a second, dense [M, H] destination of the same h' -- the next
+ * GRU layer's x and the head's input.  The mask multiplies h as the reference does it (0 * NaN = NaN); a row with mask 0 is bit for
+ * bit the row of a zero state.
+ * On the matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 products and sums); the [M, 3H] pre-activations stay in accumulators.  The
+ * order of every sum over k is a function of K and H alone and there are no atomics: h'_g[i, :] is a function of row i and network
+ * g's parameters only, not of M, groups, the pitches or where the row sits, and runs are bit-identical.
+ * K and H positive multiples of 4, H <= 1024; x_pitch >= K, h_pitch >= H, h_out_pitch >= H, each a multiple of 4; mask_pitch >= 1;
+ * x_g, h_g, w_ih_g, w_hh_g, h_out_g, y_g 16-byte aligned; M >= 0 (M == 0 succeeds and touches nothing).  No destination may be one
+ * of the sources (other workgroups still read those rows): h_out_g == h_q or x_q, y_g == h_q, x_q or h_out_q, or two groups with one
+ * destination are refused.  Rows past M and columns past H are never written.  Bad arguments return non-zero with
+ * mms_last_error(NULL) and write nothing. */
+int mms_gru_group(int device, int32_t groups, int64_t M, int32_t K, int32_t H, const float* const* x, int64_t x_pitch,
+                  const float* const* h, int64_t h_pitch, const float* const* mask, int64_t mask_pitch, const float* const* w_ih,
+                  const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, float* const* h_out,
+                  int64_t h_out_pitch, float* const* y, void* hip_stream);
 
 /* ---- the same layers on the bf16 matrix pipe with fp32 operands carried as three bf16 planes (csrc/split_kernels.hip) -----------
  * An fp32 number is exactly a0 + a1 + a2 with a0 = bf16(a), a1 = bf16(a - a0), a2 = bf16(a - a0 - a1); the product is formed as the six

@@ -16,6 +16,9 @@ step for TenAnt.  The networks are independent and of the same shape, so here ev
     last LayerNorm + fc_mean + sample + log-probs     mms_marl_heads_act    all networks (critics: v_out, no sampling)
       (utils/act.py:75-81, distributions.py:94-117;
        actor_critic.py:153)
+    recurrent policies (actor_critic.py:64-65,        the last block's LayerNorm as mms_layernorm_group (in place), one mms_gru_group
+      164-165: RNNLayer, utils/rnn.py:7-80)           per GRU layer for all networks (states read from and written into the rollout
+                                                      slots where they lie), and RNNLayer.norm in the LayerNorm slot of mms_marl_heads_act
 
 `GroupedPolicyInference` takes the agents' Actor / Critic modules AS THEY ARE (the reference's classes, or anything with the same
 attributes: `.base.feature_norm`, `.base.mlp.fc1`, `.base.mlp.fc2`, `.act.action_out.{fc_mean, log_std, std_x_coef, std_y_coef}`,
@@ -27,7 +30,11 @@ unconditionally -- the trainers update between rollouts, and the reference's HAT
 (agents/algorithms/marl/hatrpo_trainer.py:122), which moves NO version counter; (2) in every other inference call when a parameter's
 version counter or address has moved (an in-place optimizer step moves them).  What it cannot see: a write through `.data` outside a
 collect loop -- call `refresh()` after it (tests/test_marl_policy.py pins all three).  Recurrent policies
-(use_recurrent_policy / use_naive_recurrent_policy) and non-Box action spaces are not covered: the constructor raises, nothing falls back silently.
+(use_recurrent_policy / use_naive_recurrent_policy: every network carries `.rnn.rnn`, an nn.GRU of the hidden width, and `.rnn.norm`)
+run the exact-fp32 layers (the plane kernels are not used), their GRU parameters are read in place (no derived copies), and
+`get_actions` / `get_values` / `collect` / `collect_into` take and return the states (see there).  A recurrent flag without such a
+layer, a mix of recurrent and feed-forward networks, and non-Box action spaces are not covered: the constructor raises, nothing falls
+back silently.
 
 The noise stream is this build's counter-based generator (seed + agent, global env row, per-row draw counter), as in
 rl/ppo/module.py: the sampled actions differ from torch's draw for the same torch seed, their distribution and the returned
@@ -54,6 +61,31 @@ def _blocks(base):
             raise NotImplementedError("GroupedPolicyInference: Linear bias and LayerNorm affine parameters are required")
         out.append((lin, ln))
     return out
+
+
+def _is_recurrent(m):
+    return bool(getattr(m, "_use_recurrent_policy", False) or getattr(m, "_use_naive_recurrent_policy", False))
+
+
+def _rnn_of(m, hidden):
+    """(nn.GRU, nn.LayerNorm) of a recurrent Actor / Critic: its RNNLayer (utils/rnn.py:7-22) as mms_gru_group evaluates it"""
+    layer = getattr(m, "rnn", None)
+    gru, norm = getattr(layer, "rnn", None), getattr(layer, "norm", None)
+    if not isinstance(gru, nn.GRU) or not isinstance(norm, nn.LayerNorm):
+        raise NotImplementedError("GroupedPolicyInference: a recurrent policy needs .rnn.rnn (nn.GRU) and .rnn.norm (nn.LayerNorm) (utils/rnn.py:13-22)")
+    if gru.bidirectional or not gru.bias or gru.input_size != hidden or gru.hidden_size != hidden or getattr(gru, "proj_size", 0) or gru.dropout:
+        raise NotImplementedError("GroupedPolicyInference: the GRU must be unidirectional with biases, input and hidden width = the base's hidden size")
+    if norm.weight is None or norm.bias is None or tuple(norm.normalized_shape) != (hidden,):
+        raise NotImplementedError("GroupedPolicyInference: RNNLayer.norm must be an affine LayerNorm over the hidden width")
+    return gru, norm
+
+
+def _mask_ptrs(masks, M):
+    """Pointer array + common pitch (floats) of [M, 1] float32 masks"""
+    pitch = {t.stride(0) for t in masks} if M > 1 else {1}
+    if len(pitch) != 1 or any(t.dim() != 2 or tuple(t.shape) != (M, 1) or t.dtype != torch.float32 for t in masks):
+        raise ValueError("GroupedPolicyInference: masks must be float32 [M, 1] with one common row pitch")
+    return (ctypes.c_void_p * len(masks))(*[t.data_ptr() for t in masks]), max(int(pitch.pop()), 1)
 
 
 def _ptrs(tensors):
@@ -92,6 +124,9 @@ class GroupedPolicyInference:
         self._chunks = None
         self._plans = None
         self._plist = None
+        rec = [_is_recurrent(m) for m in list(actors) + list(critics)]
+        if any(rec) and not all(rec):
+            raise NotImplementedError("GroupedPolicyInference: recurrent and feed-forward networks in one group are not covered")
         if len(actors) > 16:
             # MMS_MAX_GROUPS = 32 networks per launch = 16 agents: more agents (the 100-ant swarm) run as chunks of sixteen, each its
             # own set of grouped launches.  The noise key of agent k stays seed + k however the agents are chunked.
@@ -100,10 +135,11 @@ class GroupedPolicyInference:
             self._chunks = [GroupedPolicyInference(actors[lo:hi], critics[lo:hi], seed=int(seed) + lo, row_offset=row_offset,
                                                    fold_layernorm=fold_layernorm, split_layers=split_layers, split_format=split_format)
                             for lo, hi in self._ranges]
+            if len({c.recurrent_N for c in self._chunks}) != 1:
+                raise NotImplementedError("GroupedPolicyInference: all networks must share recurrent_N")
+            self.recurrent_N, self.hidden = self._chunks[0].recurrent_N, self._chunks[0].hidden
             return
         for m in list(actors) + list(critics):
-            if getattr(m, "_use_recurrent_policy", False) or getattr(m, "_use_naive_recurrent_policy", False):
-                raise NotImplementedError("GroupedPolicyInference: recurrent policies are not covered (actor_critic.py:64-65)")
             if not getattr(m.base, "_use_feature_normalization", hasattr(m.base, "feature_norm")):
                 raise NotImplementedError("GroupedPolicyInference: use_feature_normalization = False is not covered")
         self.actors, self.critics = list(actors), list(critics)
@@ -144,6 +180,16 @@ class GroupedPolicyInference:
         if self.act_dim > 16 or self.hidden > 1024 or self.hidden % 4:
             raise NotImplementedError("GroupedPolicyInference: at most 16 actions, hidden size a multiple of 4 up to 1024")
         self.eps = float(self.actors[0].base.feature_norm.eps)
+        # recurrent policies: the RNNLayer between the base and the head (actor_critic.py:35-36, 139-140), read in place
+        self.recurrent_N, self.rnns = 0, None
+        if all(rec):
+            self.rnns = [_rnn_of(m, self.hidden) for m in self.actors + self.critics]
+            layers = {g.num_layers for g, _ in self.rnns}
+            if len(layers) != 1:
+                raise NotImplementedError("GroupedPolicyInference: all networks must share recurrent_N")
+            if any(float(nm.eps) != self.eps for _, nm in self.rnns):
+                raise NotImplementedError("GroupedPolicyInference: RNNLayer.norm must use the eps of the other LayerNorms")
+            self.recurrent_N = layers.pop()
         self.device = self.actors[0].act.action_out.fc_mean.weight.device
         self._M, self._D, self.p, self._versions, self._plans = None, None, None, (), None
         self.refresh()
@@ -165,7 +211,7 @@ class GroupedPolicyInference:
         d = lambda t: t.detach()
         self.kp_a, self.kp_c = (self.obs_dim + 3) & ~3, (self.sobs_dim + 3) & ~3
         both = self.a_blocks + self.c_blocks
-        split = self.split_layers and self.fold_layernorm and self.sobs_dim % 4 == 0 and H % 128 == 0
+        split = self.split_layers and self.fold_layernorm and self.sobs_dim % 4 == 0 and H % 128 == 0 and not self.recurrent_N
         h16 = self.split_format == "f16x2"
         pbytes = lambda N, K: N * ((K + 31) // 32) * (128 if h16 else 192)
         u8 = lambda G, N, K: [torch.empty(pbytes(N, K), dtype=torch.uint8, device=dev) for _ in range(G)]
@@ -351,6 +397,11 @@ class GroupedPolicyInference:
         vouts = [c.v_out for c in self.critics]
         self.p["hw"] = arr([d(m.weight) for m in heads] + [d(m.weight) for m in vouts])
         self.p["hb"] = arr([d(m.bias) for m in heads] + [d(m.bias) for m in vouts])
+        if self.recurrent_N:
+            for l in range(self.recurrent_N):
+                for key, name in (("gru_wih", "weight_ih_l"), ("gru_whh", "weight_hh_l"), ("gru_bih", "bias_ih_l"), ("gru_bhh", "bias_hh_l")):
+                    self.p["%s%d" % (key, l)] = arr([d(getattr(g, "%s%d" % (name, l))) for g, _ in self.rnns])
+            self.p["rn_g"], self.p["rn_b"] = arr([d(nm.weight) for _, nm in self.rnns]), arr([d(nm.bias) for _, nm in self.rnns])
         self.p["std"] = arr(self._std + [None] * self.n)
         self.p["std_none"] = arr([None] * (2 * self.n))
         self._sp = None
@@ -389,6 +440,8 @@ class GroupedPolicyInference:
             self._counters_by_M[M] = torch.zeros(n, M, dtype=torch.int64, device=dev)
         self.counters = self._counters_by_M[M]
         self.part, self.stat = z(2 * n, max(1, H // 64), M, 2), z(2 * n, M, 2)        # row statistics of the folded LayerNorms
+        if self.recurrent_N:
+            self.rnn_new = z(2 * n, M, self.recurrent_N, H)                            # the new states when the caller names no destination
         self.stat_c = z(n, M, 2)                                                       # ... of the critics' feature LayerNorm
         ub = lambda t: list(t.unbind(0))
         self.q = {
@@ -431,7 +484,7 @@ class GroupedPolicyInference:
     # -- the split path ---------------------------------------------------------------------------------------------------------
     def _split_applies(self, M, sobs_pitch):
         return (self._sp is not None and self.split_layers and self.fold_layernorm and M % 128 == 0 and self.hidden % 128 == 0
-                and sobs_pitch == self.sobs_dim and self.sobs_dim >= 8)
+                and sobs_pitch == self.sobs_dim and self.sobs_dim >= 8 and not self.recurrent_N)
 
     def _forward_split(self, L, idx, stream, M, obs_p, obs_pitch, sobs_p, with_actors, std_p, out_p, logp_p, pitch_p, cnt_p):
         """Every layer through mms_linear_group_act_split16 / mms_linear_group_act_split with all LayerNorms folded and the heads finished from the last layer's
@@ -510,27 +563,76 @@ class GroupedPolicyInference:
         pitch = (ctypes.c_int32 * (2 * n))(*([a_pitch] * n + [v_pitch] * n))
         return values, actions, logp, out_p, logp_p, pitch
 
+    # -- recurrent policies -------------------------------------------------------------------------------------------------------
+    def _states(self, what, states, count):
+        if not self.recurrent_N:
+            if states is not None:
+                raise ValueError("GroupedPolicyInference: %s given, but the policies are not recurrent" % what)
+            return None
+        if states is None or len(states) != count:
+            raise ValueError("GroupedPolicyInference: recurrent policies need %s, one per agent" % what)
+        return list(states)
+
+    def _gru_stage(self, L, idx, stream, M, cur, sfx, states, masks, dsts):
+        """RNNLayer's single-step branch (utils/rnn.py:25-29) behind the last block of the G networks whose pre-LayerNorm activations
+        are in q["h<cur><sfx>"]: that block's LayerNorm in place, then one mms_gru_group per GRU layer -- layer l reads its state from
+        states[g][:, l] and writes the new one into dsts[g][:, l] where they lie ([M, recurrent_N, H] views), and leaves its output
+        in the other activation buffer (the next layer's x, the heads' input).  Returns the index of the buffer the heads read."""
+        H, p, q, last = self.hidden, self.p, self.q, self.depth - 1
+        G = len(states)
+        chk = lambda rc, what: _lib.check(rc, None, what, L)
+        for t in list(states) + list(dsts):
+            if t.dim() != 3 or tuple(t.shape) != (M, self.recurrent_N, H):
+                raise ValueError("GroupedPolicyInference: rnn states must be [M, recurrent_N, hidden] per agent")
+        mask_p, mask_pitch = _mask_ptrs(masks, M)
+        x = q["h%d%s" % (cur, sfx)]
+        chk(L.mms_layernorm_group(idx, G, M, H, H, H, x, p["ln%d_g%s" % (last, sfx)], p["ln%d_b%s" % (last, sfx)], x, self.eps, stream), "mms_layernorm_group")
+        for l in range(self.recurrent_N):
+            h_p, h_pitch = _row_ptrs([t.detach()[:, l] for t in states])
+            o_p, o_pitch = _row_ptrs([t.detach()[:, l] for t in dsts])
+            chk(L.mms_gru_group(idx, G, M, H, H, q["h%d%s" % (cur, sfx)], H, h_p, h_pitch, mask_p, mask_pitch, p["gru_wih%d%s" % (l, sfx)],
+                                p["gru_whh%d%s" % (l, sfx)], p["gru_bih%d%s" % (l, sfx)], p["gru_bhh%d%s" % (l, sfx)], o_p, o_pitch,
+                                q["h%d%s" % (1 - cur, sfx)], stream), "mms_gru_group")
+            cur = 1 - cur
+        return cur
+
     # -- inference ----------------------------------------------------------------------------------------------------------------
-    def get_actions(self, share_obs, obs, deterministic=False, out=None):
+    def get_actions(self, share_obs, obs, deterministic=False, out=None, rnn_states=None, rnn_states_critic=None, masks=None, rnn_out=None):
         """share_obs, obs: per-agent lists of [M, share_obs_dim] / [M, obs_dim] float32 tensors (what the Runner hands agent i:
         buffer[i].share_obs[step], buffer[i].obs[step]); rows may be strided (agent i's rows of an [M, agents, K] block are read
         where they lie).  out = (values, actions, action_log_probs): optional per-agent lists of [M, 1] / [M, act_dim] /
         [M, act_dim] destination views with dense rows (e.g. slices of [M, agents, ...] rollout slots), written in place.
         Returns (values, actions, action_log_probs): per-agent lists of
         [M, 1], [M, act_dim], [M, act_dim] views of buffers that the next call overwrites (the reference's
-        FixedNormal.log_probs keeps the per-dimension log-densities, utils/distributions.py:31-34)."""
+        FixedNormal.log_probs keeps the per-dimension log-densities, utils/distributions.py:31-34).
+        Recurrent policies (policy.get_actions, mappo_policy.py:54-75): rnn_states, rnn_states_critic = per-agent lists of
+        [M, recurrent_N, hidden] float32 views with dense rows and one common pitch (buffer[i].rnn_states[step]; agent i's part of an
+        [M, agents, recurrent_N, hidden] slot), masks = per-agent [M, 1]; all three are required.  The new states go into
+        rnn_out = (actor destinations, critic destinations), lists of the same form (e.g. the next step's slot; never the sources),
+        or into buffers that the next call overwrites; the return is then the reference's five values
+        (values, actions, action_log_probs, rnn_states, rnn_states_critic)."""
         n = self.n
         if len(share_obs) != n or len(obs) != n:
             raise ValueError("one observation tensor per agent")
+        rs_a, rs_c = self._states("rnn_states", rnn_states, n), self._states("rnn_states_critic", rnn_states_critic, n)
+        mk = self._states("masks", masks, n)
+        if rnn_out is not None and (not self.recurrent_N or len(rnn_out) != 2 or len(rnn_out[0]) != n or len(rnn_out[1]) != n):
+            raise ValueError("GroupedPolicyInference: rnn_out = (actor destinations, critic destinations), one each per agent, for recurrent policies")
         self._ensure_fresh()
         if self._chunks is not None:
-            res = ([], [], [])
+            res = ([], [], [], [], [])
             for c, (lo, hi) in zip(self._chunks, self._ranges):
                 o = None if out is None else tuple(None if x is None else x[lo:hi] for x in out)
-                got = c.get_actions(share_obs[lo:hi], obs[lo:hi], deterministic=deterministic, out=o)
+                kw = {}
+                if self.recurrent_N:
+                    kw = dict(rnn_states=rs_a[lo:hi], rnn_states_critic=rs_c[lo:hi], masks=mk[lo:hi],
+                              rnn_out=None if rnn_out is None else (rnn_out[0][lo:hi], rnn_out[1][lo:hi]))
+                got = c.get_actions(share_obs[lo:hi], obs[lo:hi], deterministic=deterministic, out=o, **kw)
                 for dst, part in zip(res, got):
                     if part is not None:
                         dst.extend(part)
+            if self.recurrent_N:
+                return res[0], res[1], (None if deterministic else res[2]), res[3], res[4]
             return res[0], res[1], (None if deterministic else res[2])
         M = obs[0].shape[0]
         self._buffers(M)
@@ -552,14 +654,16 @@ class GroupedPolicyInference:
         if not fold_c1:
             chk(L.mms_layernorm_group(idx, n, M, self.sobs_dim, self.kp_c, sobs_pitch, sobs_p, p["fn_c_g"], p["fn_c_b"], q["x_c"], self.eps, stream), "mms_layernorm_group")
         slots = H // 64
-        chk(L.mms_linear_group_act(idx, n, M, H, self.kp_a, q["x_a"], p["w1_a"], p["b1_a"], q["h0_a"], 1, None, None, q["part_a"] if fold else None, stream), "mms_linear_group_act")
+        # recurrent policies: blocked summation where the generic layer kernel runs (mms.h: act + 16) -- the state carries a layer's error on
+        act = 17 if self.recurrent_N and not fold else 1
+        chk(L.mms_linear_group_act(idx, n, M, H, self.kp_a, q["x_a"], p["w1_a"], p["b1_a"], q["h0_a"], act, None, None, q["part_a"] if fold else None, stream), "mms_linear_group_act")
         if fold_c1:
             shared_rows = len({int(v) for v in sobs_p}) == 1                 # one centralised observation for all critics: one pass
             chk(L.mms_row_moments_group(idx, 1 if shared_rows else n, M, self.sobs_dim, sobs_pitch, sobs_p, q["stat_c"], self.eps, stream), "mms_row_moments_group")
             chk(L.mms_linear_group_act(idx, n, M, H, self.sobs_dim, sobs_p, p["fw1_c"], p["fc1_c"], q["h0_c"], 1, p["fs1_c"],
                                        q["stat_c0"] if shared_rows else q["stat_c"], q["part_c"], stream), "mms_linear_group_act")
         else:
-            chk(L.mms_linear_group_act(idx, n, M, H, self.kp_c, q["x_c"], p["w1_c"], p["b1_c"], q["h0_c"], 1, None, None, q["part_c"] if fold else None, stream), "mms_linear_group_act")
+            chk(L.mms_linear_group_act(idx, n, M, H, self.kp_c, q["x_c"], p["w1_c"], p["b1_c"], q["h0_c"], act, None, None, q["part_c"] if fold else None, stream), "mms_linear_group_act")
         cur = 0
         for l in range(self.depth):
             if l > 0 and fold:                                      # LayerNorm l - 1 folded in; leaves the statistics of LayerNorm l
@@ -569,15 +673,23 @@ class GroupedPolicyInference:
                 cur = 1 - cur
                 continue
             if l > 0:
-                chk(L.mms_linear_group_act(idx, 2 * n, M, H, H, q["h%d" % cur], p["w%d" % l], p["b%d" % l], q["h%d" % (1 - cur)], 1, None, None, None, stream), "mms_linear_group_act")
+                chk(L.mms_linear_group_act(idx, 2 * n, M, H, H, q["h%d" % cur], p["w%d" % l], p["b%d" % l], q["h%d" % (1 - cur)], act, None, None, None, stream), "mms_linear_group_act")
                 cur = 1 - cur
             if l + 1 < self.depth and not fold:                     # (the last LayerNorm runs inside the heads kernel)
                 chk(L.mms_layernorm_group(idx, 2 * n, M, H, H, H, q["h%d" % cur], p["ln%d_g" % l], p["ln%d_b" % l], q["h%d" % cur], self.eps, stream), "mms_layernorm_group")
         last = self.depth - 1
         values, actions, logp, out_p, logp_p, pitch = self._out_ptrs(out)
-        chk(L.mms_marl_heads_act(idx, 2 * n, M, H, q["h%d" % cur], p["ln%d_g" % last], p["ln%d_b" % last], p["hw"], p["hb"], self._A,
+        ln_g, ln_b = p["ln%d_g" % last], p["ln%d_b" % last]
+        if self.recurrent_N:
+            new_a = list(self.rnn_new[:n].unbind(0)) if rnn_out is None else list(rnn_out[0])
+            new_c = list(self.rnn_new[n:].unbind(0)) if rnn_out is None else list(rnn_out[1])
+            cur = self._gru_stage(L, idx, stream, M, cur, "", rs_a + rs_c, mk + mk, new_a + new_c)
+            ln_g, ln_b = p["rn_g"], p["rn_b"]                        # RNNLayer.norm (utils/rnn.py:79) in the heads' LayerNorm slot
+        chk(L.mms_marl_heads_act(idx, 2 * n, M, H, q["h%d" % cur], ln_g, ln_b, p["hw"], p["hb"], self._A,
                                  p["std_none"] if deterministic else p["std"], out_p, logp_p, pitch, q["cnt"], self.seed, self.row_offset, self.eps, stream),
             "mms_marl_heads_act")
+        if self.recurrent_N:
+            return values, actions, (None if deterministic else logp), new_a, new_c
         return values, actions, (None if deterministic else logp)
 
     # -- the Runner's collect step --------------------------------------------------------------------------------------------------
@@ -588,12 +700,19 @@ class GroupedPolicyInference:
 
     @torch.no_grad()
     def collect(self, buffers, step):
-        """The body of Runner.collect (agents/algorithms/marl/runner.py:198-227) for non-recurrent policies: same five return values
-        -- values [M, agents, 1], the per-agent action and log-prob lists, and the (untouched) rnn states [M, agents, ...] -- from one
-        grouped pass instead of a loop over agents.  `buffers` = the Runner's per-agent SeparatedReplayBuffers.  The padded first
+        """The body of Runner.collect (agents/algorithms/marl/runner.py:198-227): same five return values -- values [M, agents, 1], the
+        per-agent action and log-prob lists, and the rnn states [M, agents, ...] (the new ones for recurrent policies, else untouched)
+        -- from one grouped pass instead of a loop over agents.  `buffers` = the Runner's per-agent SeparatedReplayBuffers.  The padded first
         actor weights and the std vectors are refreshed at step 0 of every episode (the trainers update the parameters in between)."""
         if step == 0:
             self.refresh()
+        if self.recurrent_N:
+            # buffer[i].rnn_states[step], .rnn_states_critic[step] and .masks[step] in (runner.py:205-211); the new states come back as
+            # [M, agents, recurrent_N, hidden], what Runner.insert takes (:224-238)
+            values, actions, logp, new_a, new_c = self.get_actions(
+                [b.share_obs[step] for b in buffers], [b.obs[step] for b in buffers], rnn_states=[b.rnn_states[step] for b in buffers],
+                rnn_states_critic=[b.rnn_states_critic[step] for b in buffers], masks=[b.masks[step] for b in buffers])
+            return torch.stack(values, 1), actions, logp, torch.stack(new_a, 1), torch.stack(new_c, 1)
         values, actions, logp = self.get_actions([b.share_obs[step] for b in buffers], [b.obs[step] for b in buffers])
         rnn_states = torch.transpose(torch.stack([b.rnn_states[step] for b in buffers]), 1, 0)
         rnn_states_critic = torch.transpose(torch.stack([b.rnn_states_critic[step] for b in buffers]), 1, 0)
@@ -603,7 +722,9 @@ class GroupedPolicyInference:
     def collect_into(self, shared, deterministic=False):
         """The collect step over `SharedRolloutBuffers` (utils/shared_buffer.py), zero copy: every agent's observation rows are read
         from `shared.obs[step]` / `shared.share_obs[step]` where the env step left them, and actions, log-probs and values are
-        written straight into `shared.actions[step]`, `shared.action_log_probs[step]`, `shared.value_preds[step]`.  Returns the
+        written straight into `shared.actions[step]`, `shared.action_log_probs[step]`, `shared.value_preds[step]`.  Recurrent policies
+        read `shared.rnn_states[step][:, k, l]`, `shared.rnn_states_critic[step][:, k, l]` and `shared.masks[step]` and write the new
+        states into slot step + 1 in place (`shared.insert_step` then zeroes the rows of envs that are done).  Returns the
         [N, agents, act_dim] action slot (what `shared.env_step` takes)."""
         s, n = shared.step, self.n
         if self.refresh_every_rollout:
@@ -615,25 +736,35 @@ class GroupedPolicyInference:
         # left per call is the launches -- the eager collect step then stays ahead of the GPU like the captured one
         key = (shared.obs.data_ptr(), shared.share_obs.data_ptr(), shared.actions.data_ptr(), shared.value_preds.data_ptr(), tuple(shared.obs.shape), s,
                bool(deterministic))
+        if self.recurrent_N:
+            key += (shared.rnn_states.data_ptr(), shared.rnn_states_critic.data_ptr(), shared.masks.data_ptr(), tuple(shared.rnn_states.shape))
 
         def make():
             obs, sobs = shared.obs[s], shared.share_obs[s]
             out = ([shared.value_preds[s][:, k:k + 1] for k in range(n)], [shared.actions[s][:, k] for k in range(n)],
                    [shared.action_log_probs[s][:, k] for k in range(n)])
-            return [sobs] * n, [obs[:, k] for k in range(n)], out
+            rec = None
+            if self.recurrent_N:
+                rec = {"rnn_states": [shared.rnn_states[s][:, k] for k in range(n)], "rnn_states_critic": [shared.rnn_states_critic[s][:, k] for k in range(n)],
+                       "masks": [shared.masks[s]] * n,
+                       "rnn_out": ([shared.rnn_states[s + 1][:, k] for k in range(n)], [shared.rnn_states_critic[s + 1][:, k] for k in range(n)])}
+            return [sobs] * n, [obs[:, k] for k in range(n)], out, rec
         self._get_actions_planned(key, make, deterministic)
         return shared.actions[s]
 
     def _get_actions_planned(self, key, make, deterministic):
-        """get_actions(share_obs, obs, deterministic, out) with (share_obs, obs, out) = make(), called only when `key` is new: the split
-        path's operand pointer arrays are cached under it (the caller vouches that the key names the tensors)."""
+        """get_actions(share_obs, obs, deterministic, out, **rec) with (share_obs, obs, out, rec) = make(), called only when `key` is
+        new: the split path's operand pointer arrays are cached under it (the caller vouches that the key names the tensors).  rec:
+        None, or the recurrent policies' keyword arguments."""
         if self._plans is None:
             self._plans = {}
         plan = self._plans.get(key)
         if plan is None:
-            share_obs, obs, out = make()
+            share_obs, obs, out, rec = make()
             if self._chunks is not None:
-                plan = ("chunks", [(c, (lambda so=share_obs[lo:hi], ob=obs[lo:hi], ou=tuple(x[lo:hi] for x in out): (so, ob, ou)))
+                part = lambda lo, hi: None if rec is None else {"rnn_states": rec["rnn_states"][lo:hi], "rnn_states_critic": rec["rnn_states_critic"][lo:hi],
+                                                                "masks": rec["masks"][lo:hi], "rnn_out": tuple(x[lo:hi] for x in rec["rnn_out"])}
+                plan = ("chunks", [(c, (lambda so=share_obs[lo:hi], ob=obs[lo:hi], ou=tuple(x[lo:hi] for x in out), rc=part(lo, hi): (so, ob, ou, rc)))
                                    for c, (lo, hi) in zip(self._chunks, self._ranges)])
             else:
                 M = obs[0].shape[0]
@@ -646,13 +777,13 @@ class GroupedPolicyInference:
                 if self._split_applies(M, sobs_pitch) and direct:
                     plan = ("split", M, obs_p, obs_pitch, sobs_p) + tuple(self._out_ptrs(out)[3:]) + ((obs_f, sobs_f, out),)
                 else:
-                    plan = ("generic", share_obs, obs, out)
+                    plan = ("generic", share_obs, obs, out, rec or {})
             self._plans[key] = plan
         if plan[0] == "chunks":
             for c, mk in plan[1]:
                 c._get_actions_planned(key, mk, deterministic)
         elif plan[0] == "generic":
-            self.get_actions(plan[1], plan[2], deterministic=deterministic, out=plan[3])
+            self.get_actions(plan[1], plan[2], deterministic=deterministic, out=plan[3], **plan[4])
         else:
             _, M, obs_p, obs_pitch, sobs_p, out_p, logp_p, pitch, _keep = plan
             self._buffers(M)
@@ -688,17 +819,20 @@ class GroupedPolicyInference:
         return (st[..., 0].abs() * st[..., 1]).max()
 
     @torch.no_grad()
-    def get_values(self, share_obs, out=None):
+    def get_values(self, share_obs, out=None, rnn_states_critic=None, masks=None):
         """The critics alone (policy.get_values, mappo_policy.py:77-88; Runner.compute, runner.py:229-241): per-agent lists of
-        [M, share_obs_dim] in, [M, 1] values out (views of a buffer the next call overwrites, or the `out` destinations)."""
+        [M, share_obs_dim] in, [M, 1] values out (views of a buffer the next call overwrites, or the `out` destinations).  Recurrent
+        policies: rnn_states_critic and masks as get_actions takes them (the new states are dropped, as the reference drops them)."""
         n = self.n
         if len(share_obs) != n:
             raise ValueError("one observation tensor per agent")
+        rs_c, mk = self._states("rnn_states_critic", rnn_states_critic, n), self._states("masks", masks, n)
         self._ensure_fresh()
         if self._chunks is not None:
             res = []
             for c, (lo, hi) in zip(self._chunks, self._ranges):
-                res.extend(c.get_values(share_obs[lo:hi], None if out is None else out[lo:hi]))
+                kw = dict(rnn_states_critic=rs_c[lo:hi], masks=mk[lo:hi]) if self.recurrent_N else {}
+                res.extend(c.get_values(share_obs[lo:hi], None if out is None else out[lo:hi], **kw))
             return res
         M = share_obs[0].shape[0]
         self._buffers(M)
@@ -717,6 +851,7 @@ class GroupedPolicyInference:
         fold = self.fold_layernorm and self.depth > 1 and M % 128 == 0 and H % 128 == 0 and self._has_wt
         fold_c1 = fold and self._fold_c1 is not None and sobs_pitch == self.sobs_dim and self.sobs_dim >= 8
         slots = H // 64
+        act = 17 if self.recurrent_N and not fold else 1                       # (as in get_actions)
         if fold_c1:
             shared_rows = len({int(v) for v in sobs_p}) == 1
             chk(L.mms_row_moments_group(idx, 1 if shared_rows else n, M, self.sobs_dim, sobs_pitch, sobs_p, q["stat_c"], self.eps, stream), "mms_row_moments_group")
@@ -724,7 +859,7 @@ class GroupedPolicyInference:
                                        q["stat_c0"] if shared_rows else q["stat_c"], q["part_c"], stream), "mms_linear_group_act")
         else:
             chk(L.mms_layernorm_group(idx, n, M, self.sobs_dim, self.kp_c, sobs_pitch, sobs_p, p["fn_c_g"], p["fn_c_b"], q["x_c"], self.eps, stream), "mms_layernorm_group")
-            chk(L.mms_linear_group_act(idx, n, M, H, self.kp_c, q["x_c"], p["w1_c"], p["b1_c"], q["h0_c"], 1, None, None, q["part_c"] if fold else None, stream), "mms_linear_group_act")
+            chk(L.mms_linear_group_act(idx, n, M, H, self.kp_c, q["x_c"], p["w1_c"], p["b1_c"], q["h0_c"], act, None, None, q["part_c"] if fold else None, stream), "mms_linear_group_act")
         cur = 0
         for l in range(self.depth):
             if l > 0 and fold:
@@ -734,7 +869,7 @@ class GroupedPolicyInference:
                 cur = 1 - cur
                 continue
             if l > 0:
-                chk(L.mms_linear_group_act(idx, n, M, H, H, q["h%d/c" % cur], p["w%d/c" % l], p["b%d/c" % l], q["h%d/c" % (1 - cur)], 1, None, None, None, stream), "mms_linear_group_act")
+                chk(L.mms_linear_group_act(idx, n, M, H, H, q["h%d/c" % cur], p["w%d/c" % l], p["b%d/c" % l], q["h%d/c" % (1 - cur)], act, None, None, None, stream), "mms_linear_group_act")
                 cur = 1 - cur
             if l + 1 < self.depth and not fold:
                 chk(L.mms_layernorm_group(idx, n, M, H, H, H, q["h%d/c" % cur], p["ln%d_g/c" % l], p["ln%d_b/c" % l], q["h%d/c" % cur], self.eps, stream), "mms_layernorm_group")
@@ -742,7 +877,11 @@ class GroupedPolicyInference:
         values = list(self.values.unbind(0)) if out is None else list(out)
         vp, v_pitch = _row_ptrs(values)
         pitch = (ctypes.c_int32 * n)(*([v_pitch] * n))
-        chk(L.mms_marl_heads_act(idx, n, M, H, q["h%d/c" % cur], p["ln%d_g/c" % last], p["ln%d_b/c" % last], p["hw/c"], p["hb/c"], self._A1,
+        ln_g, ln_b = p["ln%d_g/c" % last], p["ln%d_b/c" % last]
+        if self.recurrent_N:
+            cur = self._gru_stage(L, idx, stream, M, cur, "/c", rs_c, mk, list(self.rnn_new[n:].unbind(0)))
+            ln_g, ln_b = p["rn_g/c"], p["rn_b/c"]
+        chk(L.mms_marl_heads_act(idx, n, M, H, q["h%d/c" % cur], ln_g, ln_b, p["hw/c"], p["hb/c"], self._A1,
                                  None, vp, None, pitch, None, self.seed, self.row_offset, self.eps, stream), "mms_marl_heads_act")
         return values
 
@@ -751,5 +890,8 @@ class GroupedPolicyInference:
         """Critic values of observation slot `slot` (default: the last one -- the bootstrap values of Runner.compute,
         runner.py:229-241, taken from share_obs[-1]) into dst [N, agents]: the critics alone (`get_values`)."""
         n = self.n
-        self.get_values([shared.share_obs[slot]] * n, out=[dst[:, k:k + 1] for k in range(n)])
+        kw = {}
+        if self.recurrent_N:
+            kw = dict(rnn_states_critic=[shared.rnn_states_critic[slot][:, k] for k in range(n)], masks=[shared.masks[slot]] * n)
+        self.get_values([shared.share_obs[slot]] * n, out=[dst[:, k:k + 1] for k in range(n)], **kw)
         return dst

@@ -9,8 +9,16 @@ The policy is taken as it is: `policy.actor`, `.critic`, `.actor_optimizer`, `.c
 GroupedPolicyInference relies on (`.base.feature_norm`, `.base.mlp.fc1 / fc2`, `.act.action_out.{fc_mean, log_std, std_x_coef,
 std_y_coef}`, `.v_out`).  An update runs actor.base -> fc_mean and critic.base -> v_out in torch, forms std from log_std, calls
 marl_ppo_loss, does ONE backward() of the objective (the reference's two backward() calls reach disjoint parameter sets), clips the two
-gradient norms separately and steps both optimizers.  Recurrent policies and action spaces other than Box raise in the constructor;
-nothing falls back silently.
+gradient norms separately and steps both optimizers.  Action spaces other than Box raise in the constructor; nothing falls back
+silently.
+
+Recurrent policies (use_recurrent_policy / use_naive_recurrent_policy) are accepted when `policy.actor.rnn` and `policy.critic.rnn` are
+the reference's RNNLayer (`.rnn`, an nn.GRU, and `.norm`; agents/algorithms/utils/rnn.py:7-80); a policy without one raises.  An update
+then runs `actor.rnn(features, rnn_states, masks)` and `critic.rnn(...)` -- the module's own forward, with its sequence branch
+(rnn.py:30-77) and torch's backward through time -- between the bases and the heads, on the rows and the one state per sequence that
+`recurrent_generator` (or `naive_recurrent_generator`) yields; `train` picks the generator as mappo_trainer.py:211-216 does and
+the loss stays marl_ppo_loss on the gathered fields.  The rollout's side of it is GroupedPolicyInference (mms_gru_group).  The
+generator hands the rows over as the reference's does (generators.py: chunk-major), and RNNLayer reads them as it does there.
 
 `ppo_update` takes the reference's gathered tuple.  `train` draws the permutation exactly as feed_forward_generator does
 (torch.randperm(batch), the same slices), gathers only the network inputs (share_obs, obs) and the returns the normaliser's batch
@@ -58,6 +66,10 @@ def _base(base, x):
     return x
 
 
+def _is_rnn_layer(layer):
+    return isinstance(getattr(layer, "rnn", None), nn.GRU) and isinstance(getattr(layer, "norm", None), nn.LayerNorm)
+
+
 def get_grad_norm(params):
     """agents/utils/util.py:8-15 (get_gard_norm)."""
     total = 0.0
@@ -94,8 +106,10 @@ class _Trainer:
         self._use_policy_active_masks = config["use_policy_active_masks"]
         name = type(self).__name__
         assert not (self._use_popart and self._use_valuenorm), "self._use_popart and self._use_valuenorm can not be set True simultaneously"
-        if self._use_recurrent_policy or self._use_naive_recurrent:
-            raise NotImplementedError("%s: recurrent policies are not covered (use_recurrent_policy / use_naive_recurrent_policy)" % name)
+        self._recurrent = bool(self._use_recurrent_policy or self._use_naive_recurrent)
+        if self._recurrent and not (_is_rnn_layer(getattr(policy.actor, "rnn", None)) and _is_rnn_layer(getattr(policy.critic, "rnn", None))):
+            raise NotImplementedError("%s: use_recurrent_policy / use_naive_recurrent_policy need policy.actor.rnn and policy.critic.rnn "
+                                      "(RNNLayer: .rnn = nn.GRU, .norm = nn.LayerNorm)" % name)
         head = getattr(getattr(policy.actor, "act", None), "action_out", None)
         if head is None or not (hasattr(head, "fc_mean") and hasattr(head, "log_std")):
             raise NotImplementedError("%s: only Box action spaces (ACTLayer.action_out = DiagGaussian) are covered" % name)
@@ -103,16 +117,21 @@ class _Trainer:
         self.loss_fn = marl_ppo_loss            # (a benchmark swaps in marl_ppo_loss_torch)
 
     # -- one update -------------------------------------------------------------------------------------------------------------
-    def _update(self, share_obs, obs, returns_rows, fields, indices, update_actor):
+    def _update(self, share_obs, obs, returns_rows, fields, indices, update_actor, rnn=None):
+        """rnn: None, or (rnn_states, rnn_states_critic, masks) of a recurrent generator's sample"""
         actor, critic = self.policy.actor, self.policy.critic
         head = actor.act.action_out
-        values = critic.v_out(_base(critic.base, share_obs))
+        if rnn is None:
+            features = lambda net, x, states: _base(net.base, x)
+        else:
+            features = lambda net, x, states: net.rnn(_base(net.base, x), states, rnn[2])[0]       # actor_critic.py:64-65, 164-165
+        values = critic.v_out(features(critic, share_obs, None if rnn is None else rnn[1]))
         if update_actor:
-            mu = head.fc_mean(_base(actor.base, obs))
+            mu = head.fc_mean(features(actor, obs, None if rnn is None else rnn[0]))
             std = torch.sigmoid(head.log_std / head.std_x_coef) * head.std_y_coef
         else:
             with torch.no_grad():
-                mu = head.fc_mean(_base(actor.base, obs))
+                mu = head.fc_mean(features(actor, obs, None if rnn is None else rnn[0]))
                 std = torch.sigmoid(head.log_std / head.std_x_coef) * head.std_y_coef
         norm = (None, None)
         if self._use_valuenorm:
@@ -148,11 +167,12 @@ class _Trainer:
     def ppo_update(self, sample, update_actor=True):
         """One update from the generators' gathered tuple; returns (value_loss, critic_grad_norm, policy_loss, dist_entropy,
         actor_grad_norm, imp_weights) -- imp_weights: the mean ratio (module docstring)."""
-        share_obs, obs, _, _, actions, value_preds, returns, _, active_masks, old_logp, adv = sample[:11]
+        share_obs, obs, rnn_states, rnn_states_critic, actions, value_preds, returns, masks, active_masks, old_logp, adv = sample[:11]
         cast = lambda x: torch.as_tensor(x).to(**self.tpdv)
         factor = cast(sample[12]) if self._has_factor else None
         fields = (cast(actions), cast(old_logp), cast(adv), cast(value_preds), cast(returns), cast(active_masks), factor)
-        return self._update(cast(share_obs), cast(obs), fields[4], fields, None, update_actor)
+        rnn = (cast(rnn_states), cast(rnn_states_critic), cast(masks)) if self._recurrent else None
+        return self._update(cast(share_obs), cast(obs), fields[4], fields, None, update_actor, rnn)
 
     def train(self, buffer, update_actor=True):
         """The reference's train(): ppo_epoch passes over num_mini_batch random minibatches of the buffer; returns train_info."""
@@ -165,6 +185,23 @@ class _Trainer:
         std_advantages = torch.std(advantages_copy)
         advantages = ((advantages - mean_advantages) / (std_advantages + 1e-5)).contiguous()
         train_info = {k: 0 for k in ("value_loss", "policy_loss", "dist_entropy", "actor_grad_norm", "critic_grad_norm", "ratio")}
+        if self._recurrent:                                            # mappo_trainer.py:210-227 with the recurrent generators
+            for _ in range(self.ppo_epoch):
+                if self._use_recurrent_policy:
+                    generator = buffer.recurrent_generator(advantages, self.num_mini_batch, self.data_chunk_length)
+                else:
+                    generator = buffer.naive_recurrent_generator(advantages, self.num_mini_batch)
+                for sample in generator:
+                    value_loss, critic_grad_norm, policy_loss, dist_entropy, actor_grad_norm, imp_weights = self.ppo_update(sample, update_actor)
+                    train_info["value_loss"] += value_loss.item()
+                    train_info["policy_loss"] += policy_loss.item()
+                    train_info["dist_entropy"] += dist_entropy.item()
+                    train_info["actor_grad_norm"] += actor_grad_norm
+                    train_info["critic_grad_norm"] += critic_grad_norm
+                    train_info["ratio"] += imp_weights.mean()
+            for k in train_info.keys():
+                train_info[k] /= self.ppo_epoch * self.num_mini_batch
+            return train_info
         T, N = buffer.rewards.shape[0:2]
         batch = T * N
         assert batch >= self.num_mini_batch, ("PPO requires the number of processes (%d) * number of steps (%d) = %d to be greater than or "

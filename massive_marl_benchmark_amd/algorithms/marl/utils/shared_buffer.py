@@ -164,6 +164,8 @@ class SharedRolloutBuffers:
         self.factor = torch.ones(T, N, A, 1, device=self.device)
         self.step = 0
         self._pending = {}
+        # recurrent policies: GroupedPolicyInference.collect_into writes the new states into slot step + 1, insert_step resets done envs
+        self.recurrent = bool(config.get("use_recurrent_policy", False) or config.get("use_naive_recurrent_policy", False))
         self.agents = [_AgentView(self, k) for k in range(A)]
 
     # -- environment side ----------------------------------------------------------------------------------------
@@ -208,6 +210,9 @@ class SharedRolloutBuffers:
         put(self.value_preds[s], values)
         put(self.actions[s], actions)
         put(self.action_log_probs[s], action_log_probs)
+        if self.recurrent:                                                          # runner.py:235-238: a finished episode starts from a zero state
+            done = (dones != 0).view(-1, 1, 1, 1)
+            self.rnn_states[s + 1].masked_fill_(done, 0.0), self.rnn_states_critic[s + 1].masked_fill_(done, 0.0)
         self.step = (s + 1) % self.T
 
     def finished_episode_rewards(self, running, reward_env, dones_env):

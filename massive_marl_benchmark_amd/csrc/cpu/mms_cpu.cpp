@@ -25,6 +25,7 @@
 #include "../maddpg_lane.h"
 #include "../sac_lane.h"
 #include "../sac_grad_lane.h"
+#include "../gru_lane.h"
 #include "lane_step.h"
 
 #define MMS_API extern "C" __attribute__((visibility("default")))
@@ -954,6 +955,21 @@ MMS_API int mms_marl_heads_finish(int device, int32_t groups, int64_t M, int32_t
 }
 
 // ---- grouped policy inference (plain loops) -------------------------------------------------------------------------------------
+// A dot product in one fixed order: sixteen fp32 partial sums over k % 16, each step p <- fl(p + a b) with the product exact (formed
+// and added in double, rounded to fp32: the fused multiply-add's arithmetic without depending on the host's ISA), a remainder of
+// n % 16 terms into the first ones, then the halving tree p[j] += p[j + 8], + 4, + 2, + 1.  An output sees n / 16 + 4 roundings of
+// partial sums instead of the n of a single chain: the error of a blocked fp32 product, which is what the library products that the
+// tests take as their yardstick have (a recurrent policy's state carries a layer's error from step to step).
+static inline float dot16(const float* a, const float* b, int n) {
+    float p[16] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int k = 0;
+    for (; k + 16 <= n; k += 16)
+        for (int j = 0; j < 16; j++) p[j] = (float)((double)p[j] + (double)a[k + j] * (double)b[k + j]);
+    for (int j = 0; k + j < n; j++) p[j] = (float)((double)p[j] + (double)a[k + j] * (double)b[k + j]);
+    for (int w = 8; w >= 1; w >>= 1)
+        for (int j = 0; j < w; j++) p[j] += p[j + w];
+    return p[0];
+}
 MMS_API int mms_linear_group_act(int device, int32_t groups, int64_t M, int32_t N, int32_t K, const float* const* x, const float* const* w,
                                  const float* const* b, float* const* y, int32_t act, const float* const* ln_s, const float* const* ln_stat_in,
                                  float* const* ln_part_out, void*) {
@@ -963,10 +979,9 @@ MMS_API int mms_linear_group_act(int device, int32_t groups, int64_t M, int32_t 
 #pragma omp parallel for schedule(static)
         for (int64_t m = 0; m < M; m++) {
             for (int n = 0; n < N; n++) {
-                float s = 0.f;
-                for (int k = 0; k < K; k++) s = fmaf(x[g][m * K + k], w[g][(int64_t)n * K + k], s);
+                float s = dot16(x[g] + m * K, w[g] + (int64_t)n * K, K);
                 if (ln_s) s = ln_stat_in[g][2 * m + 1] * (s - ln_stat_in[g][2 * m] * ln_s[g][n]);      // rstd (W~ h - mean s)
-                y[g][m * N + n] = act_fn(s + b[g][n], act);
+                y[g][m * N + n] = act_fn(s + b[g][n], act & 15);
             }
             if (ln_part_out)                                                                            // slot = 64 consecutive columns
                 for (int slot = 0; slot < N / 64; slot++) {
@@ -1026,6 +1041,39 @@ MMS_API int mms_layernorm_group(int device, int32_t groups, int64_t M, int32_t K
             ln_row(x[g] + m * x_pitch, K, eps, mean, rstd);
             for (int k = 0; k < K; k++) y[g][m * Kp + k] = (x[g][m * x_pitch + k] - mean) * rstd * gamma[g][k] + beta[g][k];
             for (int k = K; k < Kp; k++) y[g][m * Kp + k] = 0.f;
+        }
+    }
+    return 0;
+}
+// One GRU cell step per network (include/mms.h: mms_gru_group) over ../gru_lane.h, every dot product by dot16 (above).
+MMS_API int mms_gru_group(int device, int32_t groups, int64_t M, int32_t K, int32_t H, const float* const* x, int64_t x_pitch, const float* const* h,
+                          int64_t h_pitch, const float* const* mask, int64_t mask_pitch, const float* const* w_ih, const float* const* w_hh,
+                          const float* const* b_ih, const float* const* b_hh, float* const* h_out, int64_t h_out_pitch, float* const* y, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_gru_group(groups, M, K, H, x, x_pitch, h, h_pitch, mask, mask_pitch, w_ih, w_hh, b_ih, b_hh, h_out, h_out_pitch, y))) return 1;
+    for (int g = 0; g < groups; g++) {
+        const float *wi = w_ih[g], *wh = w_hh[g], *bi = b_ih[g], *bh = b_hh[g];
+        float* yg = y ? y[g] : nullptr;
+#pragma omp parallel for schedule(static)
+        for (int64_t m = 0; m < M; m++) {
+            float hm[mms::kGruMaxH];
+            const float* xr = x[g] + m * x_pitch;
+            const float* hr = h[g] + m * h_pitch;
+            if (mask) {
+                const float mk = mask[g][m * mask_pitch];
+                for (int k = 0; k < H; k++) hm[k] = mms::gru_masked(mk, hr[k]);
+            } else {
+                for (int k = 0; k < H; k++) hm[k] = hr[k];
+            }
+            for (int j = 0; j < H; j++) {
+                const float s_r = dot16(xr, wi + (int64_t)j * K, K) + dot16(hm, wh + (int64_t)j * H, H);
+                const float s_z = dot16(xr, wi + (int64_t)(H + j) * K, K) + dot16(hm, wh + (int64_t)(H + j) * H, H);
+                const float s_ni = dot16(xr, wi + (int64_t)(2 * H + j) * K, K);
+                const float s_nh = dot16(hm, wh + (int64_t)(2 * H + j) * H, H);
+                const float o = mms::gru_cell(s_r, s_z, s_ni, s_nh, bi[j], bi[H + j], bi[2 * H + j], bh[j], bh[H + j], bh[2 * H + j], hm[j]);
+                h_out[g][m * h_out_pitch + j] = o;
+                if (yg) yg[m * H + j] = o;
+            }
         }
     }
     return 0;

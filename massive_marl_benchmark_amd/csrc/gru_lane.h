@@ -1,0 +1,30 @@
+// gru_lane.h -- the gate arithmetic of one GRU cell step (torch.nn.GRU's cell, gate order r, z, n; the reference's RNNLayer,
+// agents/algorithms/utils/rnn.py:25-29, runs it on hxs * masks), written once for the HIP kernel (gru_kernels.hip) and the CPU build
+// (cpu/mms_cpu.cpp).  Both are compiled with -ffp-contract=off and without fast-math: every product and sum below is rounded on its
+// own, expf, tanhf and the division are the libraries' accurate ones.  The two builds differ only in the order of the dot products
+// that feed it.
+#pragma once
+#include <math.h>
+
+#include "mms_lane.h"
+
+namespace mms {
+
+constexpr int kGruMaxH = 1024;
+
+// hm = mask * h as the reference multiplies (a NaN in a masked row stays NaN); + 0 turns the -0 of 0 * negative into +0, so a masked
+// row is bit for bit the row of a zero state
+MMS_HD float gru_masked(float m, float h) { return m * h + 0.0f; }
+
+MMS_HD float gru_sigmoid(float a) { return 1.0f / (1.0f + expf(-a)); }
+
+// s_r, s_z: the r and z rows' dot products over x AND hm (one sum); s_ni, s_nh: the n row's over x and over hm, kept apart because r
+// multiplies the second with its bias
+MMS_HD float gru_cell(float s_r, float s_z, float s_ni, float s_nh, float bi_r, float bi_z, float bi_n, float bh_r, float bh_z, float bh_n, float hm) {
+    const float r = gru_sigmoid((s_r + bi_r) + bh_r);
+    const float z = gru_sigmoid((s_z + bi_z) + bh_z);
+    const float n = tanhf((s_ni + bi_n) + r * (s_nh + bh_n));
+    return (1.0f - z) * n + z * hm;
+}
+
+}  // namespace mms

@@ -11,6 +11,7 @@
 #include "trpo_plan.h"
 #include "ln_mlp_plan.h"
 #include "maddpg_args.h"
+#include "gru_args.h"
 
 namespace mms {
 hipError_t launch_step(const StepArgs& a, int task, hipStream_t stream);
@@ -649,7 +650,7 @@ __attribute__((visibility("default"))) int mms_linear_group_act(int device, int3
         if (ln_s) { a.s[g] = ln_s[g]; a.stat_in[g] = ln_stat_in[g]; }
         if (ln_part_out) a.part_out[g] = ln_part_out[g];
     }
-    a.M = (int)M; a.N = N; a.K = K; a.act = act;
+    a.M = (int)M; a.N = N; a.K = K; a.act = act & 15; a.blocked = (act & 16) != 0;
     MMS_FREE(mms::launch_linear_act(a, groups, (hipStream_t)s));
     return 0;
 }
@@ -707,6 +708,24 @@ __attribute__((visibility("default"))) int mms_marl_heads_act(int device, int32_
     }
     a.seed = seed; a.M = M; a.row_offset = row_offset; a.H = H; a.eps = eps;
     MMS_FREE(mms::launch_marl_heads(a, groups, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_gru_group(int device, int32_t groups, int64_t M, int32_t K, int32_t H, const float* const* x, int64_t x_pitch,
+                                                         const float* const* h, int64_t h_pitch, const float* const* mask, int64_t mask_pitch,
+                                                         const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
+                                                         const float* const* b_hh, float* const* h_out, int64_t h_out_pitch, float* const* y, void* s) {
+    MMS_DEV(device)
+    if (refused(check_gru_group(groups, M, K, H, x, x_pitch, h, h_pitch, mask, mask_pitch, w_ih, w_hh, b_ih, b_hh, h_out, h_out_pitch, y))) return 1;
+    mms::GruArgs a = {};
+    for (int g = 0; g < groups; g++) {
+        a.x[g] = x[g]; a.h[g] = h[g]; a.mask[g] = mask ? mask[g] : nullptr;
+        a.w_ih[g] = w_ih[g]; a.w_hh[g] = w_hh[g]; a.b_ih[g] = b_ih[g]; a.b_hh[g] = b_hh[g];
+        a.h_out[g] = h_out[g]; a.y[g] = y ? y[g] : nullptr;
+    }
+    a.x_pitch = x_pitch; a.h_pitch = h_pitch; a.mask_pitch = mask_pitch; a.h_out_pitch = h_out_pitch;
+    a.M = (int)M; a.K = K; a.H = H;
+    MMS_FREE(mms::launch_gru_group(a, groups, (hipStream_t)s));
     return 0;
 }
 

@@ -627,10 +627,10 @@ static inline std::string check_linear_group_act(int32_t groups, int64_t M, int3
                                                  const float* const* ln_stat_in, float* const* ln_part_out) {
     std::string bad = check_groups("mms_linear_group_act", groups);
     if (!bad.empty()) return bad;
-    if (!x || !w || !b || !y || M < 0 || M > 0x7fffffff || N <= 0 || K <= 0 || (K % 4) != 0 || act < 0 || act > 3)
-        return "mms_linear_group_act: bad arguments (K must be a positive multiple of 4, act 0..3)";
+    if (!x || !w || !b || !y || M < 0 || M > 0x7fffffff || N <= 0 || K <= 0 || (K % 4) != 0 || act < 0 || (act & ~16) > 3)
+        return "mms_linear_group_act: bad arguments (K must be a positive multiple of 4, act 0..3, optionally + 16)";
     if ((ln_stat_in != nullptr) != (ln_s != nullptr)) return "mms_linear_group_act: ln_stat_in and ln_s come together";
-    if ((ln_stat_in || ln_part_out) && (act != 1 || M % 128 != 0 || N % 128 != 0 || K < 8))
+    if ((ln_stat_in || ln_part_out) && ((act & ~16) != 1 || M % 128 != 0 || N % 128 != 0 || K < 8))
         return "mms_linear_group_act: the LayerNorm folds need act = ELU, M and N multiples of 128";
     for (int g = 0; g < groups; g++)
         if (!x[g] || !w[g] || !b[g] || !y[g] || (ln_s && (!ln_s[g] || !ln_stat_in[g])) || (ln_part_out && !ln_part_out[g]))
@@ -681,6 +681,33 @@ static inline std::string check_marl_heads_act(int32_t groups, int64_t M, int32_
             return "mms_marl_heads_act: null pointer in a group, or outputs outside 1..16";
         if (out_pitch && out_pitch[g] < A[g]) return "mms_marl_heads_act: out_pitch below the number of outputs";
     }
+    return {};
+}
+
+// mms_gru_group.  A workgroup writes its rows of h_out / y while others still read those rows of x and h: no destination may be one of
+// the sources (compared as pointers over all groups: the layers of one [M, recurrent_N, H] slot interleave legitimately).
+static inline std::string check_gru_group(int32_t groups, int64_t M, int32_t K, int32_t H, const float* const* x, int64_t x_pitch, const float* const* h,
+                                          int64_t h_pitch, const float* const* mask, int64_t mask_pitch, const float* const* w_ih, const float* const* w_hh,
+                                          const float* const* b_ih, const float* const* b_hh, float* const* h_out, int64_t h_out_pitch, float* const* y) {
+    std::string bad = check_groups("mms_gru_group", groups);
+    if (!bad.empty()) return bad;
+    if (!x || !h || !w_ih || !w_hh || !b_ih || !b_hh || !h_out) return "mms_gru_group: null pointer (x, h, w_ih, w_hh, b_ih, b_hh and h_out are required)";
+    if (M < 0 || M > 0x7fffffff || K < 4 || (K % 4) != 0 || H < 4 || (H % 4) != 0 || H > 1024)
+        return "mms_gru_group: bad shapes (0 <= M <= 2147483647, K and H positive multiples of 4, H <= 1024)";
+    if (x_pitch < K || h_pitch < H || h_out_pitch < H || (x_pitch % 4) != 0 || (h_pitch % 4) != 0 || (h_out_pitch % 4) != 0 || (mask && mask_pitch < 1))
+        return "mms_gru_group: bad pitches (x_pitch >= K, h_pitch >= H, h_out_pitch >= H, each a multiple of 4; mask_pitch >= 1)";
+    for (int g = 0; g < groups; g++) {
+        if (!x[g] || !h[g] || !w_ih[g] || !w_hh[g] || !b_ih[g] || !b_hh[g] || !h_out[g] || (mask && !mask[g])) return "mms_gru_group: null pointer in a group";
+        if (((addr(x[g]) | addr(h[g]) | addr(w_ih[g]) | addr(w_hh[g]) | addr(h_out[g]) | (y ? addr(y[g]) : 0)) & 15) != 0 ||
+            ((addr(b_ih[g]) | addr(b_hh[g]) | (mask ? addr(mask[g]) : 0)) & 3) != 0)
+            return "mms_gru_group: misaligned pointer in a group (x, h, w_ih, w_hh, h_out, y 16-byte aligned)";
+    }
+    for (int g = 0; g < groups; g++)
+        for (int q = 0; q < groups; q++) {
+            if (h_out[g] == h[q] || h_out[g] == x[q]) return "mms_gru_group: h_out must not be h or x (other workgroups still read those rows)";
+            if (y && y[g] && (y[g] == h[q] || y[g] == x[q] || y[g] == h_out[q])) return "mms_gru_group: y must not be h, x or h_out";
+            if (q != g && (h_out[g] == h_out[q] || (y && y[g] && y[g] == y[q]))) return "mms_gru_group: two groups share a destination";
+        }
     return {};
 }
 

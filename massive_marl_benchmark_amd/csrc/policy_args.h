@@ -17,6 +17,7 @@ struct LinearArgs {
     float* y[kMaxGroups];
     int M, N, K;
     int act;        // 0: identity, 1: ELU (alpha = 1), 2: ReLU, 3: tanh
+    int blocked;    // != 0 (mms_linear_group_act's act | 16): blocked summation over k where the generic kernel runs (linear_act_kernel)
     // LayerNorm folded into the layers on either side of it (grouped MARL inference; all NULL otherwise).
     //   part_out[g] != NULL: the epilogue also leaves, per output row, the sum and the sum of squares of its 64 activations:
     //     part_out[g][(slot * M + row) * 2 + {0, 1}], slot = 2 * column_tile + wave half, N / 64 slots -- no atomics, so the

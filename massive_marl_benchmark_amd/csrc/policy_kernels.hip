@@ -40,8 +40,12 @@ constexpr size_t kLinearLds = (size_t)2 * 2 * 128 * kPitch * sizeof(float);     
 
 // MI = 2: 128 x 128 output tile, each of the four waves a 64 x 64 quarter; MI = 1: 64 x 128 tile, each wave 32 x 64 -- twice
 // the blocks for problems whose 128-row tiling would leave CUs idle (the 8192 x 256 layers of the DDPG / TD3 actor).
-template <int MI>
+// BLOCKED (opt-in, LinearArgs::blocked; MI = 1): a slice's 32 k are summed from zero and the slice's sum is added to the running one, as
+// gru_kernels.hip does it: an output sees 16 + K / 32 roundings of partial sums instead of K / 2 (K = 388: 28 instead of 194).  A
+// recurrent policy carries a layer's error from step to step in its state; its layers ask for this.  Not BLOCKED: the code as it was.
+template <int MI, bool BLOCKED = false>
 __global__ void __launch_bounds__(256, 2) linear_act_kernel(LinearArgs a) {
+    static_assert(!BLOCKED || MI == 1, "the blocked form holds one accumulator pair per wave");
     constexpr int TM = 64 * MI;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int g = blockIdx.z;
@@ -90,6 +94,23 @@ __global__ void __launch_bounds__(256, 2) linear_act_kernel(LinearArgs a) {
     auto multiply_slice = [&](int buf) {
         const float* a_base = As + ((size_t)buf * 128 + wr + li) * kPitch + 4 * lh;
         const float* b_base = Bs + ((size_t)buf * 128 + wc + li) * kPitch + 4 * lh;
+        if (BLOCKED) {                                      // (MI = 1) the slice summed from zero, then added
+            f32x16 t0 = {}, t1 = {};
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const float4 af = *reinterpret_cast<const float4*>(a_base + 8 * c);
+                const float4 b0 = *reinterpret_cast<const float4*>(b_base + 8 * c);
+                const float4 b1 = *reinterpret_cast<const float4*>(b_base + 32 * kPitch + 8 * c);
+#define MMS_STEP_B(e)                                                           \
+    t0 = __builtin_amdgcn_mfma_f32_32x32x2f32(af.e, b0.e, t0, 0, 0, 0);         \
+    t1 = __builtin_amdgcn_mfma_f32_32x32x2f32(af.e, b1.e, t1, 0, 0, 0);
+                MMS_STEP_B(x) MMS_STEP_B(y) MMS_STEP_B(z) MMS_STEP_B(w)
+#undef MMS_STEP_B
+            }
+            acc[0][0] += t0;
+            acc[0][1] += t1;
+            return;
+        }
 #pragma unroll
         for (int half = 0; half < 2; half++) {              // 16 k at a time: 8 fragment reads (32 registers), then 32 MFMAs
             float4 af[2][2], bf[2][2];
@@ -388,7 +409,7 @@ __global__ void __launch_bounds__(256, 2) linear_act_fast_kernel(LinearArgs a) {
 
 // More than 64 KB of dynamic LDS needs an opt-in per kernel and per device; remembered so that it is asked for once.
 static hipError_t allow_large_lds(const void* kernel, int slot) {
-    static bool done[18][64] = {};
+    static bool done[19][64] = {};
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -446,6 +467,11 @@ hipError_t launch_linear_act(const LinearArgs& a, int groups, hipStream_t s) {
         else if (tail && elu) MMS_LAUNCH_FAST(true, true, 1, 9)
         else if (!tail) MMS_LAUNCH_FAST(false, false, 1, 10)
         else MMS_LAUNCH_FAST(true, false, 1, 11)
+    } else if (a.blocked) {                 // 64-row tiles: one accumulator pair per wave beside the slice's own
+        auto kern = linear_act_kernel<1, true>;
+        if (hipError_t e = allow_large_lds(reinterpret_cast<const void*>(kern), 18); e != hipSuccess) return e;
+        grid.y = (a.M + 63) / 64;
+        hipLaunchKernelGGL(kern, grid, dim3(256), kLinearLds, s, a);
     } else if (small) hipLaunchKernelGGL(linear_act_kernel<1>, grid, dim3(256), kLinearLds, s, a);
     else hipLaunchKernelGGL(linear_act_kernel<2>, grid, dim3(256), kLinearLds, s, a);
 #undef MMS_LAUNCH_FAST
