@@ -25,6 +25,16 @@ class MmsError(RuntimeError):
     pass
 
 
+def h32_bytes(rows, K):
+    """Size of [rows, K] as two scaled fp16 planes (include/mms.h: MMS_H32_BYTES)."""
+    return rows * ((K + 31) // 32) * 128
+
+
+def p32_bytes(rows, K):
+    """Size of [rows, K] as three bf16 planes (include/mms.h: MMS_P32_BYTES)."""
+    return rows * ((K + 31) // 32) * 192
+
+
 def _bind(path):
     L = ctypes.CDLL(path)
     vp, ci, c64, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float

@@ -213,7 +213,7 @@ class GroupedPolicyInference:
         both = self.a_blocks + self.c_blocks
         split = self.split_layers and self.fold_layernorm and self.sobs_dim % 4 == 0 and H % 128 == 0 and not self.recurrent_N
         h16 = self.split_format == "f16x2"
-        pbytes = lambda N, K: N * ((K + 31) // 32) * (128 if h16 else 192)
+        pbytes = _lib.h32_bytes if h16 else _lib.p32_bytes
         u8 = lambda G, N, K: [torch.empty(pbytes(N, K), dtype=torch.uint8, device=dev) for _ in range(G)]
         D = {"split": split, "w1_a": z(n, H, self.kp_a), "w1_c": z(n, H, self.kp_c), "std": z(n, A), "fold": {}, "calls": [], "scale_jobs": []}
         up = lambda ts: (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
@@ -455,7 +455,7 @@ class GroupedPolicyInference:
         }
         if self._sp is not None and M % 128 == 0:
             h16 = self.split_format == "f16x2"
-            u8 = lambda g, rows, K: [torch.empty(rows * ((K + 31) // 32) * (128 if h16 else 192), dtype=torch.uint8, device=dev) for _ in range(g)]
+            u8 = lambda g, rows, K: [torch.empty((_lib.h32_bytes if h16 else _lib.p32_bytes)(rows, K), dtype=torch.uint8, device=dev) for _ in range(g)]
             self.sx_a, self.sx_c = u8(n, M, self.obs_dim), u8(n, M, self.sobs_dim)
             self.sh = [u8(2 * n, M, H), u8(2 * n, M, H)]
             self.stat_a = z(n, M, 2)

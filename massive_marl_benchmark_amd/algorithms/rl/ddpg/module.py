@@ -81,8 +81,6 @@ _MAX_GROUPS = 32         # include/mms.h: MMS_MAX_GROUPS
 _last_split16 = None     # the launch arguments of a split16_hidden call without a scratch dict: referenced until the next one
 
 
-def _h32_bytes(rows, K):
-    return rows * ((K + 31) // 32) * 128       # include/mms.h: MMS_H32_BYTES
 
 
 class _Split16Owner:
@@ -171,10 +169,10 @@ def split16_hidden(nets, x_or_pair, scratch=None):
     if buf is None:
         f32 = lambda *s: torch.empty(*s, device=dev)
         u8 = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)
-        buf = {"w": [[(u8(_h32_bytes(N, K)), f32(N), f32(N), f32(N)) for N, K in shapes] for _ in range(G)],     # planes, scale, inv, l1
+        buf = {"w": [[(u8(_lib.h32_bytes(N, K)), f32(N), f32(N), f32(N)) for N, K in shapes] for _ in range(G)],     # planes, scale, inv, l1
                "chain": torch.zeros(G, max(Lh, 1), 2, device=dev),
-               "x": u8(_h32_bytes(M, K_in)), "xs": f32(M), "xi": f32(M), "cs": f32(G, max(Lh, 1), M), "ci": f32(G, max(Lh, 1), M),
-               "h": [[u8(_h32_bytes(M, N)) for N, _ in shapes[:-1]] for _ in range(G)]}
+               "x": u8(_lib.h32_bytes(M, K_in)), "xs": f32(M), "xi": f32(M), "cs": f32(G, max(Lh, 1), M), "ci": f32(G, max(Lh, 1), M),
+               "h": [[u8(_lib.h32_bytes(M, N)) for N, _ in shapes[:-1]] for _ in range(G)]}
         holder[key] = buf
     out = [torch.empty(M, shapes[-1][0], device=dev) for _ in range(G)]
     vp = ctypes.c_void_p

@@ -152,10 +152,6 @@ class ActorCritic(nn.Module):
                 and all(l.weight.dtype == torch.float32 and l.in_features % 4 == 0 and l.bias is not None for l in lin[:-1]))
 
     # -- split-operand layers ------------------------------------------------------------------
-    @staticmethod
-    def _p32_bytes(rows, K):
-        return rows * ((K + 31) // 32) * 192               # MMS_P32_BYTES (include/mms.h)
-
     def _weight_planes(self, lin, L, idx, stream, force=False):
         """P32 planes of a Linear layer's weight (a buffer allocated once per layer), re-split when the parameter has changed (its version
         counter moves with every in-place optimizer step), has moved, or refresh() asks (force)."""
@@ -166,17 +162,13 @@ class ActorCritic(nn.Module):
         hit = self._wplanes.get(id(lin))
         if force or hit is None or hit[0] != tag:
             planes = hit[1] if hit is not None and hit[1].device == w.device else \
-                torch.empty(self._p32_bytes(lin.out_features, lin.in_features), dtype=torch.uint8, device=w.device)
+                torch.empty(_lib.p32_bytes(lin.out_features, lin.in_features), dtype=torch.uint8, device=w.device)
             wc = w.contiguous()
             _lib.check(L.mms_split_planes(idx, lin.out_features, lin.in_features, 0, ctypes.c_void_p(wc.data_ptr()),
                                           ctypes.c_void_p(planes.data_ptr()), stream), None, "mms_split_planes", L)
             self._wplanes[id(lin)] = (tag, planes, lin)
             return planes
         return hit[1]
-
-    @staticmethod
-    def _h32_bytes(rows, K):
-        return rows * ((K + 31) // 32) * 128               # MMS_H32_BYTES (include/mms.h)
 
     # -- two scaled fp16 planes per operand: everything derived from the parameters lives at a STABLE address and is rebuilt by device
     #    work only (refresh), so that a hipGraph of a rollout that starts with refresh() follows every optimizer step ---------------------
@@ -208,7 +200,7 @@ class ActorCritic(nn.Module):
             for l in net:
                 assert l.weight.dtype == torch.float32 and l.weight.is_contiguous() and l.bias is not None and l.weight.device == dev
                 N, K = l.out_features, l.in_features
-                rs.append({"lin": l, "N": N, "K": K, "planes": torch.empty(self._h32_bytes(N, K), dtype=torch.uint8, device=dev),
+                rs.append({"lin": l, "N": N, "K": K, "planes": torch.empty(_lib.h32_bytes(N, K), dtype=torch.uint8, device=dev),
                            "scale": torch.empty(N, device=dev), "inv": torch.empty(N, device=dev), "l1": torch.empty(N, device=dev)})
             recs.append(rs)
             slices.append((off, max(len(net) - 1, 0)))
@@ -378,9 +370,9 @@ class ActorCritic(nn.Module):
         f32 = lambda *sh: torch.empty(*sh, device=dev)
         u8 = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)
         if bufs is None:
-            bufs = {"x": [u8(self._h32_bytes(M, x.shape[1])) for x in inputs], "xs": [f32(M) for _ in range(G)], "xi": [f32(M) for _ in range(G)],
+            bufs = {"x": [u8(_lib.h32_bytes(M, x.shape[1])) for x in inputs], "xs": [f32(M) for _ in range(G)], "xi": [f32(M) for _ in range(G)],
                     "cs": [f32(G, max(nl - 1, 1), M) for _ in range(G)], "ci": [f32(G, max(nl - 1, 1), M) for _ in range(G)],
-                    "h": [[u8(self._h32_bytes(M, r["N"])) for _ in range(G)] for r in recs[0][:-1]],
+                    "h": [[u8(_lib.h32_bytes(M, r["N"])) for _ in range(G)] for r in recs[0][:-1]],
                     "out": [f32(M, recs[0][-1]["N"]) for _ in range(G)], "keep": []}
             self._split_bufs[key] = bufs
         arr = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
@@ -409,7 +401,7 @@ class ActorCritic(nn.Module):
                 # recurrence (mms_chain_scales16), re-evaluated by refresh(); the buffers belong to (networks, rows, scale)
                 pl, scale = planes
                 scale = float(scale)
-                assert pl.dtype == torch.uint8 and pl.numel() == self._h32_bytes(M, x.shape[1]) and pl.device == dev
+                assert pl.dtype == torch.uint8 and pl.numel() == _lib.h32_bytes(M, x.shape[1]) and pl.device == dev
                 gm = tuple(members[g] for g in grp)
                 gkey = (gm, M, scale)
                 if gkey not in st["given"]:
@@ -481,8 +473,8 @@ class ActorCritic(nn.Module):
         bufs = self._split_bufs.get(key)
         if bufs is None:
             u8 = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)
-            bufs = {"x": [u8(self._p32_bytes(M, K)) for _ in range(G)],
-                    "h": [[u8(self._p32_bytes(M, l.out_features)) for _ in range(G)] for l in nets[0][:-1]],
+            bufs = {"x": [u8(_lib.p32_bytes(M, K)) for _ in range(G)],
+                    "h": [[u8(_lib.p32_bytes(M, l.out_features)) for _ in range(G)] for l in nets[0][:-1]],
                     "out": [torch.empty(M, nets[0][-1].out_features, device=dev) for _ in range(G)]}
             self._split_bufs[key] = bufs
         arr = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../mms_lane.h"
+#include "../planes16_lane.h"
 
 namespace mms {
 
@@ -63,6 +64,12 @@ static inline float h2f(uint16_t h) {
     memcpy(&f, &u, 4);
     return f;
 }
+// one element of an H32 plane row (planes16_lane.h) at c = planes16_elem(...): t = x s in, the number the two planes stand for out
+static inline void planes16_put(uint16_t* c, float t) {
+    c[0] = f2h(t);
+    c[32] = f2h(planes16_lo(t, h2f(c[0])));
+}
+static inline float planes16_get(const uint16_t* c) { return planes16_join(h2f(c[0]), h2f(c[32])); }
 
 // The engine's buffers (include/mms.h: mms_get_tensor names).  obs / obs_clipped / obs_out / rew_out / done_out may be NULL
 // (mms_set_obs_outputs, mms_bind_obs_out, mms_bind_rollout_out); dr is NULL unless mms_set_dr(h, 1).
@@ -236,14 +243,10 @@ static void host_ant_env(const mms_config* C, const HostBufs& b, int env, int do
         if (b.obs_clipped) b.obs_clipped[(size_t)env * obs_dim + i] = c;
         if (b.obs_out) b.obs_out[(size_t)env * obs_dim + i] = c;
     }
-    if (b.obs_planes) {                                                 // as the epilogue of ant_step_kernel
+    if (b.obs_planes) {                                                 // the clamped row under a constant scale (planes16_lane.h)
         const int KC = (obs_dim + 31) / 32;
-        for (int k = 0; k < KC * 32; k++) {
-            const float t = k < obs_dim ? clampf(s_obs[k], -C->clip_obs, C->clip_obs) * b.obs_planes_scale : 0.f;
-            uint16_t* c = b.obs_planes + ((size_t)env * KC + k / 32) * 64 + k % 32;
-            c[0] = f2h(t);
-            c[32] = f2h((t - h2f(c[0])) * 2048.f);
-        }
+        for (int k = 0; k < KC * 32; k++)
+            planes16_put(planes16_elem(b.obs_planes, env, KC, k), k < obs_dim ? clampf(s_obs[k], -C->clip_obs, C->clip_obs) * b.obs_planes_scale : 0.f);
     }
 }
 

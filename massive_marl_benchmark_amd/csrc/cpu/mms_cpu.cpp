@@ -623,42 +623,38 @@ MMS_API int mms_linear_group_act_split(int device, int32_t groups, int64_t M, in
 }
 
 // ---- the same with two scaled fp16 planes per operand (csrc/split16_kernels.hip), format H32 = f16 [rows, KC, 2, 32] -------------------
-using mms::f2h;
-using mms::h2f;
-static inline void pow2_scale(float bound, float& scale, float& inv) {    // as split16_kernels.hip
-    int e = 14;
-    if (bound > 0.f) (void)frexpf(bound, &e);
-    int sh = 14 - e;
-    sh = sh > 100 ? 100 : (sh < -100 ? -100 : sh);
-    scale = ldexpf(1.f, sh);
-    inv = ldexpf(1.f, -sh);
+// The format and its bound rules: planes16_lane.h; one element in and out: planes16_put / planes16_get (lane_step.h).
+using mms::chain_scales;
+using mms::planes16_elem;
+using mms::planes16_get;
+using mms::planes16_put;
+using mms::pow2_scale;
+
+// One row -> its planes (planes may be NULL) and its power-of-two scale: the largest magnitude, then 32 k at a time under that scale,
+// the tail zero.  at(k) = element k of the row, k < K; the same value at every call.  Returns the largest magnitude.
+template <class At>
+static float split_row16(uint16_t* planes, int64_t r, int K, At at, float& sc, float& iv) {
+    const int KC = (K + 31) / 32;
+    float big = 0.f;
+    for (int k = 0; k < K; k++) big = fmaxf(big, fabsf(at(k)));
+    pow2_scale(big, sc, iv);
+    for (int k = 0; k < KC * 32 && planes; k++) planes16_put(planes16_elem(planes, r, KC, k), k < K ? at(k) * sc : 0.f);
+    return big;
 }
-static inline void split2(float t, uint16_t* hi, uint16_t* lo) {
-    *hi = f2h(t);
-    *lo = f2h((t - h2f(*hi)) * 2048.f);
+// ... and the scales of the layers behind row r, from its bound
+static void chain_rows16(int32_t nchains, int32_t L, const float* chain, float bound, float* chain_scale, float* chain_inv, int64_t rows, int64_t r) {
+    for (int c = 0; c < nchains; c++) chain_scales(chain + (size_t)c * L * 2, c, L, bound, chain_scale, chain_inv, rows, r);
 }
-static inline float join2(const uint16_t* chunk, int j) { return h2f(chunk[j]) + h2f(chunk[32 + j]) * (1.f / 2048.f); }
 
 static void split_planes16_rows(int32_t groups, int64_t rows, int32_t K, int32_t x_pitch, const float* const* x, void* const* planes, float* const* scale,
                                 float* const* inv, int32_t nchains, int32_t L, const float* const* chain, float* const* chain_scale,
                                 float* const* chain_inv, float* const* stat, float eps) {
-    const int KC = (K + 31) / 32;
     for (int g = 0; g < groups; g++) {
-        uint16_t* out = (uint16_t*)planes[g];
         const float* xg = x[g];
 #pragma omp parallel for schedule(static)
         for (int64_t r = 0; r < rows; r++) {
-            float big = 0.f;
-            for (int k = 0; k < K; k++) big = fmaxf(big, fabsf(xg[r * x_pitch + k]));
             float sc, iv;
-            pow2_scale(big, sc, iv);
-            for (int kc = 0; kc < KC; kc++) {
-                uint16_t* c = out + (r * KC + kc) * 64;
-                for (int j = 0; j < 32; j++) {
-                    const int k = kc * 32 + j;
-                    split2(k < K ? xg[r * x_pitch + k] * sc : 0.f, c + j, c + 32 + j);
-                }
-            }
+            const float big = split_row16((uint16_t*)planes[g], r, K, [&](int k) { return xg[r * x_pitch + k]; }, sc, iv);
             if (scale[g]) scale[g][r] = sc;
             if (inv[g]) inv[g][r] = iv;
             if (stat) {                                                   // two-pass LayerNorm statistics of the row
@@ -669,16 +665,7 @@ static void split_planes16_rows(int32_t groups, int64_t rows, int32_t K, int32_t
                 stat[g][2 * r] = mean;
                 stat[g][2 * r + 1] = 1.0f / sqrtf(m2 / (float)K + eps);
             }
-            for (int c = 0; c < nchains; c++) {
-                float bound = big;
-                for (int l = 0; l < L; l++) {
-                    bound = (chain[g][((size_t)c * L + l) * 2] * bound + chain[g][((size_t)c * L + l) * 2 + 1]) * 1.001f;
-                    float s2, i2;
-                    pow2_scale(bound, s2, i2);
-                    chain_scale[g][((size_t)c * L + l) * rows + r] = s2;
-                    chain_inv[g][((size_t)c * L + l) * rows + r] = i2;
-                }
-            }
+            if (nchains > 0) chain_rows16(nchains, L, chain[g], big, chain_scale[g], chain_inv[g], rows, r);
         }
     }
 }
@@ -693,8 +680,8 @@ MMS_API int mms_split_planes16_group(int device, int32_t groups, int64_t rows, i
     return 0;
 }
 
-// The same for rows that are the concatenation of two sources (include/mms.h): split_planes16_rows' statement with element k of a row read
-// from x0 (k < K0) or x1 -- operation by operation what it does on the materialised concatenation, hence the same bits.
+// The same for rows that are the concatenation of two sources (include/mms.h): element k of a row is read from x0 (k < K0) or x1 --
+// operation by operation what split_planes16_rows does on the materialised concatenation, hence the same bits.
 MMS_API int mms_split_planes16_cat(int device, int64_t rows, int32_t K0, int32_t pitch0, const float* x0, int32_t K1, int32_t pitch1, const float* x1,
                                    void* planes, float* scale, float* inv, int32_t nchains, int32_t L, const float* chain, float* chain_scale,
                                    float* chain_inv, void*) {
@@ -702,35 +689,13 @@ MMS_API int mms_split_planes16_cat(int device, int64_t rows, int32_t K0, int32_t
     if (pitch0 == 0) pitch0 = K0;
     if (pitch1 == 0) pitch1 = K1;
     if (refused(check_split_planes16_cat(rows, K0, pitch0, x0, K1, pitch1, x1, planes, nchains, L, chain, chain_scale, chain_inv))) return 1;
-    const int K = K0 + K1, KC = (K + 31) / 32;
-    uint16_t* out = (uint16_t*)planes;
 #pragma omp parallel for schedule(static)
     for (int64_t r = 0; r < rows; r++) {
-        float big = 0.f;
-        for (int k = 0; k < K0; k++) big = fmaxf(big, fabsf(x0[r * pitch0 + k]));
-        for (int k = 0; k < K1; k++) big = fmaxf(big, fabsf(x1[r * pitch1 + k]));
         float sc, iv;
-        pow2_scale(big, sc, iv);
-        for (int kc = 0; kc < KC; kc++) {
-            uint16_t* c = out + (r * KC + kc) * 64;
-            for (int j = 0; j < 32; j++) {
-                const int k = kc * 32 + j;
-                const float v = k < K0 ? x0[r * pitch0 + k] : (k < K ? x1[r * pitch1 + (k - K0)] : 0.f);
-                split2(v * sc, c + j, c + 32 + j);
-            }
-        }
+        const float big = split_row16((uint16_t*)planes, r, K0 + K1, [&](int k) { return k < K0 ? x0[r * pitch0 + k] : x1[r * pitch1 + (k - K0)]; }, sc, iv);
         if (scale) scale[r] = sc;
         if (inv) inv[r] = iv;
-        for (int c = 0; c < nchains; c++) {
-            float bound = big;
-            for (int l = 0; l < L; l++) {
-                bound = (chain[((size_t)c * L + l) * 2] * bound + chain[((size_t)c * L + l) * 2 + 1]) * 1.001f;
-                float s2, i2;
-                pow2_scale(bound, s2, i2);
-                chain_scale[((size_t)c * L + l) * rows + r] = s2;
-                chain_inv[((size_t)c * L + l) * rows + r] = i2;
-            }
-        }
+        chain_rows16(nchains, L, chain, big, chain_scale, chain_inv, rows, r);
     }
     return 0;
 }
@@ -782,18 +747,7 @@ MMS_API int mms_chain_refresh16(int device, int32_t nchains, int32_t L, const fl
         chain[2 * e] = m;
         chain[2 * e + 1] = b;
     }
-    for (int c = 0; c < nchains && rows > 0; c++) {
-        float bound = bound0;
-        for (int l = 0; l < L; l++) {
-            bound = (chain[((size_t)c * L + l) * 2] * bound + chain[((size_t)c * L + l) * 2 + 1]) * 1.001f;
-            float sc, iv;
-            pow2_scale(bound, sc, iv);
-            for (int64_t r = 0; r < rows; r++) {
-                chain_scale[((size_t)c * L + l) * rows + r] = sc;
-                chain_inv[((size_t)c * L + l) * rows + r] = iv;
-            }
-        }
-    }
+    for (int64_t r = 0; r < rows; r++) chain_rows16(nchains, L, chain, bound0, chain_scale, chain_inv, rows, r);
     return 0;
 }
 
@@ -804,37 +758,30 @@ MMS_API int mms_fold_planes16_group(int device, int32_t groups, const int64_t* N
     if (cpu_only(device)) return 1;
     if (refused(check_fold_planes16_group(groups, N, K, w, planes, inv))) return 1;
     for (int g = 0; g < groups; g++) {
-        const int Kg = K[g], KC = (Kg + 31) / 32;
+        const int Kg = K[g];
         const float* gm = gamma ? gamma[g] : nullptr;
         const float* bt = beta ? beta[g] : nullptr;
         uint16_t* out = planes ? (uint16_t*)planes[g] : nullptr;
 #pragma omp parallel for schedule(static)
         for (int64_t r = 0; r < N[g]; r++) {
             const float* wr = w[g] + r * Kg;
-            float big = 0.f, s = 0.f, c = 0.f, l2 = 0.f;
+            const auto wt_at = [&](int k) { return gm ? wr[k] * gm[k] : wr[k]; };            // W~[r, k]
+            float s = 0.f, c = 0.f, l2 = 0.f;
             for (int k = 0; k < Kg; k++) {
-                const float v = gm ? wr[k] * gm[k] : wr[k];
-                big = fmaxf(big, fabsf(v));
+                const float v = wt_at(k);
                 s += v;
                 l2 += v * v;
                 if (bt) c += wr[k] * bt[k];
             }
             if (bias && bias[g]) c += bias[g][r];
             float sc, iv;
-            pow2_scale(big, sc, iv);
-            for (int kc = 0; kc < KC && out; kc++) {
-                uint16_t* ch = out + (r * KC + kc) * 64;
-                for (int j = 0; j < 32; j++) {
-                    const int k = kc * 32 + j;
-                    split2(k < Kg ? (gm ? wr[k] * gm[k] : wr[k]) * sc : 0.f, ch + j, ch + 32 + j);
-                }
-            }
+            split_row16(out, r, Kg, wt_at, sc, iv);
             if (wt && wt[g])
-                for (int k = 0; k < Kg; k++) wt[g][r * Kg + k] = gm ? wr[k] * gm[k] : wr[k];
+                for (int k = 0; k < Kg; k++) wt[g][r * Kg + k] = wt_at(k);
             if (inv && inv[g]) inv[g][r] = iv;
             if (s_out && s_out[g]) s_out[g][r] = s;
             if (c_out && c_out[g]) c_out[g][r] = c;
-            if (rb && rb[g]) rb[g][r] = sqrtf(l2) * sqrtf((float)Kg) + fabsf(c);
+            if (rb && rb[g]) rb[g][r] = mms::fold_row_bound(l2, Kg, c);
         }
     }
     return 0;
@@ -847,10 +794,8 @@ MMS_API int mms_fold_scales16_group(int device, int32_t groups, const float* con
     for (int g = 0; g < groups; g++) {
         float m = 0.f;
         for (int i = 0; i < n[g]; i++) m = fmaxf(m, rb[g][i]);
-        float bound = m * 1.001f;
-        if (!(bound > 1e-30f)) bound = 1e-30f;
         float sc, iv;
-        pow2_scale(bound, sc, iv);
+        pow2_scale(mms::fold_net_bound(m), sc, iv);
         if (scale1 && scale1[g]) scale1[g][0] = sc;
         for (int64_t r = 0; r < M; r++) {
             if (ysc && ysc[g]) ysc[g][r] = sc;
@@ -874,21 +819,18 @@ MMS_API int mms_linear_group_act_split16(int device, int32_t groups, int64_t M, 
         const uint16_t* wp = (const uint16_t*)w[g];
         std::vector<float> wf((size_t)N * KC * 32);
         for (int64_t n = 0; n < N; n++)
-            for (int k = 0; k < KC * 32; k++) wf[n * KC * 32 + k] = join2(wp + (n * KC + k / 32) * 64, k % 32);
+            for (int k = 0; k < KC * 32; k++) wf[n * KC * 32 + k] = planes16_get(planes16_elem(wp, n, KC, k));
         void* yg = out_mode != 2 ? y[g] : nullptr;
         const float* xi = x_inv[g];
         const float* wi = w_inv[g];
         const float* ys = out_mode == 1 ? y_scale[g] : nullptr;
         split_layer_rows(M, N, KC, wf, b[g], act, out_mode, ln ? ln_s[g] : nullptr, ln ? ln_stat_in[g] : nullptr, ln ? ln_part_out[g] : nullptr,
                          out_mode == 2 ? head_w[g] : nullptr, out_mode == 2 ? head_part[g] : nullptr, out_mode == 2 ? head_dims[g] : 0,
-                         [&](int64_t m, float* xr) { for (int k = 0; k < KC * 32; k++) xr[k] = join2(xp + (m * KC + k / 32) * 64, k % 32); },
+                         [&](int64_t m, float* xr) { for (int k = 0; k < KC * 32; k++) xr[k] = planes16_get(planes16_elem(xp, m, KC, k)); },
                          [&](int64_t m, int n) { return wi[n] * xi[m]; },
                          [&](int64_t m, const float* row) {
                              if (out_mode == 1) {
-                                 for (int n = 0; n < N; n++) {
-                                     uint16_t* c = (uint16_t*)yg + (m * NC + n / 32) * 64 + n % 32;
-                                     split2(row[n] * ys[m], c, c + 32);
-                                 }
+                                 for (int n = 0; n < N; n++) planes16_put(planes16_elem((uint16_t*)yg, m, NC, n), row[n] * ys[m]);
                              } else {
                                  memcpy((float*)yg + m * N, row, (size_t)N * 4);
                              }

@@ -14,20 +14,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "planes16_lane.h"
 #include "policy_args.h"
 
 namespace mms {
 
 typedef _Float16 fold_f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void fold_pow2_scale(float bound, float& scale, float& inv) {      // as pow2_scale of split16_kernels.hip
-    int e = 14;
-    if (bound > 0.f) (void)frexpf(bound, &e);
-    int sh = 14 - e;
-    sh = sh > 100 ? 100 : (sh < -100 ? -100 : sh);
-    scale = ldexpf(1.f, sh);
-    inv = ldexpf(1.f, -sh);
-}
 
 // One wave per row (64 lanes walk the row's 8-element pieces, two passes as split16_planes_kernel), four rows per block,
 // blockIdx.y = network.  Matrices of different shapes in one launch (rows_g / K_g per network).
@@ -78,7 +70,7 @@ __global__ void __launch_bounds__(256) fold_planes16_kernel(FoldPlanesArgs a) {
     }
     if (a.bias[g]) c += a.bias[g][row];
     float scale, inv;
-    fold_pow2_scale(big, scale, inv);
+    pow2_scale(big, scale, inv);
     uint8_t* __restrict__ out = reinterpret_cast<uint8_t*>(a.planes[g]);
     float* __restrict__ wt_out = a.wt[g];
     for (int p = lane; p < pieces; p += 64) {
@@ -91,7 +83,7 @@ __global__ void __launch_bounds__(256) fold_planes16_kernel(FoldPlanesArgs a) {
             const float wt = gam ? v[j] * gm[j] : v[j];
             const float t = wt * scale;
             hi[j] = (_Float16)t;
-            lo[j] = (_Float16)((t - (float)hi[j]) * 2048.f);
+            lo[j] = (_Float16)planes16_lo(t, (float)hi[j]);
             if (!ALIGNED && wt_out && live && p * 8 + j < K) wt_out[row * (int64_t)K + p * 8 + j] = wt;
             v[j] = wt;
         }
@@ -106,7 +98,7 @@ __global__ void __launch_bounds__(256) fold_planes16_kernel(FoldPlanesArgs a) {
             }
         }
         if (out && live) {
-            uint8_t* dst = out + (row * KC + (p >> 2)) * (int64_t)128 + (p & 3) * 16;
+            uint8_t* dst = out + (row * KC + (p >> 2)) * (int64_t)kChunk16 + (p & 3) * 16;    // planes16_piece, written out: the call changes this kernel's registers
             *reinterpret_cast<fold_f16x8*>(dst) = hi;
             *reinterpret_cast<fold_f16x8*>(dst + 64) = lo;
         }
@@ -115,7 +107,7 @@ __global__ void __launch_bounds__(256) fold_planes16_kernel(FoldPlanesArgs a) {
         if (a.inv[g]) a.inv[g][row] = inv;
         if (a.s[g]) a.s[g][row] = s;
         if (a.c[g]) a.c[g][row] = c;
-        if (a.rb[g]) a.rb[g][row] = sqrtf(l2) * sqrtf((float)K) + fabsf(c);
+        if (a.rb[g]) a.rb[g][row] = fold_row_bound(l2, K, c);
     }
 }
 
@@ -151,10 +143,8 @@ __global__ void __launch_bounds__(256) fold_scales16_kernel(FoldScalesArgs a) {
     if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
     __syncthreads();
     m = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-    float bound = m * 1.001f;
-    if (!(bound > 1e-30f)) bound = 1e-30f;
     float sc, iv;
-    fold_pow2_scale(bound, sc, iv);
+    pow2_scale(fold_net_bound(m), sc, iv);
     if (blockIdx.x == 0 && threadIdx.x == 0 && a.scale1[g]) a.scale1[g][0] = sc;
     const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (row < a.M) {

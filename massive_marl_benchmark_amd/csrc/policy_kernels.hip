@@ -7,10 +7,7 @@
 // quarter as 2 x 2 MFMA tiles (64 accumulator registers); K is walked in slices of 32 through LDS, double buffered -- the
 // global loads of slice k+1 are in flight while the 64 MFMAs of slice k issue (4096 cycles per wave), one barrier per slice.
 // Both networks (blockIdx.z) and all tiles of a layer make 512 blocks at M = 4096, N = 1024: two resident blocks per CU.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
+#include "layer_common.h"
 #include "mms_lane.h"
 #include "policy_args.h"
 
@@ -19,15 +16,6 @@ namespace mms {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kTM = 128, kTN = 128;
-
-// epilogue activation (uniform per launch): 0 identity, 1 ELU (alpha = 1, torch.nn.ELU), 2 ReLU, 3 tanh
-__device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == 1) return (v > 0.f) ? v : (expf(v) - 1.f);
-    if (act == 2) return fmaxf(v, 0.f);
-    if (act == 3) return 1.f - 2.f / (__expf(2.f * v) + 1.f);     // tanh, absolute error ~1e-7; a few instructions where it is inlined 64 times
-    return v;
-}
-
 
 // LDS layout: both operand tiles row-major, [128 rows][32 k + 4 pad] -- exactly how they arrive from HBM, so staging is a plain
 // 16-B store per 16-B load.  The MFMA wants lane (i, h) to supply A[i][k] for ONE k per instruction; which k it supplies in
@@ -167,7 +155,7 @@ __global__ void __launch_bounds__(256, 2) linear_act_kernel(LinearArgs a) {
             for (int r = 0; r < 16; r++) {
                 const int row = m0 + wr + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 float v = acc[i][j][r] + bias;
-                v = apply_act(v, a.act);
+                v = act_apply(v, a.act);
                 if (row < M && col < N) Y[(size_t)row * N + col] = v;
             }
         }
@@ -339,7 +327,7 @@ __global__ void __launch_bounds__(256, 2) linear_act_fast_kernel(LinearArgs a) {
         float* yp = Y + (size_t)(m0 + wr + 32 * (I) + 4 * lh) * N + col;                                     \
         _Pragma("unroll") for (int r = 0; r < 16; r++) {                                                     \
             float v = ACC[r] + bias;                                                                         \
-            v = ELU_ONLY ? ((v > 0.f) ? v : (expf(v) - 1.f)) : apply_act(v, a.act);                          \
+            v = ELU_ONLY ? ((v > 0.f) ? v : (expf(v) - 1.f)) : act_apply(v, a.act);                          \
             yp[(size_t)((r & 3) + 8 * (r >> 2)) * N] = v;                                                    \
         }                                                                                                    \
     }
@@ -407,25 +395,13 @@ __global__ void __launch_bounds__(256, 2) linear_act_fast_kernel(LinearArgs a) {
 #undef MMS_MFMA4
 #undef MMS_FRAGS
 
-// More than 64 KB of dynamic LDS needs an opt-in per kernel and per device; remembered so that it is asked for once.
-static hipError_t allow_large_lds(const void* kernel, int slot) {
-    static bool done[19][64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64 || !done[slot][dev]) {
-        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) done[slot][dev] = true;
-    }
-    return hipSuccess;
-}
+constexpr size_t kLdsOptIn = 160 * 1024;        // what these kernels ask allow_large_lds for: the whole LDS of a CU
 
 hipError_t launch_linear_act(const LinearArgs& a, int groups, hipStream_t s) {
     if (a.M == 0 || a.N == 0) return hipSuccess;
     dim3 grid((a.N + kTN - 1) / kTN, (a.M + kTM - 1) / kTM, groups);
-    if (hipError_t e = allow_large_lds(reinterpret_cast<const void*>(linear_act_kernel<2>), 2); e != hipSuccess) return e;
-    if (hipError_t e = allow_large_lds(reinterpret_cast<const void*>(linear_act_kernel<1>), 5); e != hipSuccess) return e;
+    if (hipError_t e = allow_large_lds<linear_act_kernel<2>>(kLdsOptIn); e != hipSuccess) return e;
+    if (hipError_t e = allow_large_lds<linear_act_kernel<1>>(kLdsOptIn); e != hipSuccess) return e;
     // 128-row tiles that would leave CUs without a block: 64-row tiles, twice the blocks.  (At exactly one block per CU -- the
     // policy's 512-wide layer -- both tilings measure the same, 72-78 us: the fixed cost of a launch dominates, not the slice rate.)
     static const int small_max = getenv("MMS_LINEAR_SMALL_MAX") ? atoi(getenv("MMS_LINEAR_SMALL_MAX")) : 255;
@@ -434,42 +410,42 @@ hipError_t launch_linear_act(const LinearArgs& a, int groups, hipStream_t s) {
     const bool small = (size_t)grid.x * grid.y * grid.z <= (size_t)small_max && a.M > 64 && !getenv("MMS_LINEAR_TALL_TILES") && !ln_out && !ln_in;
     const bool fast = a.M % (small ? 64 : kTM) == 0 && a.N % kTN == 0 && a.K >= 8 && !getenv("MMS_LINEAR_GENERIC");
     if (small) grid.y = (a.M + 63) / 64;
-#define MMS_LAUNCH_FAST(TAIL, ELU, MI, SLOT)                                                                                   \
+#define MMS_LAUNCH_FAST(TAIL, ELU, MI)                                                                                         \
     {                                                                                                                          \
         auto kern = linear_act_fast_kernel<TAIL, ELU, MI>;                                                                     \
-        if (hipError_t e = allow_large_lds(reinterpret_cast<const void*>(kern), SLOT); e != hipSuccess) return e;              \
+        if (hipError_t e = allow_large_lds<linear_act_fast_kernel<TAIL, ELU, MI>>(kLdsOptIn); e != hipSuccess) return e;       \
         hipLaunchKernelGGL(kern, dim3(grid.x * grid.y * grid.z), dim3(256), kLinearLds, s, a);                                 \
     }
-#define MMS_LAUNCH_FAST_LN(TAIL, LNF, SLOT)                                                                                     \
+#define MMS_LAUNCH_FAST_LN(TAIL, LNF)                                                                                           \
     {                                                                                                                          \
         auto kern = linear_act_fast_kernel<TAIL, true, 2, LNF>;                                                                \
-        if (hipError_t e = allow_large_lds(reinterpret_cast<const void*>(kern), SLOT); e != hipSuccess) return e;              \
+        if (hipError_t e = allow_large_lds<linear_act_fast_kernel<TAIL, true, 2, LNF>>(kLdsOptIn); e != hipSuccess) return e;  \
         hipLaunchKernelGGL(kern, dim3(grid.x * grid.y * grid.z), dim3(256), kLinearLds, s, a);                                 \
     }
     const bool tail = a.K % kBK != 0, elu = a.act == 1;
     if (ln_out || ln_in) {                  // the LayerNorm folds: the callers (mms_linear_group_act) only ask for them where they exist
         if (!(fast && !small && elu)) return hipErrorInvalidValue;
-        if (ln_in && ln_out && tail) MMS_LAUNCH_FAST_LN(true, 3, 16)
-        else if (ln_in && tail) MMS_LAUNCH_FAST_LN(true, 2, 17)
-        else if (ln_in && ln_out) MMS_LAUNCH_FAST_LN(false, 3, 12)
-        else if (ln_in) MMS_LAUNCH_FAST_LN(false, 2, 13)
-        else if (tail) MMS_LAUNCH_FAST_LN(true, 1, 14)
-        else MMS_LAUNCH_FAST_LN(false, 1, 15)
+        if (ln_in && ln_out && tail) MMS_LAUNCH_FAST_LN(true, 3)
+        else if (ln_in && tail) MMS_LAUNCH_FAST_LN(true, 2)
+        else if (ln_in && ln_out) MMS_LAUNCH_FAST_LN(false, 3)
+        else if (ln_in) MMS_LAUNCH_FAST_LN(false, 2)
+        else if (tail) MMS_LAUNCH_FAST_LN(true, 1)
+        else MMS_LAUNCH_FAST_LN(false, 1)
         return hipGetLastError();
     }
     if (fast && !small) {
-        if (!tail && elu) MMS_LAUNCH_FAST(false, true, 2, 3)
-        else if (tail && elu) MMS_LAUNCH_FAST(true, true, 2, 4)
-        else if (!tail) MMS_LAUNCH_FAST(false, false, 2, 6)
-        else MMS_LAUNCH_FAST(true, false, 2, 7)
+        if (!tail && elu) MMS_LAUNCH_FAST(false, true, 2)
+        else if (tail && elu) MMS_LAUNCH_FAST(true, true, 2)
+        else if (!tail) MMS_LAUNCH_FAST(false, false, 2)
+        else MMS_LAUNCH_FAST(true, false, 2)
     } else if (fast) {
-        if (!tail && elu) MMS_LAUNCH_FAST(false, true, 1, 8)
-        else if (tail && elu) MMS_LAUNCH_FAST(true, true, 1, 9)
-        else if (!tail) MMS_LAUNCH_FAST(false, false, 1, 10)
-        else MMS_LAUNCH_FAST(true, false, 1, 11)
+        if (!tail && elu) MMS_LAUNCH_FAST(false, true, 1)
+        else if (tail && elu) MMS_LAUNCH_FAST(true, true, 1)
+        else if (!tail) MMS_LAUNCH_FAST(false, false, 1)
+        else MMS_LAUNCH_FAST(true, false, 1)
     } else if (a.blocked) {                 // 64-row tiles: one accumulator pair per wave beside the slice's own
         auto kern = linear_act_kernel<1, true>;
-        if (hipError_t e = allow_large_lds(reinterpret_cast<const void*>(kern), 18); e != hipSuccess) return e;
+        if (hipError_t e = allow_large_lds<linear_act_kernel<1, true>>(kLdsOptIn); e != hipSuccess) return e;
         grid.y = (a.M + 63) / 64;
         hipLaunchKernelGGL(kern, grid, dim3(256), kLinearLds, s, a);
     } else if (small) hipLaunchKernelGGL(linear_act_kernel<1>, grid, dim3(256), kLinearLds, s, a);

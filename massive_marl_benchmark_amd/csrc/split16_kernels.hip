@@ -22,19 +22,17 @@
 // does not change when the scale is lowered by 2^18).
 //
 // Plane format "H32": [rows][KC][2][32] f16, KC = ceil(K / 32): hi and lo of 32 consecutive k of a row are 128 contiguous bytes
-// (one cache line).  Columns past K are zero.
+// (one cache line).  Columns past K are zero.  The format's rules -- scale, hi / lo, offsets, bounds -- are defined in planes16_lane.h.
 //
 // Tiling as split_kernels.hip: 512-thread block = 8 waves (4 (m) x 2 (n)), output tile (64 MT) x 128, the product evaluated
 // transposed (W fragments as the A operand), persistent grid of at most one block per CU.  LDS image of a k-step: the tile's rows
 // at pitch 128 (X rows, then W rows), each row eight 16-byte slots [plane][k-group] with the slot index XORed with (row >> 1) & 7:
 // the sixteen lanes of a ds_read_b128 group (rows 0-3 / 12-15 with k-group g, rows 4-11 with k-group g +- 1) then cover the sixteen
 // slots of the 256-byte bank row exactly once.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
 #include <type_traits>
 
+#include "layer_common.h"
+#include "planes16_lane.h"
 #include "policy_args.h"
 
 namespace mms {
@@ -69,20 +67,6 @@ typedef uint32_t u32x4_16 __attribute__((ext_vector_type(4)));
 #ifndef MMS_S16_ROLL
 #define MMS_S16_ROLL 1
 #endif
-constexpr int kChunk16 = 128;                    // one row's two planes of 32 k
-constexpr float kLoScale = 2048.f;               // the lo plane holds the residual times 2^11
-constexpr int kTopExp = 14;                      // a row's bound sits at 2^14 (fp16 ends just below 2^16)
-
-// scale = 2^(14 - e) with bound <= 2^e; an all-zero row keeps scale 1
-__device__ __forceinline__ void pow2_scale(float bound, float& scale, float& inv) {
-    int e = kTopExp;
-    if (bound > 0.f) (void)frexpf(bound, &e);    // bound = f 2^e, 0.5 <= f < 1
-    int sh = kTopExp - e;
-    sh = sh > 100 ? 100 : (sh < -100 ? -100 : sh);
-    scale = ldexpf(1.f, sh);
-    inv = ldexpf(1.f, -sh);
-}
-
 // ---- fp32 [rows, K] -> H32 planes + per-row scales -----------------------------------------------------------------------------
 // P lanes per row (a power of two, 64 / P rows per wave: a 46-wide row is 8 pieces of 8 k, eight rows share a wave), two passes over
 // the row (largest magnitude and sum, then the planes and the squared deviations): the second pass finds the row in L1 / L2.
@@ -145,12 +129,12 @@ __global__ void __launch_bounds__(256) split16_planes_kernel(Split16PlanesArgs a
         for (int j = 0; j < 8; j++) {
             const float t = v[j] * scale;
             hi[j] = (_Float16)t;
-            lo[j] = (_Float16)((t - (float)hi[j]) * kLoScale);
+            lo[j] = (_Float16)planes16_lo(t, (float)hi[j]);
             const float d = (p * 8 + j < K) ? v[j] - mean : 0.f;
             m2 += d * d;
         }
         if (live) {
-            uint8_t* dst = out + (row * KC + (p >> 2)) * (int64_t)kChunk16 + (p & 3) * 16;
+            uint8_t* dst = planes16_piece(out, row, KC, p);
             *reinterpret_cast<f16x8*>(dst) = hi;
             *reinterpret_cast<f16x8*>(dst + 64) = lo;
         }
@@ -168,8 +152,8 @@ __global__ void __launch_bounds__(256) split16_planes_kernel(Split16PlanesArgs a
         for (int c = sub; c < a.nchains; c += P) {
             const float* ch = a.chain[g] + (size_t)c * a.L * 2;
             float bound = big;
-            for (int l = 0; l < a.L; l++) {
-                bound = (ch[2 * l] * bound + ch[2 * l + 1]) * 1.001f;   // (rounding of the bound itself; 2^14 leaves a factor 4 besides)
+            for (int l = 0; l < a.L; l++) {                             // chain_scales, written out: the call changes this kernel's code
+                bound = chain_bound(ch[2 * l], bound, ch[2 * l + 1]);
                 float sc, iv;
                 pow2_scale(bound, sc, iv);
                 a.chain_scale[g][((size_t)c * a.L + l) * rows + row] = sc;
@@ -266,10 +250,10 @@ __global__ void __launch_bounds__(256) split16_cat_kernel(Split16CatArgs a, int 
         for (int j = 0; j < 8; j++) {
             const float t = v[j] * scale;
             hi[j] = (_Float16)t;
-            lo[j] = (_Float16)((t - (float)hi[j]) * kLoScale);
+            lo[j] = (_Float16)planes16_lo(t, (float)hi[j]);
         }
         if (live) {
-            uint8_t* dst = out + (row * KC + (p >> 2)) * (int64_t)kChunk16 + (p & 3) * 16;
+            uint8_t* dst = planes16_piece(out, row, KC, p);
             *reinterpret_cast<f16x8*>(dst) = hi;
             *reinterpret_cast<f16x8*>(dst + 64) = lo;
         }
@@ -283,8 +267,8 @@ __global__ void __launch_bounds__(256) split16_cat_kernel(Split16CatArgs a, int 
         for (int c = sub; c < a.nchains; c += P) {
             const float* ch = a.chain + (size_t)c * a.L * 2;
             float bound = big;
-            for (int l = 0; l < a.L; l++) {
-                bound = (ch[2 * l] * bound + ch[2 * l + 1]) * 1.001f;   // (as split16_planes_kernel)
+            for (int l = 0; l < a.L; l++) {                             // chain_scales, written out: the call changes this kernel's code
+                bound = chain_bound(ch[2 * l], bound, ch[2 * l + 1]);
                 float sc, iv;
                 pow2_scale(bound, sc, iv);
                 a.chain_scale[((size_t)c * a.L + l) * rows + row] = sc;
@@ -313,7 +297,7 @@ hipError_t launch_split16_planes_cat(const Split16CatArgs& a, hipStream_t s) {
 // Entry e = c L + l of the chain = (largest weight-row 1-norm, largest |bias|) of layer l of chain c, from the row norms the weight
 // split left: every block reduces all entries (a few thousand floats: cheaper than a second launch and a dependency), block 0 stores
 // them; then the chain's scales for rows whose input bound is a CONSTANT (observation rows clamped to clip_obs, whose planes the step
-// kernel writes) -- the recurrence of split16_planes_kernel with b_0 = bound0, the same value for every row.
+// kernel writes) -- chain_scales (planes16_lane.h) with b_0 = bound0, the same value for every row.
 __global__ void __launch_bounds__(256) chain_refresh16_kernel(ChainRefreshArgs a) {
     __shared__ float s_chain[2 * kMaxGroups];
     const int E = a.nchains * a.L;
@@ -336,8 +320,8 @@ __global__ void __launch_bounds__(256) chain_refresh16_kernel(ChainRefreshArgs a
     if (row >= a.rows) return;
     for (int c = 0; c < a.nchains; c++) {
         float bound = a.bound0;
-        for (int l = 0; l < a.L; l++) {
-            bound = (s_chain[2 * (c * a.L + l)] * bound + s_chain[2 * (c * a.L + l) + 1]) * 1.001f;
+        for (int l = 0; l < a.L; l++) {                                 // chain_scales, written out: the call changes this kernel's code
+            bound = chain_bound(s_chain[2 * (c * a.L + l)], bound, s_chain[2 * (c * a.L + l) + 1]);
             float sc, iv;
             pow2_scale(bound, sc, iv);
             a.chain_scale[((size_t)c * a.L + l) * a.rows + row] = sc;
@@ -365,13 +349,6 @@ struct Geom16 {
     static constexpr int HW_OFF = 3 * BUF + (SCRATCH_IN_BUF ? 0 : SCRATCH);
     static constexpr size_t LDS = (size_t)HW_OFF + 16 * 128 * 4;        // + the output head's weights [16][128] f32 (out_mode 2)
 };
-
-__device__ __forceinline__ float act16_apply(float v, int act) {
-    if (act == 1) return (v > 0.f) ? v : (expf(v) - 1.f);
-    if (act == 2) return fmaxf(v, 0.f);
-    if (act == 3) return 1.f - 2.f / (__expf(2.f * v) + 1.f);
-    return v;
-}
 
 // ELU on four accumulator values with as few vector instructions as the ISA allows (the epilogue is VALU-issue bound: 64 outputs per
 // lane, two waves per SIMD): x log2(e) as a packed multiply (the factor in a register: a packed instruction takes no literal), v_exp_f32
@@ -769,7 +746,7 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
                     if constexpr (ELU) raw = elu16_4(raw);
                     else {
 #pragma unroll
-                        for (int r = 0; r < 4; r++) raw[r] = act16_apply(raw[r], act);
+                        for (int r = 0; r < 4; r++) raw[r] = act_apply(raw[r], act);
                     }
                 }
                 acc[mt][nt] = raw;
@@ -908,19 +885,6 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
 #endif
 }
 
-static hipError_t allow_lds16(const void* kernel, int slot, size_t bytes) {
-    static bool done[16][64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64 || !done[slot][dev]) {
-        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) done[slot][dev] = true;
-    }
-    return hipSuccess;
-}
-
 // mms_layer_clock_probe: launches from here on report into out[2 (n % slots)], n counting from this call (out = nullptr: off)
 static uint64_t* g_probe_out = nullptr;
 static int g_probe_slots = 0;
@@ -934,27 +898,18 @@ void set_split16_clock_probe(uint64_t* out, int slots) {
 // M a multiple of 128, N of 128 (checked by the caller).  256-row tiles when they still give every CU a block.
 hipError_t launch_linear_split16(const Split16LinearArgs& a, int groups, hipStream_t s) {
     if (a.M == 0 || a.N == 0 || groups == 0) return hipSuccess;
-    int cus = 256;
-    {
-        static int cached[64] = {};                                     // (hipGetDeviceProperties per launch is host time an eager rollout step pays)
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-            if (cached[dev] == 0) {
-                int n = 0;
-                cached[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-            }
-            cus = cached[dev];
-        }
-    }
-    static const int force_mt = getenv("MMS_SPLIT_MT") ? atoi(getenv("MMS_SPLIT_MT")) : 0;
-    const int64_t tiles256 = (a.M % 256 == 0) ? (int64_t)groups * (a.M / 256) * (a.N / 128) : 0;
-    const bool big = force_mt ? (force_mt == 4 && tiles256 > 0) : tiles256 >= cus;
+    const int cus = device_cu_count();
+    const bool big = split_tiles_256(a.M, a.N, groups, cus);
     const bool ln = a.stat_in[0] != nullptr;
     if (a.out_mode < 0 || a.out_mode > 2 || (ln && a.out_mode == 0) || (!ln && a.out_mode == 2)) return hipErrorInvalidValue;
-#define MMS_LAUNCH_SPLIT16(MT, OUT, LNF, SLOT)                                                                                 \
+#define MMS_LAUNCH_SPLIT16(MT, OUT, LNF)                                                                                       \
     {                                                                                                                          \
-        auto kern = (LNF != 0 || a.act == 1) ? linear_split16_kernel<MT, OUT, LNF, true> : linear_split16_kernel<MT, OUT, LNF, false>; \
-        if (hipError_t e = allow_lds16(reinterpret_cast<const void*>(kern), SLOT + ((LNF != 0 || a.act == 1) ? 0 : 8), Geom16<MT>::LDS); e != hipSuccess) return e; \
+        const bool elu = LNF != 0 || a.act == 1;                                                                               \
+        auto kern = elu ? linear_split16_kernel<MT, OUT, LNF, true> : linear_split16_kernel<MT, OUT, LNF, false>;              \
+        if (hipError_t e = elu ? allow_large_lds<linear_split16_kernel<MT, OUT, LNF, true>>(Geom16<MT>::LDS)                   \
+                               : allow_large_lds<linear_split16_kernel<MT, OUT, LNF, false>>(Geom16<MT>::LDS);                 \
+            e != hipSuccess)                                                                                                   \
+            return e;                                                                                                          \
         Split16LinearArgs b = a;                                                                                               \
         b.tiles = (int)((int64_t)groups * (a.M / (64 * MT)) * (a.N / 128));                                                    \
         b.clock_probe = g_probe_out ? g_probe_out + 2 * (g_probe_next++ % g_probe_slots) : nullptr;                           \
@@ -963,14 +918,14 @@ hipError_t launch_linear_split16(const Split16LinearArgs& a, int groups, hipStre
         hipLaunchKernelGGL(kern, dim3(grid), dim3(512), Geom16<MT>::LDS, s, b);                                                \
     }
     if (ln) {
-        if (big && a.out_mode == 1) MMS_LAUNCH_SPLIT16(4, 1, 3, 4)
-        else if (big) MMS_LAUNCH_SPLIT16(4, 2, 3, 5)
-        else if (a.out_mode == 1) MMS_LAUNCH_SPLIT16(2, 1, 3, 6)
-        else MMS_LAUNCH_SPLIT16(2, 2, 3, 7)
-    } else if (big && a.out_mode == 1) MMS_LAUNCH_SPLIT16(4, 1, 0, 0)
-    else if (big) MMS_LAUNCH_SPLIT16(4, 0, 0, 1)
-    else if (a.out_mode == 1) MMS_LAUNCH_SPLIT16(2, 1, 0, 2)
-    else MMS_LAUNCH_SPLIT16(2, 0, 0, 3)
+        if (big && a.out_mode == 1) MMS_LAUNCH_SPLIT16(4, 1, 3)
+        else if (big) MMS_LAUNCH_SPLIT16(4, 2, 3)
+        else if (a.out_mode == 1) MMS_LAUNCH_SPLIT16(2, 1, 3)
+        else MMS_LAUNCH_SPLIT16(2, 2, 3)
+    } else if (big && a.out_mode == 1) MMS_LAUNCH_SPLIT16(4, 1, 0)
+    else if (big) MMS_LAUNCH_SPLIT16(4, 0, 0)
+    else if (a.out_mode == 1) MMS_LAUNCH_SPLIT16(2, 1, 0)
+    else MMS_LAUNCH_SPLIT16(2, 0, 0)
 #undef MMS_LAUNCH_SPLIT16
     return hipGetLastError();
 }

@@ -22,10 +22,7 @@
 // with four consecutive n of one row m: the epilogue packs them into 8-byte plane pieces / one 16-byte fp32 piece.
 // K walks in steps of 32 through LDS (double buffered, 72 KB per buffer at MT = 4), the next step's operands prefetched into
 // registers at the top of a step and stored to LDS at its end; one barrier per step.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
+#include "layer_common.h"
 #include "policy_args.h"
 
 namespace mms {
@@ -109,13 +106,6 @@ struct SplitGeom {
     static constexpr int HW_OFF = 2 * BUF + (SCRATCH_IN_BUF ? 0 : SCRATCH);
     static constexpr size_t LDS = (size_t)HW_OFF + 16 * 128 * 4;
 };
-
-__device__ __forceinline__ float act_apply(float v, int act) {
-    if (act == 1) return (v > 0.f) ? v : (expf(v) - 1.f);
-    if (act == 2) return fmaxf(v, 0.f);
-    if (act == 3) return 1.f - 2.f / (__expf(2.f * v) + 1.f);
-    return v;
-}
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -422,57 +412,31 @@ __global__ void __launch_bounds__(512, 2) linear_split_kernel(SplitLinearArgs a)
     }
 }
 
-static hipError_t allow_lds(const void* kernel, int slot, size_t bytes) {
-    static bool done[8][64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64 || !done[slot][dev]) {
-        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) done[slot][dev] = true;
-    }
-    return hipSuccess;
-}
-
 // M a multiple of 128, N of 128 (checked by the caller).  256-row tiles when they still give every CU a block.
 hipError_t launch_linear_split(const SplitLinearArgs& a, int groups, hipStream_t s) {
     if (a.M == 0 || a.N == 0 || groups == 0) return hipSuccess;
-    int cus = 256;
-    {
-        static int cached[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-            if (cached[dev] == 0) {
-                int n = 0;
-                cached[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-            }
-            cus = cached[dev];
-        }
-    }
-    static const int force_mt = getenv("MMS_SPLIT_MT") ? atoi(getenv("MMS_SPLIT_MT")) : 0;
-    const int64_t tiles256 = (a.M % 256 == 0) ? (int64_t)groups * (a.M / 256) * (a.N / 128) : 0;
-    const bool big = force_mt ? (force_mt == 4 && tiles256 > 0) : tiles256 >= cus;
+    const int cus = device_cu_count();
+    const bool big = split_tiles_256(a.M, a.N, groups, cus);
     const bool ln = a.stat_in[0] != nullptr;
     if (a.out_mode < 0 || a.out_mode > 2 || (ln && a.out_mode == 0) || (!ln && a.out_mode == 2)) return hipErrorInvalidValue;
-#define MMS_LAUNCH_SPLIT(MT, OUT, LNF, SLOT)                                                                                   \
+#define MMS_LAUNCH_SPLIT(MT, OUT, LNF)                                                                                         \
     {                                                                                                                          \
         auto kern = linear_split_kernel<MT, OUT, LNF>;                                                                         \
-        if (hipError_t e = allow_lds(reinterpret_cast<const void*>(kern), SLOT, SplitGeom<MT>::LDS); e != hipSuccess) return e; \
+        if (hipError_t e = allow_large_lds<linear_split_kernel<MT, OUT, LNF>>(SplitGeom<MT>::LDS); e != hipSuccess) return e;  \
         SplitLinearArgs b = a;                                                                                                 \
         b.tiles = (int)((int64_t)groups * (a.M / (64 * MT)) * (a.N / 128));                                                    \
         const unsigned grid = (unsigned)(b.tiles < cus ? b.tiles : cus);        /* persistent: at most one block per CU */      \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SplitGeom<MT>::LDS, s, b);                                             \
     }
     if (ln) {
-        if (big && a.out_mode == 1) MMS_LAUNCH_SPLIT(4, 1, 3, 4)
-        else if (big) MMS_LAUNCH_SPLIT(4, 2, 3, 5)
-        else if (a.out_mode == 1) MMS_LAUNCH_SPLIT(2, 1, 3, 6)
-        else MMS_LAUNCH_SPLIT(2, 2, 3, 7)
-    } else if (big && a.out_mode == 1) MMS_LAUNCH_SPLIT(4, 1, 0, 0)
-    else if (big) MMS_LAUNCH_SPLIT(4, 0, 0, 1)
-    else if (a.out_mode == 1) MMS_LAUNCH_SPLIT(2, 1, 0, 2)
-    else MMS_LAUNCH_SPLIT(2, 0, 0, 3)
+        if (big && a.out_mode == 1) MMS_LAUNCH_SPLIT(4, 1, 3)
+        else if (big) MMS_LAUNCH_SPLIT(4, 2, 3)
+        else if (a.out_mode == 1) MMS_LAUNCH_SPLIT(2, 1, 3)
+        else MMS_LAUNCH_SPLIT(2, 2, 3)
+    } else if (big && a.out_mode == 1) MMS_LAUNCH_SPLIT(4, 1, 0)
+    else if (big) MMS_LAUNCH_SPLIT(4, 0, 0)
+    else if (a.out_mode == 1) MMS_LAUNCH_SPLIT(2, 1, 0)
+    else MMS_LAUNCH_SPLIT(2, 0, 0)
 #undef MMS_LAUNCH_SPLIT
     return hipGetLastError();
 }

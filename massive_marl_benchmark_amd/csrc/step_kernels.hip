@@ -17,6 +17,7 @@
 
 #include "head_block.h"
 #include "mms_lane.h"
+#include "planes16_lane.h"
 #include "step_args.h"
 
 namespace mms {
@@ -618,14 +619,14 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 64 ? MMS_WAVES_PER_EU : ((BLOC
                 if (obs_out) obs_out[i] = c;
             }
         }
-        // ... and, when bound, the clamped row once more as the policy layers' operand planes (format H32 of split16_kernels.hip: per
+        // ... and, when bound, the clamped row once more as the policy layers' operand planes (format H32, planes16_lane.h: per
         // 32 k the fp16 hi and lo planes, 128 bytes): the rows are bounded by clip_obs, so their scale is a constant and the separate
         // split pass over the observation (6 us, one launch) is not needed.  One 8-k piece per thread and trip.
         if (a.obs_planes) {
             typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
             const int KC = (obs_dim + 31) >> 5, pieces = KC * 4;
             const float sc = a.obs_planes_scale;
-            uint8_t* out = reinterpret_cast<uint8_t*>(a.obs_planes) + (size_t)e0 * KC * 128;
+            uint8_t* out = reinterpret_cast<uint8_t*>(a.obs_planes) + (size_t)e0 * KC * kChunk16;
             int tix = threadIdx.x;
             asm volatile("" : "+v"(tix));           // (opaque: nothing of this loop's index math is hoisted across the physics -- one spill otherwise)
             for (int i = tix; i < n_live * pieces; i += BLOCK) {
@@ -636,9 +637,9 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 64 ? MMS_WAVES_PER_EU : ((BLOC
                 for (int j = 0; j < 8; j++) {
                     const float t = (k0 + j < obs_dim) ? clampf(r[j], -clip, clip) * sc : 0.f;
                     hi[j] = (_Float16)t;
-                    lo[j] = (_Float16)((t - (float)hi[j]) * 2048.f);
+                    lo[j] = (_Float16)planes16_lo(t, (float)hi[j]);
                 }
-                uint8_t* dst = out + ((size_t)e * KC + (p >> 2)) * 128 + (p & 3) * 16;
+                uint8_t* dst = planes16_piece(out, e, KC, p);
                 *reinterpret_cast<f16x8_t*>(dst) = hi;
                 *reinterpret_cast<f16x8_t*>(dst + 64) = lo;
             }
