@@ -36,7 +36,7 @@
  *                                                                        mms_marl_heads_finish
  *   Actor / Critic forward of every MAPPO / HAPPO agent                  mms_linear_group_act, mms_layernorm_group,
  *     (algorithms/marl/actor_critic.py:43-69, 137-155; runner.py:186-216)  mms_row_stats_group, mms_marl_heads_act
- *   RNNLayer's single-step branch of every recurrent agent              mms_gru_group
+ *   RNNLayer's single-step branch of every recurrent agent              mms_gru_group, mms_gru_gates_group
  *     (algorithms/utils/rnn.py:25-29; marl/actor_critic.py:64-65, 164-165)
  *   SquashedGaussianMLPActor heads + rsample + log-probability          mms_sac_heads_act
  *     (algorithms/rl/sac/module.py:23-61; sac.py:166, 374-376)
@@ -547,6 +547,26 @@ int mms_gru_group(int device, int32_t groups, int64_t M, int32_t K, int32_t H, c
                   const float* const* h, int64_t h_pitch, const float* const* mask, int64_t mask_pitch, const float* const* w_ih,
                   const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, float* const* h_out,
                   int64_t h_out_pitch, float* const* y, void* hip_stream);
+
+/* The gate arithmetic of the same cell step on pre-activations that layer launches left in memory: the unfused form of mms_gru_group,
+ * for callers that run the two products x W_ih^T and h W_hh^T on another kernel (GroupedPolicyInference's rnn_format="f16x2" runs them
+ * on mms_linear_group_act_split16, N = 3H, identity activation, out_mode 0).  For g < groups, i < M, j < H, gate order r, z, n:
+ *   gi_g [M, 3H] at g_pitch = x W_ih^T + b_ih, the bias already added; gh_g [M, 3H] at g_pitch = h W_hh^T of the UNMASKED state, no bias
+ *   hm  = mask_g[i] * h_g[i, j]                                  (mask == NULL: hm = h)
+ *   a_* = mask_g[i] * gh_g[i, * H + j] + b_hh_g[* H + j]         ((m h) W^T = m (h W^T) for a per-row 0 / 1 mask)
+ *   r = sigmoid(gi_r + a_r);  z = sigmoid(gi_z + a_z);  n = tanh(gi_n + r * a_n);  h' = (1 - z) * n + z * hm
+ * h' goes to h_out_g[i, j] (at h_out_pitch) and, where given, to y_g[i, j] (dense [M, H]; y NULL as a whole or per group).  gi, gh, h,
+ * mask, b_hh, h_out, y: HOST arrays of `groups` device pointers; pitches in floats.  Both products of the mask are followed by + 0, so a
+ * row with mask 0 is bit for bit the row of a zero state with zero gh.  A streaming kernel without atomics: h'_g[i, :] is a function of
+ * row i and the group's b_hh only, not of M, groups, the pitches or where the row sits, and runs are bit-identical.
+ * H a positive multiple of 4 up to 1024; g_pitch >= 3H, h_pitch >= H, h_out_pitch >= H, each a multiple of 4; mask_pitch >= 1; gi_g,
+ * gh_g, h_g, b_hh_g, h_out_g, y_g 16-byte aligned; M >= 0 (M == 0 succeeds and touches nothing); groups 1..MMS_MAX_GROUPS.  No
+ * destination may be one of the sources: h_out_g == h_q, gi_q or gh_q, y_g == h_q, gi_q, gh_q or h_out_q, or two groups with one
+ * destination are refused.  Rows past M, columns past H and whatever lies between pitched rows are never written.  Bad arguments return
+ * non-zero with mms_last_error(NULL) and write nothing. */
+int mms_gru_gates_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* gi, const float* const* gh, int64_t g_pitch,
+                        const float* const* h, int64_t h_pitch, const float* const* mask, int64_t mask_pitch,
+                        const float* const* b_hh, float* const* h_out, int64_t h_out_pitch, float* const* y, void* hip_stream);
 
 /* ---- the same layers on the bf16 matrix pipe with fp32 operands carried as three bf16 planes (csrc/split_kernels.hip) -----------
  * An fp32 number is exactly a0 + a1 + a2 with a0 = bf16(a), a1 = bf16(a - a0), a2 = bf16(a - a0 - a1); the product is formed as the six

@@ -32,7 +32,10 @@ version counter or address has moved (an in-place optimizer step moves them).  W
 collect loop -- call `refresh()` after it (tests/test_marl_policy.py pins all three).  Recurrent policies
 (use_recurrent_policy / use_naive_recurrent_policy: every network carries `.rnn.rnn`, an nn.GRU of the hidden width, and `.rnn.norm`)
 run the exact-fp32 layers (the plane kernels are not used), their GRU parameters are read in place (no derived copies), and
-`get_actions` / `get_values` / `collect` / `collect_into` take and return the states (see there).  A recurrent flag without such a
+`get_actions` / `get_values` / `collect` / `collect_into` take and return the states (see there).  `rnn_format="f16x2"` (opt-in)
+moves a recurrent group's products onto the two-plane fp16 layer kernel where the shapes allow (`_rnn16_applies`, `_forward_rnn16`):
+every base block and both GRU products as split + mms_linear_group_act_split16 into fp32, the gates by mms_gru_gates_group;
+`rnn_route` names the route the last call took.  A recurrent flag without such a
 layer, a mix of recurrent and feed-forward networks, and non-Box action spaces are not covered: the constructor raises, nothing falls
 back silently.
 
@@ -118,9 +121,15 @@ def _critic_halves(table, n):
 
 
 class GroupedPolicyInference:
-    def __init__(self, actors, critics, seed=0, row_offset=0, fold_layernorm=True, split_layers=True, split_format="f16x2"):
+    def __init__(self, actors, critics, seed=0, row_offset=0, fold_layernorm=True, split_layers=True, split_format="f16x2", rnn_format="fp32"):
         if len(actors) != len(critics) or not actors:
             raise ValueError("one actor and one critic per agent")
+        # Recurrent groups only (others ignore it): "fp32" = the exact-fp32 layers and mms_gru_group; "f16x2" = the plane route of
+        # _forward_rnn16 for the calls whose shapes it takes (_rnn16_applies), the fp32 route for all others
+        if rnn_format not in ("fp32", "f16x2"):
+            raise ValueError("rnn_format: fp32 or f16x2")
+        self.rnn_format = rnn_format
+        self._route = "fp32"
         self._chunks = None
         self._plans = None
         self._plist = None
@@ -133,7 +142,8 @@ class GroupedPolicyInference:
             self.n = len(actors)
             self._ranges = [(lo, min(lo + 16, self.n)) for lo in range(0, self.n, 16)]
             self._chunks = [GroupedPolicyInference(actors[lo:hi], critics[lo:hi], seed=int(seed) + lo, row_offset=row_offset,
-                                                   fold_layernorm=fold_layernorm, split_layers=split_layers, split_format=split_format)
+                                                   fold_layernorm=fold_layernorm, split_layers=split_layers, split_format=split_format,
+                                                   rnn_format=rnn_format)
                             for lo, hi in self._ranges]
             if len({c.recurrent_N for c in self._chunks}) != 1:
                 raise NotImplementedError("GroupedPolicyInference: all networks must share recurrent_N")
@@ -291,8 +301,37 @@ class GroupedPolicyInference:
                 for l in range(1, depth - 1):
                     D["scale1"][l] = z(2 * n)
                     D["scale_jobs"].append((l, list(D["fold"][l]["rb"].unbind(0))))
+        # rnn_format="f16x2": the two-plane operands of every matrix the plane route multiplies by, UNFOLDED (the route normalises in
+        # memory: the layer kernel's LayerNorm folds do not come with an fp32 output) -- the base blocks' weights and, per GRU layer,
+        # weight_ih and weight_hh -- by mms_weight_planes16_group, one launch per set of at most 2n matrices; and the zero vector that
+        # stands in for the bias of h W_hh^T (b_hh is added by the gate kernel, behind the mask)
+        D["rnn16"] = None
+        if self._rnn16_built():
+            def wset(ws, N, K):
+                G = len(ws)
+                st = {"planes": u8(G, N, K), "scale": z(G, N), "inv": z(G, N)}
+                src = [d(w) for w in ws]
+                D["calls"].append((L.mms_weight_planes16_group, (idx, G, i64([N] * G), i32([K] * G), up(src), up(st["planes"]), up(list(st["scale"].unbind(0))),
+                                                                 up(list(st["inv"].unbind(0))), None), "mms_weight_planes16_group", src))
+                return st
+            R = {"a1": wset([b[0][0].weight for b in self.a_blocks], H, self.obs_dim), "c1": wset([b[0][0].weight for b in self.c_blocks], H, self.sobs_dim),
+                 "w": {l: wset([b[l][0].weight for b in both], H, H) for l in range(1, depth)}, "ih": {}, "hh": {}, "zero": z(3 * H)}
+            for l in range(self.recurrent_N):
+                R["ih"][l] = wset([getattr(g, "weight_ih_l%d" % l) for g, _ in self.rnns], 3 * H, H)
+                R["hh"][l] = wset([getattr(g, "weight_hh_l%d" % l) for g, _ in self.rnns], 3 * H, H)
+            D["rnn16"] = R
         self._D = D
         return D
+
+    def _rnn16_built(self):
+        """The part of the plane route's conditions that the constructor's arguments and the networks' shapes decide"""
+        return bool(self.recurrent_N and self.rnn_format == "f16x2" and self.split_layers and self.fold_layernorm and self.split_format == "f16x2"
+                    and self.hidden % 128 == 0 and self.sobs_dim >= 8)
+
+    @property
+    def rnn_route(self):
+        """"f16x2" when the last inference call of a recurrent group took the plane route, else "fp32" (read-only)"""
+        return self._chunks[0].rnn_route if self._chunks is not None else self._route
 
     def refresh(self):
         """Rebuild every copy derived from the parameters from the parameters as they are NOW: device work only (a handful of launches
@@ -419,6 +458,14 @@ class GroupedPolicyInference:
                     self.p["swi%d" % l] = arr(ub(st["inv"]))
             hd = D["heads"]
             self.p["hwt"], self.p["hs"], self.p["hc"] = arr(ub(hd["wt"])), arr(ub(hd["s"])), arr(ub(hd["c"]))
+        if D["rnn16"] is not None:
+            R = D["rnn16"]
+            raw = lambda ts: (self._keep.append(ts), (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts]))[1]
+            sets = [("a1", R["a1"]), ("c1", R["c1"])] + [("w%d" % l, st) for l, st in R["w"].items()]
+            sets += [("ih%d" % l, st) for l, st in R["ih"].items()] + [("hh%d" % l, st) for l, st in R["hh"].items()]
+            for name, st in sets:
+                self.p["r16_" + name], self.p["r16i_" + name] = raw(st["planes"]), arr(ub(st["inv"]))
+            self.p["r16_zero"] = arr([R["zero"]] * (2 * self.n))
         self._A = (ctypes.c_int32 * (2 * self.n))(*([self.act_dim] * self.n + [1] * self.n))
         self._A1 = (ctypes.c_int32 * self.n)(*([1] * self.n))
         self._Aa = (ctypes.c_int32 * self.n)(*([self.act_dim] * self.n))
@@ -477,6 +524,16 @@ class GroupedPolicyInference:
                 for l in self.ysc:
                     self.q["ysc%d" % l], self.q["yinv%d" % l] = _ptrs(ub(self.ysc[l])), _ptrs(ub(self.yinv[l]))
                 self.q["ysc0_a"], self.q["yinv0_a"] = _ptrs(ub(self.ysc[0][:n])), _ptrs(ub(self.yinv[0][:n]))
+        if self._D["rnn16"] is not None and M % 128 == 0:
+            # the plane route's scratch: planes and row scales of the first layers' inputs, of a block's / GRU layer's x (0) and of the
+            # state (1), and the two [M, 3H] pre-activation blocks per network
+            u8 = lambda g, K: [torch.empty(_lib.h32_bytes(M, K), dtype=torch.uint8, device=dev) for _ in range(g)]
+            up = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+            self.r16 = {"sx_a": u8(n, self.obs_dim), "sx_c": u8(n, self.sobs_dim), "sh0": u8(2 * n, H), "sh1": u8(2 * n, H),
+                        "xs_a": z(n, M), "xi_a": z(n, M), "xs_c": z(n, M), "xi_c": z(n, M), "hs0": z(2 * n, M), "hi0": z(2 * n, M), "hs1": z(2 * n, M),
+                        "hi1": z(2 * n, M), "gi": z(2 * n, M, 3 * H), "gh": z(2 * n, M, 3 * H)}
+            for key, t in self.r16.items():
+                self.q["r16_" + key] = up(t) if isinstance(t, list) else _ptrs(ub(t))
         _critic_halves(self.q, n)
         self._M = M
         self._fill_scales()
@@ -596,6 +653,68 @@ class GroupedPolicyInference:
             cur = 1 - cur
         return cur
 
+    # -- recurrent policies on the plane kernels (rnn_format="f16x2") -------------------------------------------------------------------
+    def _rnn16_applies(self, M, sobs_pitch):
+        """Decided before the first launch: everything else runs the fp32 route exactly as without the keyword"""
+        return self._rnn16_built() and self._D["rnn16"] is not None and M % 128 == 0 and sobs_pitch == self.sobs_dim
+
+    def _forward_rnn16(self, L, idx, stream, M, obs_p, obs_pitch, sobs_p, with_actors, states, masks, dsts):
+        """The pass of a recurrent group with every product on mms_linear_group_act_split16 (two fp16 planes per operand, fp32 out):
+          feature LayerNorm (mms_layernorm_group), then per base block: split of the normalised rows (mms_split_planes16_group: each
+          row's own scale, no bound chain), Linear + ELU into fp32 (out_mode 0), the block's LayerNorm in place;
+          per GRU layer: split of x (dense) and of the UNMASKED state where it lies in its slot, gi = x W_ih^T + b_ih and gh = h W_hh^T
+          (N = 3H, identity; two launches: 2 G networks may exceed MMS_MAX_GROUPS), and mms_gru_gates_group, which applies the mask
+          behind the product, adds b_hh and writes h' into the destination slot and the other activation buffer.
+        with_actors = False: the critics alone.  Returns the index of the activation buffer the heads read."""
+        n, H, p, q = self.n, self.hidden, self.p, self.q
+        chk = lambda rc, what: _lib.check(rc, None, what, L)
+        sfx = "" if with_actors else "/c"
+        G = len(states)
+        for t in list(states) + list(dsts):
+            if t.dim() != 3 or tuple(t.shape) != (M, self.recurrent_N, H):
+                raise ValueError("GroupedPolicyInference: rnn states must be [M, recurrent_N, hidden] per agent")
+        mask_p, mask_pitch = _mask_ptrs(masks, M)
+
+        def split(groups, K, pitch, src, dst, xs, xi):
+            chk(L.mms_split_planes16_group(idx, groups, M, K, pitch, src, q[dst], q[xs], q[xi], 0, 0, None, None, None, None, self.eps, stream), "mms_split_planes16_group")
+
+        def layer(groups, N, K, x, w, b, y, xinv, winv, act):
+            chk(L.mms_linear_group_act_split16(idx, groups, M, N, K, x, w, b, y, xinv, winv, None, act, 0, None, None, None, None, None, None, stream),
+                "mms_linear_group_act_split16")
+
+        def norm(groups, x, g, b):
+            chk(L.mms_layernorm_group(idx, groups, M, H, H, H, x, g, b, x, self.eps, stream), "mms_layernorm_group")
+        if with_actors:
+            chk(L.mms_layernorm_group(idx, n, M, self.obs_dim, self.kp_a, obs_pitch, obs_p, p["fn_a_g"], p["fn_a_b"], q["x_a"], self.eps, stream), "mms_layernorm_group")
+            split(n, self.obs_dim, self.kp_a, q["x_a"], "r16_sx_a", "r16_xs_a", "r16_xi_a")
+            layer(n, H, self.obs_dim, q["r16_sx_a"], p["r16_a1"], p["b1_a"], q["h0_a"], q["r16_xi_a"], p["r16i_a1"], 1)
+        chk(L.mms_layernorm_group(idx, n, M, self.sobs_dim, self.kp_c, self.sobs_dim, sobs_p, p["fn_c_g"], p["fn_c_b"], q["x_c"], self.eps, stream), "mms_layernorm_group")
+        split(n, self.sobs_dim, self.kp_c, q["x_c"], "r16_sx_c", "r16_xs_c", "r16_xi_c")
+        layer(n, H, self.sobs_dim, q["r16_sx_c"], p["r16_c1"], p["b1_c"], q["h0_c"], q["r16_xi_c"], p["r16i_c1"], 1)
+        cur = 0
+        norm(G, q["h0" + sfx], p["ln0_g" + sfx], p["ln0_b" + sfx])
+        for l in range(1, self.depth):
+            split(G, H, H, q["h%d%s" % (cur, sfx)], "r16_sh0" + sfx, "r16_hs0" + sfx, "r16_hi0" + sfx)
+            layer(G, H, H, q["r16_sh0" + sfx], p["r16_w%d%s" % (l, sfx)], p["b%d%s" % (l, sfx)], q["h%d%s" % (1 - cur, sfx)], q["r16_hi0" + sfx],
+                  p["r16i_w%d%s" % (l, sfx)], 1)
+            cur = 1 - cur
+            norm(G, q["h%d%s" % (cur, sfx)], p["ln%d_g%s" % (l, sfx)], p["ln%d_b%s" % (l, sfx)])
+        for l in range(self.recurrent_N):
+            h_p, h_pitch = _row_ptrs([t.detach()[:, l] for t in states])
+            o_p, o_pitch = _row_ptrs([t.detach()[:, l] for t in dsts])
+            if h_pitch >= 2 ** 31:
+                raise ValueError("GroupedPolicyInference: the state rows' pitch must fit 31 bits")
+            split(G, H, H, q["h%d%s" % (cur, sfx)], "r16_sh0" + sfx, "r16_hs0" + sfx, "r16_hi0" + sfx)
+            split(G, H, h_pitch, h_p, "r16_sh1" + sfx, "r16_hs1" + sfx, "r16_hi1" + sfx)
+            layer(G, 3 * H, H, q["r16_sh0" + sfx], p["r16_ih%d%s" % (l, sfx)], p["gru_bih%d%s" % (l, sfx)], q["r16_gi" + sfx], q["r16_hi0" + sfx],
+                  p["r16i_ih%d%s" % (l, sfx)], 0)
+            layer(G, 3 * H, H, q["r16_sh1" + sfx], p["r16_hh%d%s" % (l, sfx)], p["r16_zero" + sfx], q["r16_gh" + sfx], q["r16_hi1" + sfx],
+                  p["r16i_hh%d%s" % (l, sfx)], 0)
+            chk(L.mms_gru_gates_group(idx, G, M, H, q["r16_gi" + sfx], q["r16_gh" + sfx], 3 * H, h_p, h_pitch, mask_p, mask_pitch, p["gru_bhh%d%s" % (l, sfx)],
+                                      o_p, o_pitch, q["h%d%s" % (1 - cur, sfx)], stream), "mms_gru_gates_group")
+            cur = 1 - cur
+        return cur
+
     # -- inference ----------------------------------------------------------------------------------------------------------------
     def get_actions(self, share_obs, obs, deterministic=False, out=None, rnn_states=None, rnn_states_critic=None, masks=None, rnn_out=None):
         """share_obs, obs: per-agent lists of [M, share_obs_dim] / [M, obs_dim] float32 tensors (what the Runner hands agent i:
@@ -647,8 +766,19 @@ class GroupedPolicyInference:
             values, actions, logp, out_p, logp_p, pitch = self._out_ptrs(out)
             self._forward_split(L, idx, stream, M, obs_p, obs_pitch, sobs_p, True, p["std_none"] if deterministic else p["std"], out_p, logp_p, pitch, q["cnt"])
             return values, actions, (None if deterministic else logp)
-        chk(L.mms_layernorm_group(idx, n, M, self.obs_dim, self.kp_a, obs_pitch, obs_p, p["fn_a_g"], p["fn_a_b"], q["x_a"], self.eps, stream), "mms_layernorm_group")
         H = self.hidden
+        rnn16 = bool(self.recurrent_N) and self._rnn16_applies(M, sobs_pitch)
+        self._route = "f16x2" if rnn16 else "fp32"
+        if rnn16:
+            values, actions, logp, out_p, logp_p, pitch = self._out_ptrs(out)
+            new_a = list(self.rnn_new[:n].unbind(0)) if rnn_out is None else list(rnn_out[0])
+            new_c = list(self.rnn_new[n:].unbind(0)) if rnn_out is None else list(rnn_out[1])
+            cur = self._forward_rnn16(L, idx, stream, M, obs_p, obs_pitch, sobs_p, True, rs_a + rs_c, mk + mk, new_a + new_c)
+            chk(L.mms_marl_heads_act(idx, 2 * n, M, H, q["h%d" % cur], p["rn_g"], p["rn_b"], p["hw"], p["hb"], self._A,
+                                     p["std_none"] if deterministic else p["std"], out_p, logp_p, pitch, q["cnt"], self.seed, self.row_offset, self.eps, stream),
+                "mms_marl_heads_act")
+            return values, actions, (None if deterministic else logp), new_a, new_c
+        chk(L.mms_layernorm_group(idx, n, M, self.obs_dim, self.kp_a, obs_pitch, obs_p, p["fn_a_g"], p["fn_a_b"], q["x_a"], self.eps, stream), "mms_layernorm_group")
         fold = self.fold_layernorm and self.depth > 1 and M % 128 == 0 and H % 128 == 0 and self.kp_a >= 8 and self._has_wt
         fold_c1 = fold and self._fold_c1 is not None and sobs_pitch == self.sobs_dim and self.sobs_dim >= 8
         if not fold_c1:
@@ -694,9 +824,9 @@ class GroupedPolicyInference:
 
     # -- the Runner's collect step --------------------------------------------------------------------------------------------------
     @classmethod
-    def from_trainers(cls, trainers, seed=0, row_offset=0):
+    def from_trainers(cls, trainers, seed=0, row_offset=0, rnn_format="fp32"):
         """One object for a Runner's agents: `trainers[i].policy.actor` / `.critic` (runner.py:69-101)."""
-        return cls([t.policy.actor for t in trainers], [t.policy.critic for t in trainers], seed=seed, row_offset=row_offset)
+        return cls([t.policy.actor for t in trainers], [t.policy.critic for t in trainers], seed=seed, row_offset=row_offset, rnn_format=rnn_format)
 
     @torch.no_grad()
     def collect(self, buffers, step):
@@ -847,6 +977,15 @@ class GroupedPolicyInference:
             values = list(self.values.unbind(0)) if out is None else list(out)
             vp, v_pitch = _row_ptrs(values)
             self._forward_split(L, idx, stream, M, None, 0, sobs_p, False, None, vp, None, (ctypes.c_int32 * n)(*([v_pitch] * n)), None)
+            return values
+        rnn16 = bool(self.recurrent_N) and self._rnn16_applies(M, sobs_pitch)
+        self._route = "f16x2" if rnn16 else "fp32"
+        if rnn16:
+            values = list(self.values.unbind(0)) if out is None else list(out)
+            vp, v_pitch = _row_ptrs(values)
+            cur = self._forward_rnn16(L, idx, stream, M, None, 0, sobs_p, False, rs_c, mk, list(self.rnn_new[n:].unbind(0)))
+            chk(L.mms_marl_heads_act(idx, n, M, H, q["h%d/c" % cur], p["rn_g/c"], p["rn_b/c"], p["hw/c"], p["hb/c"], self._A1,
+                                     None, vp, None, (ctypes.c_int32 * n)(*([v_pitch] * n)), None, self.seed, self.row_offset, self.eps, stream), "mms_marl_heads_act")
             return values
         fold = self.fold_layernorm and self.depth > 1 and M % 128 == 0 and H % 128 == 0 and self._has_wt
         fold_c1 = fold and self._fold_c1 is not None and sobs_pitch == self.sobs_dim and self.sobs_dim >= 8

@@ -1020,6 +1020,28 @@ MMS_API int mms_gru_group(int device, int32_t groups, int64_t M, int32_t K, int3
     }
     return 0;
 }
+// The gate arithmetic alone on given pre-activations (include/mms.h: mms_gru_gates_group): ../gru_lane.h's gru_gates per element.
+MMS_API int mms_gru_gates_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* gi, const float* const* gh, int64_t g_pitch,
+                                const float* const* h, int64_t h_pitch, const float* const* mask, int64_t mask_pitch, const float* const* b_hh,
+                                float* const* h_out, int64_t h_out_pitch, float* const* y, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_gru_gates_group(groups, M, H, gi, gh, g_pitch, h, h_pitch, mask, mask_pitch, b_hh, h_out, h_out_pitch, y))) return 1;
+    for (int g = 0; g < groups; g++) {
+        const float* bh = b_hh[g];
+        float* yg = y ? y[g] : nullptr;
+#pragma omp parallel for schedule(static)
+        for (int64_t m = 0; m < M; m++) {
+            const float *ir = gi[g] + m * g_pitch, *hr = gh[g] + m * g_pitch, *hs = h[g] + m * h_pitch;
+            const float mk = mask ? mask[g][m * mask_pitch] : 1.f;
+            for (int j = 0; j < H; j++) {
+                const float o = mms::gru_gates(mask != nullptr, mk, ir[j], ir[H + j], ir[2 * H + j], hr[j], hr[H + j], hr[2 * H + j], bh[j], bh[H + j], bh[2 * H + j], hs[j]);
+                h_out[g][m * h_out_pitch + j] = o;
+                if (yg) yg[m * H + j] = o;
+            }
+        }
+    }
+    return 0;
+}
 MMS_API int mms_marl_heads_act(int device, int32_t groups, int64_t M, int32_t H, const float* const* h, const float* const* gamma,
                                const float* const* beta, const float* const* w, const float* const* b, const int32_t* A, const float* const* std,
                                float* const* out, float* const* logp, const int32_t* out_pitch, int64_t* const* counters, uint64_t seed,

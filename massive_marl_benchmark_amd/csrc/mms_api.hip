@@ -12,6 +12,7 @@
 #include "ln_mlp_plan.h"
 #include "maddpg_args.h"
 #include "gru_args.h"
+#include "gru_gates_args.h"
 
 namespace mms {
 hipError_t launch_step(const StepArgs& a, int task, hipStream_t stream);
@@ -726,6 +727,23 @@ __attribute__((visibility("default"))) int mms_gru_group(int device, int32_t gro
     a.x_pitch = x_pitch; a.h_pitch = h_pitch; a.mask_pitch = mask_pitch; a.h_out_pitch = h_out_pitch;
     a.M = (int)M; a.K = K; a.H = H;
     MMS_FREE(mms::launch_gru_group(a, groups, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_gru_gates_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* gi, const float* const* gh,
+                                                               int64_t g_pitch, const float* const* h, int64_t h_pitch, const float* const* mask,
+                                                               int64_t mask_pitch, const float* const* b_hh, float* const* h_out, int64_t h_out_pitch,
+                                                               float* const* y, void* s) {
+    MMS_DEV(device)
+    if (refused(check_gru_gates_group(groups, M, H, gi, gh, g_pitch, h, h_pitch, mask, mask_pitch, b_hh, h_out, h_out_pitch, y))) return 1;
+    mms::GruGatesArgs a = {};
+    for (int g = 0; g < groups; g++) {
+        a.gi[g] = gi[g]; a.gh[g] = gh[g]; a.h[g] = h[g]; a.mask[g] = mask ? mask[g] : nullptr;
+        a.b_hh[g] = b_hh[g]; a.h_out[g] = h_out[g]; a.y[g] = y ? y[g] : nullptr;
+    }
+    a.g_pitch = g_pitch; a.h_pitch = h_pitch; a.mask_pitch = mask_pitch; a.h_out_pitch = h_out_pitch;
+    a.M = (int)M; a.H = H;
+    MMS_FREE(mms::launch_gru_gates_group(a, groups, (hipStream_t)s));
     return 0;
 }
 

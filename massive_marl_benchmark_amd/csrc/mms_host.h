@@ -711,6 +711,32 @@ static inline std::string check_gru_group(int32_t groups, int64_t M, int32_t K, 
     return {};
 }
 
+// mms_gru_gates_group: the refusal rules of mms_gru_group with the pre-activation blocks gi / gh in x's place (and b_hh read 16 bytes
+// at a time)
+static inline std::string check_gru_gates_group(int32_t groups, int64_t M, int32_t H, const float* const* gi, const float* const* gh, int64_t g_pitch,
+                                                const float* const* h, int64_t h_pitch, const float* const* mask, int64_t mask_pitch,
+                                                const float* const* b_hh, float* const* h_out, int64_t h_out_pitch, float* const* y) {
+    std::string bad = check_groups("mms_gru_gates_group", groups);
+    if (!bad.empty()) return bad;
+    if (!gi || !gh || !h || !b_hh || !h_out) return "mms_gru_gates_group: null pointer (gi, gh, h, b_hh and h_out are required)";
+    if (M < 0 || M > 0x7fffffff || H < 4 || (H % 4) != 0 || H > 1024)
+        return "mms_gru_gates_group: bad shapes (0 <= M <= 2147483647, H a positive multiple of 4, H <= 1024)";
+    if (g_pitch < 3 * (int64_t)H || h_pitch < H || h_out_pitch < H || (g_pitch % 4) != 0 || (h_pitch % 4) != 0 || (h_out_pitch % 4) != 0 || (mask && mask_pitch < 1))
+        return "mms_gru_gates_group: bad pitches (g_pitch >= 3 H, h_pitch >= H, h_out_pitch >= H, each a multiple of 4; mask_pitch >= 1)";
+    for (int g = 0; g < groups; g++) {
+        if (!gi[g] || !gh[g] || !h[g] || !b_hh[g] || !h_out[g] || (mask && !mask[g])) return "mms_gru_gates_group: null pointer in a group";
+        if (((addr(gi[g]) | addr(gh[g]) | addr(h[g]) | addr(b_hh[g]) | addr(h_out[g]) | (y ? addr(y[g]) : 0)) & 15) != 0 || ((mask ? addr(mask[g]) : 0) & 3) != 0)
+            return "mms_gru_gates_group: misaligned pointer in a group (gi, gh, h, b_hh, h_out, y 16-byte aligned)";
+    }
+    for (int g = 0; g < groups; g++)
+        for (int q = 0; q < groups; q++) {
+            if (h_out[g] == h[q] || h_out[g] == gi[q] || h_out[g] == gh[q]) return "mms_gru_gates_group: h_out must not be h, gi or gh";
+            if (y && y[g] && (y[g] == h[q] || y[g] == gi[q] || y[g] == gh[q] || y[g] == h_out[q])) return "mms_gru_gates_group: y must not be h, gi, gh or h_out";
+            if (q != g && (h_out[g] == h_out[q] || (y && y[g] && y[g] == y[q]))) return "mms_gru_gates_group: two groups share a destination";
+        }
+    return {};
+}
+
 // mms_mlp_grad and mms_mlp_grad_rop: the shapes, then (workspace NULL is the size query: nothing else is read) the operands.  The
 // workspace's size and alignment are the HIP build's own; the CPU build needs none.
 static inline std::string check_mlp_shapes(const char* entry, int32_t layers, int64_t M, const int32_t* dims, const int64_t* ws_bytes) {

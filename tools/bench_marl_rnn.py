@@ -14,7 +14,22 @@ end in a device synchronise, after warm-up passes of the same shape; reported as
 Both paths start from the same states; the worst difference of their values is printed as a check that they compute the same thing.
 One JSON line per envs value on stdout (and appended to --out when given).
 
-    python tools/bench_marl_rnn.py [--envs 4096,80] [--rounds 5] [--calls 20] [--out profiles/marl_rnn_bench.jsonl]
+--rnn-format f16x2 (or both) adds the opt-in plane route of GroupedPolicyInference(rnn_format="f16x2") to the same alternating rounds,
+against the grouped fp32 pass of the same process:
+
+  grouped16_ms   the same get_actions of an object built with rnn_format="f16x2" (rnn_route says which route the calls took: envs
+                 that are no multiple of 128 stay on the fp32 route), f16x2_speedup_median = grouped_ms / grouped16_ms
+  rnn16_stages_us  what the route adds per GRU layer, each stage alone for all 20 networks (`--calls` back-to-back launches between
+                 two device events): the splits of x and of the state, the two products (N = 3H) and mms_gru_gates_group with the
+                 bytes it moves per second (gi, gh and h read, h_out and y written)
+  error_vs_f64   rms error of the values and of the actors' / critics' new states against float64 copies of the modules: the fp32
+                 route, the f16x2 route and the per-agent torch fp32 modules
+
+Kernel times: `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_marl_rnn.py --envs 4096 --profile-passes 20`
+runs nothing but 20 passes of the f16x2 route (after 3 of warm-up); `--kernel-stats DIR/.../*kernel_stats.csv --envs 4096 --profile-passes 20`
+then prints (and appends to --out) one JSON line with every kernel's calls per pass and average time.
+
+    python tools/bench_marl_rnn.py [--envs 4096,80] [--rounds 5] [--calls 20] [--rnn-format fp32|f16x2|both] [--out profiles/marl_rnn_bench.jsonl]
 """
 import argparse
 import ctypes
@@ -37,7 +52,28 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--out", default="")
+    ap.add_argument("--rnn-format", default="fp32", choices=["fp32", "f16x2", "both"])
+    ap.add_argument("--profile-passes", type=int, default=0, help="only this many passes of the f16x2 route: the run to put under rocprofv3")
+    ap.add_argument("--kernel-stats", default="", help="a rocprofv3 kernel_stats.csv of such a run: print its per-kernel times and exit")
     args = ap.parse_args()
+
+    def emit(res):
+        line = json.dumps(res)
+        print(line, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+    if args.kernel_stats:
+        import csv
+        passes = max(args.profile_passes, 1) + 3
+        rows = [r for r in csv.DictReader(open(args.kernel_stats))]
+        kernels = [{"name": r["Name"].split("(")[0][-60:], "calls_per_pass": round(int(r["Calls"]) / passes, 2), "avg_us": round(float(r["AverageNs"]) / 1e3, 2),
+                    "us_per_pass": round(int(r["Calls"]) * float(r["AverageNs"]) / 1e3 / passes, 2)} for r in rows if int(r["Calls"]) >= passes and "mms::" in r["Name"]]        # (the engine's kernels: not the constructor's torch copies)
+        emit({"bench": "marl_rnn_kernels", "rnn_format": "f16x2", "envs": int(args.envs.split(",")[0]), "passes": passes, "source": "rocprofv3 --kernel-trace --stats",
+              "kernels": kernels, "us_per_pass_total": round(sum(k["us_per_pass"] for k in kernels), 1)})
+        return
+    with16 = args.rnn_format != "fp32" or args.profile_passes > 0
     import torch
     import marl_modules as mm
     import marl_rnn_modules as rm
@@ -55,6 +91,7 @@ def main():
         mm.randomize(m, gen)
         m.to(dev).eval()
     grouped = GroupedPolicyInference(actors, critics, seed=3)
+    grouped16 = GroupedPolicyInference(actors, critics, seed=3, rnn_format="f16x2") if with16 else None
 
     for envs in [int(v) for v in args.envs.split(",")]:
         g = torch.Generator(device=dev).manual_seed(envs)
@@ -72,6 +109,15 @@ def main():
 
         def run_grouped():
             grouped.get_actions(sobs_l, obs_l, **kw)
+
+        def run_grouped16():
+            grouped16.get_actions(sobs_l, obs_l, **kw)
+        if args.profile_passes:
+            for _ in range(3 + args.profile_passes):
+                run_grouped16()
+            torch.cuda.synchronize()
+            print("profile passes: %d + 3 at %d envs, route %s" % (args.profile_passes, envs, grouped16.rnn_route))
+            continue
 
         @torch.no_grad()
         def run_per_agent():
@@ -106,14 +152,26 @@ def main():
         torch.cuda.synchronize()
         agree = {"values_max_diff": float((values - v_grouped).abs().max()), "states_max_diff": float((states[1] - s_grouped).abs().max())}
         ts = {"grouped_ms": [], "per_agent_ms": []}
+        if with16:
+            ts["grouped16_ms"] = []
+            for _ in range(3):
+                run_grouped16()
         for _ in range(args.rounds):
             ts["grouped_ms"].append(a_round(run_grouped))
+            if with16:
+                ts["grouped16_ms"].append(a_round(run_grouped16))
             ts["per_agent_ms"].append(a_round(run_per_agent))
         stat = lambda v: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
         res = {"bench": "marl_rnn", "agents": N, "obs": OBS, "share_obs": SOBS, "act": ACT, "hidden": H, "layer_N": LAYER_N, "recurrent_N": R, "envs": envs,
                "rounds": args.rounds, "calls": args.calls, "device": torch.cuda.get_device_name(0), "agree": agree}
         res.update({k: stat(v) for k, v in ts.items()})
         res["speedup_median"] = round(res["per_agent_ms"]["median"] / res["grouped_ms"]["median"], 3)
+        if with16:
+            res["rnn_route"] = grouped16.rnn_route
+            res["f16x2_speedup_median"] = round(res["grouped_ms"]["median"] / res["grouped16_ms"]["median"], 3)
+            res["error_vs_f64"] = errors_vs_f64(torch, rm, actors, critics, obs, sobs, states, states_c, masks, values, run_grouped, run_grouped16, run_per_agent)
+            if grouped16.rnn_route == "f16x2":
+                res["rnn16_stages_us"] = stage_times(torch, _lib, L, idx, stream, envs, args, rnd, masks)
 
         # the kernel alone
         G, M = 2 * N, envs
@@ -136,14 +194,72 @@ def main():
         us = us[1:]                                                          # (the first round is the warm-up)
         med = statistics.median(us)
         res["gru_us"] = {"median": round(med, 2), "min": round(min(us), 2), "max": round(max(us), 2), "TFLOPs": round(12.0 * G * M * H * H / med / 1e6, 2)}
-        line = json.dumps(res)
-        print(line, flush=True)
-        if args.out:
-            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-            with open(args.out, "a") as f:
-                f.write(line + "\n")
+        emit(res)
         del x, h_in, h_out, y, wi, wh
         torch.cuda.empty_cache()
+
+
+def errors_vs_f64(torch, rm, actors, critics, obs, sobs, states, states_c, masks, values, run_fp32, run_f16x2, run_torch):
+    """rms error of (values, actors' new states, critics' new states) against float64 copies of the modules, per path"""
+    import copy
+    truth = []
+    for k in range(N):
+        a, c = copy.deepcopy(actors[k]).double(), copy.deepcopy(critics[k]).double()
+        _, _, v, na, nc = rm.torch_forward(a, c, obs[:, k].double(), sobs.double(), states[0][:, k].double(), states_c[0][:, k].double(), masks.double())
+        truth.append((v[:, 0], na, nc))
+        del a, c
+    tv, ta, tc = (torch.stack([t[i] for t in truth], 1) for i in range(3))
+    rms = lambda t: float(t.pow(2).mean().sqrt())
+    out = {"truth_rms": {"values": rms(tv), "rnn_states": rms(ta), "rnn_states_critic": rms(tc)}}
+    for name, fn in (("fp32", run_fp32), ("f16x2", run_f16x2), ("torch_fp32", run_torch)):
+        fn()
+        torch.cuda.synchronize()
+        out[name] = {"values": rms(values.double() - tv), "rnn_states": rms(states[1].double() - ta), "rnn_states_critic": rms(states_c[1].double() - tc)}
+    return out
+
+
+def stage_times(torch, _lib, L, idx, stream, envs, args, rnd, masks):
+    """the five launches the plane route adds per GRU layer, each alone for 20 networks at M = envs, K = H: median us (min - max)"""
+    G, M = 2 * N, envs
+    tab = lambda ts_: (ctypes.c_void_p * len(ts_))(*[t.data_ptr() for t in ts_])
+    u8 = lambda rows: [torch.empty(_lib.h32_bytes(rows, H), dtype=torch.uint8, device="cuda:0") for _ in range(G)]
+    f32 = lambda *s: torch.empty(*s, device="cuda:0")
+    x, h_in = [rnd(M, H) for _ in range(G)], torch.tanh(rnd(G, M, R, H))
+    h_out, y = f32(G, M, R, H), f32(G, M, H)
+    w = [rnd(3 * H, H) * H ** -0.5 for _ in range(G)]
+    bi, bh = [rnd(3 * H) * 0.1 for _ in range(G)], [rnd(3 * H) * 0.1 for _ in range(G)]
+    px, ph, pw = u8(M), u8(M), u8(3 * H)
+    xs, xi, hs, hi, ws, wi = f32(G, M), f32(G, M), f32(G, M), f32(G, M), f32(G, 3 * H), f32(G, 3 * H)
+    gi, gh = f32(G, M, 3 * H), f32(G, M, 3 * H)
+    ub = lambda t: tab(list(t.unbind(0)))
+    _lib.check(L.mms_weight_planes16_group(idx, G, (ctypes.c_int64 * G)(*[3 * H] * G), (ctypes.c_int32 * G)(*[H] * G), tab(w), tab(pw), ub(ws), ub(wi), None, stream),
+               None, "mms_weight_planes16_group", L)
+    none6 = (None,) * 6
+    stages = {
+        "split_x": (L.mms_split_planes16_group, (idx, G, M, H, H, tab(x), tab(px), ub(xs), ub(xi), 0, 0, None, None, None, None, 1e-5, stream)),
+        "split_h": (L.mms_split_planes16_group, (idx, G, M, H, R * H, ub(h_in), tab(ph), ub(hs), ub(hi), 0, 0, None, None, None, None, 1e-5, stream)),
+        "product_gi": (L.mms_linear_group_act_split16, (idx, G, M, 3 * H, H, tab(px), tab(pw), tab(bi), ub(gi), ub(xi), ub(wi), None, 0, 0) + none6 + (stream,)),
+        "product_gh": (L.mms_linear_group_act_split16, (idx, G, M, 3 * H, H, tab(ph), tab(pw), tab(bi), ub(gh), ub(hi), ub(wi), None, 0, 0) + none6 + (stream,)),
+        "gates": (L.mms_gru_gates_group, (idx, G, M, H, ub(gi), ub(gh), 3 * H, ub(h_in), R * H, tab([masks] * G), 1, tab(bh), ub(h_out), R * H, ub(y), stream)),
+    }
+    out = {}
+    for name, (fn, a) in stages.items():
+        us = []
+        for _ in range(args.rounds + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.calls):
+                _lib.check(fn(*a), None, name, L)
+            e1.record()
+            e1.synchronize()
+            us.append(e0.elapsed_time(e1) * 1000 / args.calls)
+        us = us[1:]
+        out[name] = {"median": round(statistics.median(us), 2), "min": round(min(us), 2), "max": round(max(us), 2)}
+    gbytes = 4.0 * G * M * (2 * 3 * H + H + 2 * H) / 1e9
+    out["gates"]["GB"] = round(gbytes, 3)
+    out["gates"]["TB_per_s"] = round(gbytes / out["gates"]["median"] * 1e3, 2)
+    out["product_gi"]["TFLOPs"] = round(2.0 * G * M * 3 * H * H / out["product_gi"]["median"] / 1e6, 1)
+    return out
 
 
 if __name__ == "__main__":
