@@ -38,6 +38,9 @@
  *     (algorithms/marl/actor_critic.py:43-69, 137-155; runner.py:186-216)  mms_row_stats_group, mms_marl_heads_act
  *   RNNLayer's single-step branch of every recurrent agent              mms_gru_group, mms_gru_gates_group
  *     (algorithms/utils/rnn.py:25-29; marl/actor_critic.py:64-65, 164-165)
+ *   RNNLayer's sequence branch in ppo_update and autograd's backward    mms_gru_gates_group (forward),
+ *     through time of its nn.GRU pieces (algorithms/utils/rnn.py:30-77;   mms_gru_gates_grad_group (backward); opt-in,
+ *     reached from marl/mappo_trainer.py:130, happo_trainer.py:121)       config key fused_rnn_update
  *   SquashedGaussianMLPActor heads + rsample + log-probability          mms_sac_heads_act
  *     (algorithms/rl/sac/module.py:23-61; sac.py:166, 374-376)
  *   autograd's backward of that head's epilogue in compute_loss_pi      mms_sac_heads_grad
@@ -567,6 +570,37 @@ int mms_gru_group(int device, int32_t groups, int64_t M, int32_t K, int32_t H, c
 int mms_gru_gates_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* gi, const float* const* gh, int64_t g_pitch,
                         const float* const* h, int64_t h_pitch, const float* const* mask, int64_t mask_pitch,
                         const float* const* b_hh, float* const* h_out, int64_t h_out_pitch, float* const* y, void* hip_stream);
+
+/* The backward of mms_gru_gates_group for up to MMS_MAX_GROUPS networks per call (csrc/gru_grad_kernels.hip): what a GRU's backward
+ * through time does per step besides its matrix products, which stay with the caller's library (algorithms/marl/rnn_seq.py runs the
+ * actor and the critic of one agent as the two groups).  gi, gh (g_pitch), h (h_pitch), mask (mask_pitch), b_hh: the forward's inputs
+ * with the forward's meaning; r, z, n are recomputed by the forward's statements and are bit for bit the forward's.  dh_out_g [M, H] at
+ * dh_out_pitch is d loss / d h'; dy_g [M, H] at dy_pitch (NULL as a whole or per group) a second gradient of the same h' (the forward's
+ * y); G = dh_out + dy, one fp32 addition (dy NULL: G = dh_out).  For g < groups, i < M, j < H, with m = mask_g[i] (NULL: 1):
+ *   hm = m h;  a_* = m gh_* + b_hh_*;  r, z, n as in mms_gru_gates_group
+ *   dpn = G (1 - z) (1 - n^2)          dpz = G (hm - n) z (1 - z)          dpr = dpn a_n r (1 - r)
+ *   dgi_g[i] = [dpr | dpz | dpn]       dgh_g[i] = m [dpr | dpz | r dpn] + 0          (each [M, 3H] at dg_pitch)
+ *   dh_g[i]  = m (G z) + 0             ([M, H] at dh_pitch: the direct path only)
+ *   dbias_g  = the column sums over the M rows of [dpr | dpz | dpn | r dpn], NOT multiplied by m    ([4H]; NULL as a whole or per group:
+ *              not computed)
+ * The caller completes the step: dh_{t-1} = dh + dgh W_hh, db_ih = dbias[0:3H], db_hh = dbias[0:2H] | dbias[3H:4H].  The + 0 makes a
+ * row with mask 0 have dgh and dh of +0 bit for bit, and mask == NULL a mask of ones bit for bit.
+ * dgi, dgh and dh of row i are a function of row i and the group's b_hh alone.  dbias: per-workgroup partials in double in the
+ * workspace over a partition of the rows that is a function of (M, H), one finish pass in a fixed order, rounded once, no atomics --
+ * bit-identical run to run and independent of `groups`.
+ * Workspace as for mms_ppo_loss: workspace == NULL stores the bytes needed (a function of groups, M and H; the CPU build: 0) in
+ * *ws_bytes and returns 0 without reading anything else; otherwise 256-byte aligned with *ws_bytes at least that.  At most two launches
+ * on hip_stream, no host synchronisation; the pointer tables travel in the kernel arguments.
+ * H, M, groups, pitches (dg_pitch as g_pitch; dh_out_pitch, dy_pitch, dh_pitch as h_pitch) and alignments (dgi_g, dgh_g, dh_g, dh_out_g,
+ * dy_g 16 bytes; dbias_g 4): the rules of mms_gru_gates_group.  No destination (dgi_g, dgh_g, dh_g, dbias_g) may be a source (gi_q,
+ * gh_q, h_q, mask_q, b_hh_q, dh_out_q, dy_q) or another destination of any group: refused -- callers ping-pong two dh buffers.  Rows
+ * past M, columns past the views and whatever lies between pitched rows are never written; M == 0 succeeds and writes nothing.  Bad
+ * arguments return non-zero with mms_last_error(NULL) and write nothing. */
+int mms_gru_gates_grad_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* gi, const float* const* gh, int64_t g_pitch,
+                             const float* const* h, int64_t h_pitch, const float* const* mask, int64_t mask_pitch,
+                             const float* const* b_hh, const float* const* dh_out, int64_t dh_out_pitch, const float* const* dy,
+                             int64_t dy_pitch, float* const* dgi, float* const* dgh, int64_t dg_pitch, float* const* dh, int64_t dh_pitch,
+                             float* const* dbias, void* workspace, int64_t* ws_bytes, void* hip_stream);
 
 /* ---- the same layers on the bf16 matrix pipe with fp32 operands carried as three bf16 planes (csrc/split_kernels.hip) -----------
  * An fp32 number is exactly a0 + a1 + a2 with a0 = bf16(a), a1 = bf16(a - a0), a2 = bf16(a - a0 - a1); the product is formed as the six

@@ -20,6 +20,14 @@ then runs `actor.rnn(features, rnn_states, masks)` and `critic.rnn(...)` -- the 
 the loss stays marl_ppo_loss on the gathered fields.  The rollout's side of it is GroupedPolicyInference (mms_gru_group).  The
 generator hands the rows over as the reference's does (generators.py: chunk-major), and RNNLayer reads them as it does there.
 
+`config["fused_rnn_update"]` (absent in the reference's configs; default False = the paragraph above, unchanged): the update runs
+base -> rnn_seq.gru_sequence -> rnn.norm -> head instead -- the GRU of the actor and of the critic in grouped calls, the gate
+arithmetic and its backward in HIP (mms_gru_gates_group, mms_gru_gates_grad_group), every product on the library, the mask applied at
+every step, which for the buffers' 0 / 1 masks is RNNLayer's function without its host read of the masks and its one nn.GRU call per
+piece (rnn_seq.py).  With update_actor=False the actor runs alone under no_grad.  The constructor raises NotImplementedError for
+what gru_sequence refuses: a hidden size that is not a multiple of 4 or above 1024, an actor and a critic of unequal GRU shape, a
+policy that is not recurrent.
+
 `ppo_update` takes the reference's gathered tuple.  `train` draws the permutation exactly as feed_forward_generator does
 (torch.randperm(batch), the same slices), gathers only the network inputs (share_obs, obs) and the returns the normaliser's batch
 moments need, and hands the index vector and the buffer's own tensors to the loss: under the same torch seed it equals a loop of
@@ -49,6 +57,7 @@ import torch.nn as nn
 
 from ...optim import FusedAdam
 from .loss import marl_ppo_loss
+from .rnn_seq import check_grus, gru_sequence
 from .utils.valuenorm import ValueNorm
 
 
@@ -110,6 +119,12 @@ class _Trainer:
         if self._recurrent and not (_is_rnn_layer(getattr(policy.actor, "rnn", None)) and _is_rnn_layer(getattr(policy.critic, "rnn", None))):
             raise NotImplementedError("%s: use_recurrent_policy / use_naive_recurrent_policy need policy.actor.rnn and policy.critic.rnn "
                                       "(RNNLayer: .rnn = nn.GRU, .norm = nn.LayerNorm)" % name)
+        # opt-in (the reference's config has no such key): the recurrent update's GRU through rnn_seq.gru_sequence (module docstring)
+        self._fused_rnn_update = bool(config.get("fused_rnn_update", False))
+        if self._fused_rnn_update:
+            if not self._recurrent:
+                raise NotImplementedError("%s: fused_rnn_update needs use_recurrent_policy or use_naive_recurrent_policy" % name)
+            check_grus([policy.actor.rnn.rnn, policy.critic.rnn.rnn], "%s: fused_rnn_update" % name)
         head = getattr(getattr(policy.actor, "act", None), "action_out", None)
         if head is None or not (hasattr(head, "fc_mean") and hasattr(head, "log_std")):
             raise NotImplementedError("%s: only Box action spaces (ACTLayer.action_out = DiagGaussian) are covered" % name)
@@ -123,6 +138,8 @@ class _Trainer:
         head = actor.act.action_out
         if rnn is None:
             features = lambda net, x, states: _base(net.base, x)
+        elif self._fused_rnn_update:
+            return self._update_tail(*self._fused_rnn_forward(share_obs, obs, rnn, update_actor), returns_rows, fields, indices)
         else:
             features = lambda net, x, states: net.rnn(_base(net.base, x), states, rnn[2])[0]       # actor_critic.py:64-65, 164-165
         values = critic.v_out(features(critic, share_obs, None if rnn is None else rnn[1]))
@@ -133,6 +150,28 @@ class _Trainer:
             with torch.no_grad():
                 mu = head.fc_mean(features(actor, obs, None if rnn is None else rnn[0]))
                 std = torch.sigmoid(head.log_std / head.std_x_coef) * head.std_y_coef
+        return self._update_tail(mu, std, values, returns_rows, fields, indices)
+
+    def _fused_rnn_forward(self, share_obs, obs, rnn, update_actor):
+        """(mu, std, values) with base -> gru_sequence -> rnn.norm -> head: the networks that need gradients in one grouped call, the actor
+        alone under no_grad when it is not updated"""
+        actor, critic = self.policy.actor, self.policy.critic
+        head = actor.act.action_out
+        if update_actor:
+            (ya, _), (yc, _) = gru_sequence([_base(actor.base, obs), _base(critic.base, share_obs)], [rnn[0], rnn[1]], rnn[2], [actor.rnn.rnn, critic.rnn.rnn])
+            mu = head.fc_mean(actor.rnn.norm(ya))
+            std = torch.sigmoid(head.log_std / head.std_x_coef) * head.std_y_coef
+        else:
+            (yc, _), = gru_sequence([_base(critic.base, share_obs)], [rnn[1]], rnn[2], [critic.rnn.rnn])
+            with torch.no_grad():
+                (ya, _), = gru_sequence([_base(actor.base, obs)], [rnn[0]], rnn[2], [actor.rnn.rnn])
+                mu = head.fc_mean(actor.rnn.norm(ya))
+                std = torch.sigmoid(head.log_std / head.std_x_coef) * head.std_y_coef
+        return mu, std, critic.v_out(critic.rnn.norm(yc))
+
+    def _update_tail(self, mu, std, values, returns_rows, fields, indices):
+        """The normaliser, the loss, one backward, the clips and the steps of one update"""
+        actor, critic = self.policy.actor, self.policy.critic
         norm = (None, None)
         if self._use_valuenorm:
             self.value_normalizer.update(returns_rows)                 # ... and the targets stay raw (module docstring)

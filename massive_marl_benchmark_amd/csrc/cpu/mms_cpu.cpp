@@ -26,6 +26,7 @@
 #include "../sac_lane.h"
 #include "../sac_grad_lane.h"
 #include "../gru_lane.h"
+#include "../gru_grad_lane.h"
 #include "lane_step.h"
 
 #define MMS_API extern "C" __attribute__((visibility("default")))
@@ -1039,6 +1040,56 @@ MMS_API int mms_gru_gates_group(int device, int32_t groups, int64_t M, int32_t H
                 if (yg) yg[m * H + j] = o;
             }
         }
+    }
+    return 0;
+}
+// The backward of that gate step (include/mms.h: mms_gru_gates_grad_group) over ../gru_grad_lane.h.  The rows in the chunks of
+// gru_grad_chunk_rows(M, H) (OpenMP over chunks): a chunk's column sums in double over ascending rows, the chunks added in ascending
+// order and rounded once -- the result does not depend on the number of threads or on `groups`.  No workspace.
+MMS_API int mms_gru_gates_grad_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* gi, const float* const* gh, int64_t g_pitch,
+                                     const float* const* h, int64_t h_pitch, const float* const* mask, int64_t mask_pitch, const float* const* b_hh,
+                                     const float* const* dh_out, int64_t dh_out_pitch, const float* const* dy, int64_t dy_pitch, float* const* dgi,
+                                     float* const* dgh, int64_t dg_pitch, float* const* dh, int64_t dh_pitch, float* const* dbias, void* workspace,
+                                     int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_gru_gates_grad_group(groups, M, H, gi, gh, g_pitch, h, h_pitch, mask, mask_pitch, b_hh, dh_out, dh_out_pitch, dy, dy_pitch, dgi, dgh,
+                                           dg_pitch, dh, dh_pitch, dbias, workspace, ws_bytes, 0)))
+        return 1;
+    if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query
+    if (M == 0) return 0;
+    const int64_t chunk = mms::gru_grad_chunk_rows(M, H), nchunks = mms::gru_grad_chunks(M, H);
+    const int C = 4 * H;
+    for (int g = 0; g < groups; g++) {
+        const float* bh = b_hh[g];
+        const float* dyg = dy ? dy[g] : nullptr;
+        float* db = dbias ? dbias[g] : nullptr;
+        std::vector<double> part(db ? (size_t)nchunks * C : 0, 0.0);
+#pragma omp parallel for schedule(static)
+        for (int64_t c = 0; c < nchunks; c++) {
+            double* p = db ? part.data() + c * C : nullptr;
+            const int64_t end = (c + 1) * chunk < M ? (c + 1) * chunk : M;
+            for (int64_t m = c * chunk; m < end; m++) {
+                const float *ir = gi[g] + m * g_pitch, *hr = gh[g] + m * g_pitch, *hs = h[g] + m * h_pitch, *go = dh_out[g] + m * dh_out_pitch;
+                const float* gy = dyg ? dyg + m * dy_pitch : nullptr;
+                float *di = dgi[g] + m * dg_pitch, *dg = dgh[g] + m * dg_pitch, *dhr = dh[g] + m * dh_pitch;
+                const float mk = mask ? mask[g][m * mask_pitch] : 1.f;
+                for (int j = 0; j < H; j++) {
+                    const float G = gy ? go[j] + gy[j] : go[j];
+                    const mms::GruGateGrad o = mms::gru_gates_grad(mask != nullptr, mk, ir[j], ir[H + j], ir[2 * H + j], hr[j], hr[H + j], hr[2 * H + j], bh[j],
+                                                                   bh[H + j], bh[2 * H + j], hs[j], G);
+                    di[j] = o.dpr; di[H + j] = o.dpz; di[2 * H + j] = o.dpn;
+                    dg[j] = o.dgh_r; dg[H + j] = o.dgh_z; dg[2 * H + j] = o.dgh_n;
+                    dhr[j] = o.dh;
+                    if (p) { p[j] += (double)o.dpr; p[H + j] += (double)o.dpz; p[2 * H + j] += (double)o.dpn; p[3 * H + j] += (double)o.rdpn; }
+                }
+            }
+        }
+        if (db)
+            for (int q = 0; q < C; q++) {
+                double s = 0.0;
+                for (int64_t c = 0; c < nchunks; c++) s += part[c * C + q];
+                db[q] = (float)s;
+            }
     }
     return 0;
 }

@@ -13,6 +13,7 @@
 #include "maddpg_args.h"
 #include "gru_args.h"
 #include "gru_gates_args.h"
+#include "gru_grad_args.h"
 
 namespace mms {
 hipError_t launch_step(const StepArgs& a, int task, hipStream_t stream);
@@ -744,6 +745,34 @@ __attribute__((visibility("default"))) int mms_gru_gates_group(int device, int32
     a.g_pitch = g_pitch; a.h_pitch = h_pitch; a.mask_pitch = mask_pitch; a.h_out_pitch = h_out_pitch;
     a.M = (int)M; a.H = H;
     MMS_FREE(mms::launch_gru_gates_group(a, groups, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_gru_gates_grad_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* gi,
+                                                                    const float* const* gh, int64_t g_pitch, const float* const* h, int64_t h_pitch,
+                                                                    const float* const* mask, int64_t mask_pitch, const float* const* b_hh,
+                                                                    const float* const* dh_out, int64_t dh_out_pitch, const float* const* dy,
+                                                                    int64_t dy_pitch, float* const* dgi, float* const* dgh, int64_t dg_pitch,
+                                                                    float* const* dh, int64_t dh_pitch, float* const* dbias, void* workspace,
+                                                                    int64_t* ws_bytes, void* s) {
+    MMS_DEV(device)
+    const bool shapes = groups >= 1 && groups <= MMS_MAX_GROUPS && M >= 0 && M <= 0x7fffffff && H >= 4 && H <= 1024 && (H % 4) == 0;
+    const int64_t need = shapes ? mms::gru_grad_ws_bytes(groups, M, H) : 0;
+    if (refused(check_gru_gates_grad_group(groups, M, H, gi, gh, g_pitch, h, h_pitch, mask, mask_pitch, b_hh, dh_out, dh_out_pitch, dy, dy_pitch, dgi, dgh,
+                                           dg_pitch, dh, dh_pitch, dbias, workspace, ws_bytes, need)))
+        return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }                // the size query
+    mms::GruGradArgs a = {};
+    for (int g = 0; g < groups; g++) {
+        a.gi[g] = gi[g]; a.gh[g] = gh[g]; a.h[g] = h[g]; a.mask[g] = mask ? mask[g] : nullptr; a.b_hh[g] = b_hh[g];
+        a.dh_out[g] = dh_out[g]; a.dy[g] = dy ? dy[g] : nullptr;
+        a.dgi[g] = dgi[g]; a.dgh[g] = dgh[g]; a.dh[g] = dh[g]; a.dbias[g] = dbias ? dbias[g] : nullptr;
+    }
+    a.part = static_cast<double*>(workspace);
+    a.g_pitch = g_pitch; a.h_pitch = h_pitch; a.mask_pitch = mask_pitch; a.dh_out_pitch = dh_out_pitch; a.dy_pitch = dy_pitch;
+    a.dg_pitch = dg_pitch; a.dh_pitch = dh_pitch;
+    a.M = (int)M; a.H = H;
+    MMS_FREE(mms::launch_gru_gates_grad_group(a, groups, (hipStream_t)s));
     return 0;
 }
 

@@ -737,6 +737,54 @@ static inline std::string check_gru_gates_group(int32_t groups, int64_t M, int32
     return {};
 }
 
+// mms_gru_gates_grad_group: ws_bytes and the shapes first (workspace NULL is the size query: nothing else is read), then the forward's
+// rules for the forward's inputs, the same pitch and alignment rules for the gradients, and every destination against every source and
+// every other destination over all groups.  `need`: the build's workspace size (the CPU build: 0).
+static inline std::string check_gru_gates_grad_group(int32_t groups, int64_t M, int32_t H, const float* const* gi, const float* const* gh, int64_t g_pitch,
+                                                     const float* const* h, int64_t h_pitch, const float* const* mask, int64_t mask_pitch,
+                                                     const float* const* b_hh, const float* const* dh_out, int64_t dh_out_pitch, const float* const* dy,
+                                                     int64_t dy_pitch, float* const* dgi, float* const* dgh, int64_t dg_pitch, float* const* dh,
+                                                     int64_t dh_pitch, float* const* dbias, const void* workspace, const int64_t* ws_bytes, int64_t need) {
+    const char* who = "mms_gru_gates_grad_group";
+    std::string bad = check_groups(who, groups);
+    if (!bad.empty()) return bad;
+    if (!ws_bytes) return std::string(who) + ": ws_bytes required";
+    if (M < 0 || M > 0x7fffffff || H < 4 || (H % 4) != 0 || H > 1024)
+        return std::string(who) + ": bad shapes (0 <= M <= 2147483647, H a positive multiple of 4, H <= 1024)";
+    if (!workspace) return {};
+    if (!gi || !gh || !h || !b_hh || !dh_out || !dgi || !dgh || !dh)
+        return std::string(who) + ": null pointer (gi, gh, h, b_hh, dh_out, dgi, dgh and dh are required)";
+    if (g_pitch < 3 * (int64_t)H || dg_pitch < 3 * (int64_t)H || h_pitch < H || dh_out_pitch < H || dh_pitch < H || (dy && dy_pitch < H) || (g_pitch % 4) != 0 ||
+        (dg_pitch % 4) != 0 || (h_pitch % 4) != 0 || (dh_out_pitch % 4) != 0 || (dh_pitch % 4) != 0 || (dy && (dy_pitch % 4) != 0) || (mask && mask_pitch < 1))
+        return std::string(who) + ": bad pitches (g_pitch, dg_pitch >= 3 H; h_pitch, dh_out_pitch, dy_pitch, dh_pitch >= H; each a multiple of 4; mask_pitch >= 1)";
+    if (*ws_bytes < need) return std::string(who) + ": workspace too small (" + std::to_string(*ws_bytes) + " bytes, needs " + std::to_string(need) + ")";
+    if (addr(workspace) & 255) return std::string(who) + ": workspace must be 256-byte aligned";
+    for (int g = 0; g < groups; g++) {
+        if (!gi[g] || !gh[g] || !h[g] || !b_hh[g] || !dh_out[g] || !dgi[g] || !dgh[g] || !dh[g] || (mask && !mask[g])) return std::string(who) + ": null pointer in a group";
+        if (((addr(gi[g]) | addr(gh[g]) | addr(h[g]) | addr(b_hh[g]) | addr(dh_out[g]) | (dy ? addr(dy[g]) : 0) | addr(dgi[g]) | addr(dgh[g]) | addr(dh[g])) & 15) != 0 ||
+            (((mask ? addr(mask[g]) : 0) | (dbias ? addr(dbias[g]) : 0)) & 3) != 0)
+            return std::string(who) + ": misaligned pointer in a group (gi, gh, h, b_hh, dh_out, dy, dgi, dgh, dh 16-byte aligned)";
+    }
+    for (int g = 0; g < groups; g++) {
+        const float* dst[4] = {dgi[g], dgh[g], dh[g], dbias ? dbias[g] : nullptr};
+        for (int k = 0; k < 4; k++) {
+            if (!dst[k]) continue;
+            for (int l = k + 1; l < 4; l++)
+                if (dst[k] == dst[l]) return std::string(who) + ": two destinations share an address";
+            for (int q = 0; q < groups; q++) {
+                const float* src[7] = {gi[q], gh[q], h[q], mask ? mask[q] : nullptr, b_hh[q], dh_out[q], dy ? dy[q] : nullptr};
+                for (int l = 0; l < 7; l++)
+                    if (dst[k] == src[l]) return std::string(who) + ": a destination (dgi, dgh, dh, dbias) must not be a source (gi, gh, h, mask, b_hh, dh_out, dy)";
+                if (q == g) continue;
+                const float* other[4] = {dgi[q], dgh[q], dh[q], dbias ? dbias[q] : nullptr};
+                for (int l = 0; l < 4; l++)
+                    if (dst[k] == other[l]) return std::string(who) + ": two groups share a destination";
+            }
+        }
+    }
+    return {};
+}
+
 // mms_mlp_grad and mms_mlp_grad_rop: the shapes, then (workspace NULL is the size query: nothing else is read) the operands.  The
 // workspace's size and alignment are the HIP build's own; the CPU build needs none.
 static inline std::string check_mlp_shapes(const char* entry, int32_t layers, int64_t M, const int32_t* dims, const int64_t* ws_bytes) {
