@@ -41,6 +41,9 @@
  *   RNNLayer's sequence branch in ppo_update and autograd's backward    mms_gru_gates_group (forward),
  *     through time of its nn.GRU pieces (algorithms/utils/rnn.py:30-77;   mms_gru_gates_grad_group (backward); opt-in,
  *     reached from marl/mappo_trainer.py:130, happo_trainer.py:121)       config key fused_rnn_update
+ *   MLPLayer's Linear + ELU + LayerNorm blocks in ppo_update and         mms_elu_ln_group (forward),
+ *     autograd's backward of them (algorithms/utils/mlp.py:19-35;          mms_elu_ln_grad_group (backward); opt-in,
+ *     reached from marl/mappo_trainer.py:124-130, happo_trainer.py:115)    config key fused_block_update
  *   SquashedGaussianMLPActor heads + rsample + log-probability          mms_sac_heads_act
  *     (algorithms/rl/sac/module.py:23-61; sac.py:166, 374-376)
  *   autograd's backward of that head's epilogue in compute_loss_pi      mms_sac_heads_grad
@@ -601,6 +604,49 @@ int mms_gru_gates_grad_group(int device, int32_t groups, int64_t M, int32_t H, c
                              const float* const* b_hh, const float* const* dh_out, int64_t dh_out_pitch, const float* const* dy,
                              int64_t dy_pitch, float* const* dgi, float* const* dgh, int64_t dg_pitch, float* const* dh, int64_t dh_pitch,
                              float* const* dbias, void* workspace, int64_t* ws_bytes, void* hip_stream);
+
+/* ---- the `Linear + ELU + LayerNorm` blocks of the MAPPO / HAPPO networks in an update (csrc/elu_ln_kernels.hip) --------------------
+ * What one block of MLPLayer (agents/algorithms/utils/mlp.py:19-27) does behind its matrix product, for up to MMS_MAX_GROUPS networks
+ * of one width per call (algorithms/marl/blocks.py runs the actor and the critic of one agent as the two groups); the products stay with
+ * the caller's library.  z_g [M, H] at z_pitch is the bias-free product x W^T.  For g < groups, i < M, j < H (csrc/elu_ln_lane.h):
+ *   u = z_g[i, j] + bias_g[j];  a = u > 0 ? u : expm1f(u)                                (ELU, alpha = 1; fp32, as torch holds them)
+ *   mean = sum_j(a) / H;  var = sum_j((a - mean)^2) / H  (two-pass, biased, as nn.LayerNorm);  rstd = 1 / sqrt(var + eps)
+ *   y_g[i, j] = (a - mean) rstd gamma_g[j] + beta_g[j]   ([M, H] at y_pitch);   stat_g[i] = (mean, rstd)   ([M, 2], dense)
+ * What is stored (mean, rstd, y) is fp32; what lies between two stored values (the sums, var, (a - mean) rstd) is formed in double from
+ * the fp32 values and rounded once; var and y use the stored, rounded mean and rstd, which is what the backward reads.
+ * z, bias, gamma, beta, y, stat: HOST arrays of `groups` device pointers; pitches in floats.  A streaming kernel without atomics; the
+ * order of a row's sums is a function of H alone, so y_g[i, :] and stat_g[i] are a function of row i and the group's parameters only,
+ * not of M, groups, the pitches or where the row sits, and runs are bit-identical.
+ * H a positive multiple of 4 up to 1024; z_pitch, y_pitch >= H and multiples of 4; z_g, bias_g, gamma_g, beta_g, y_g 16-byte aligned,
+ * stat_g 8; eps >= 0; M >= 0 (M == 0 succeeds and touches nothing); groups 1..MMS_MAX_GROUPS.  No destination (y_g, stat_g) may be a
+ * source or another destination of any group.  Rows past M, columns past H and whatever lies between pitched rows are never written.
+ * One launch on hip_stream, no host synchronisation.  Bad arguments return non-zero with mms_last_error(NULL) and write nothing. */
+int mms_elu_ln_group(int device, int32_t groups, int64_t M, int32_t H, float eps, const float* const* z, int64_t z_pitch,
+                     const float* const* bias, const float* const* gamma, const float* const* beta, float* const* y, int64_t y_pitch,
+                     float* const* stat, void* hip_stream);
+
+/* The backward of mms_elu_ln_group.  z (z_pitch), bias, gamma: the forward's inputs; stat: the forward's output; u, a and
+ * xhat = (a - mean) rstd are recomputed from them by the forward's statements and are bit for bit the forward's.  dy_g [M, H] at
+ * dy_pitch is d loss / d y.  For g < groups, i < M, j < H:
+ *   q = dy gamma;  c1 = sum_j(q) / H;  c2 = sum_j(q xhat) / H                          (in double, as xhat)
+ *   da = rstd (q - c1 - xhat c2);  dz_g[i, j] = da (u > 0 ? 1 : a + 1), rounded once     ([M, H] at dz_pitch)
+ *   dparams_g = the column sums over the M rows of [dz | dy xhat | dy] = [dbias | dgamma | dbeta]   ([3H]; NULL as a whole or per
+ *               group: not computed)
+ * The caller completes the block: dW = dz^T x, dx = dz W.  dz_g[i, :] is a function of row i and the group's parameters alone.
+ * dparams: per-workgroup partials in double in the workspace over a partition of the rows that is a function of (M, H), one finish
+ * pass in a fixed order, rounded once, no atomics -- bit-identical run to run and independent of `groups`.  M == 0 succeeds and
+ * writes zeros into every dparams_g, nothing else.
+ * Workspace as for mms_gru_gates_grad_group: workspace == NULL stores the bytes needed (a function of groups, M and H; the CPU build:
+ * 0) in *ws_bytes and returns 0 without reading anything else; otherwise 256-byte aligned with *ws_bytes at least that.  At most two
+ * launches on hip_stream, no memset, no host synchronisation; the pointer tables travel in the kernel arguments.
+ * H, M, groups, pitches and alignments: the rules of mms_elu_ln_group (dy_g, dz_g 16 bytes, dparams_g 4).  No destination (dz_g,
+ * dparams_g) may be a source (z_q, bias_q, gamma_q, stat_q, dy_q) or another destination of any group.  Rows past M, columns past H
+ * and whatever lies between pitched rows are never written.  Bad arguments return non-zero with mms_last_error(NULL) and write
+ * nothing. */
+int mms_elu_ln_grad_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* z, int64_t z_pitch,
+                          const float* const* bias, const float* const* gamma, const float* const* stat, const float* const* dy,
+                          int64_t dy_pitch, float* const* dz, int64_t dz_pitch, float* const* dparams, void* workspace,
+                          int64_t* ws_bytes, void* hip_stream);
 
 /* ---- the same layers on the bf16 matrix pipe with fp32 operands carried as three bf16 planes (csrc/split_kernels.hip) -----------
  * An fp32 number is exactly a0 + a1 + a2 with a0 = bf16(a), a1 = bf16(a - a0), a2 = bf16(a - a0 - a1); the product is formed as the six

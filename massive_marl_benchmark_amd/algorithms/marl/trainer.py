@@ -28,6 +28,15 @@ piece (rnn_seq.py).  With update_actor=False the actor runs alone under no_grad.
 what gru_sequence refuses: a hidden size that is not a multiple of 4 or above 1024, an actor and a critic of unequal GRU shape, a
 policy that is not recurrent.
 
+`config["fused_block_update"]` (absent in the reference's configs; default False = unchanged): every MLPBase.forward of an update --
+on the feed-forward route, the RNNLayer route and the fused_rnn_update route alike -- runs through blocks.mlp_base instead: per block
+level one library product per network and ONE grouped call for the ELU, the LayerNorm and the rows' statistics
+(mms_elu_ln_group), their backward with the bias, gamma and beta gradients in one call as well (mms_elu_ln_grad_group), two [M, H]
+tensors less saved per block.  With update_actor=True the actor and the critic share the grouped calls; with update_actor=False
+the actor runs alone under no_grad.  The constructor raises NotImplementedError for what mlp_base refuses (blocks.check_blocks): a block
+that is not Linear with bias + ELU(alpha=1) + affine LayerNorm, differing eps, a hidden width that is not a multiple of 4 or above
+1024, non-fp32 parameters, an actor and a critic of unequal width or depth.
+
 `ppo_update` takes the reference's gathered tuple.  `train` draws the permutation exactly as feed_forward_generator does
 (torch.randperm(batch), the same slices), gathers only the network inputs (share_obs, obs) and the returns the normaliser's batch
 moments need, and hands the index vector and the buffer's own tensors to the loss: under the same torch seed it equals a loop of
@@ -57,6 +66,7 @@ import torch.nn as nn
 
 from ...optim import FusedAdam
 from .loss import marl_ppo_loss
+from .blocks import check_blocks, mlp_base
 from .rnn_seq import check_grus, gru_sequence
 from .utils.valuenorm import ValueNorm
 
@@ -125,6 +135,10 @@ class _Trainer:
             if not self._recurrent:
                 raise NotImplementedError("%s: fused_rnn_update needs use_recurrent_policy or use_naive_recurrent_policy" % name)
             check_grus([policy.actor.rnn.rnn, policy.critic.rnn.rnn], "%s: fused_rnn_update" % name)
+        # opt-in (likewise): the bases' ELU + LayerNorm blocks through blocks.mlp_base (module docstring)
+        self._fused_block_update = bool(config.get("fused_block_update", False))
+        if self._fused_block_update:
+            check_blocks([getattr(policy.actor, "base", None), getattr(policy.critic, "base", None)], "%s: fused_block_update" % name)
         head = getattr(getattr(policy.actor, "act", None), "action_out", None)
         if head is None or not (hasattr(head, "fc_mean") and hasattr(head, "log_std")):
             raise NotImplementedError("%s: only Box action spaces (ACTLayer.action_out = DiagGaussian) are covered" % name)
@@ -136,12 +150,13 @@ class _Trainer:
         """rnn: None, or (rnn_states, rnn_states_critic, masks) of a recurrent generator's sample"""
         actor, critic = self.policy.actor, self.policy.critic
         head = actor.act.action_out
+        base = self._bases(share_obs, obs, update_actor)
         if rnn is None:
-            features = lambda net, x, states: _base(net.base, x)
+            features = lambda net, x, states: base(net, x)
         elif self._fused_rnn_update:
-            return self._update_tail(*self._fused_rnn_forward(share_obs, obs, rnn, update_actor), returns_rows, fields, indices)
+            return self._update_tail(*self._fused_rnn_forward(share_obs, obs, rnn, update_actor, base), returns_rows, fields, indices)
         else:
-            features = lambda net, x, states: net.rnn(_base(net.base, x), states, rnn[2])[0]       # actor_critic.py:64-65, 164-165
+            features = lambda net, x, states: net.rnn(base(net, x), states, rnn[2])[0]             # actor_critic.py:64-65, 164-165
         values = critic.v_out(features(critic, share_obs, None if rnn is None else rnn[1]))
         if update_actor:
             mu = head.fc_mean(features(actor, obs, None if rnn is None else rnn[0]))
@@ -152,19 +167,34 @@ class _Trainer:
                 std = torch.sigmoid(head.log_std / head.std_x_coef) * head.std_y_coef
         return self._update_tail(mu, std, values, returns_rows, fields, indices)
 
-    def _fused_rnn_forward(self, share_obs, obs, rnn, update_actor):
+    def _bases(self, share_obs, obs, update_actor):
+        """base(net, x): MLPBase.forward of the actor (on obs) or the critic (on share_obs).  Without fused_block_update the module's own
+        layers where the caller asks for them; with it mlp_base up front: both networks in grouped calls, or the critic alone and
+        the actor under no_grad when it is not updated"""
+        if not self._fused_block_update:
+            return lambda net, x: _base(net.base, x)
+        actor, critic = self.policy.actor, self.policy.critic
+        if update_actor:
+            fa, fc = mlp_base([obs, share_obs], [actor.base, critic.base])
+        else:
+            fc, = mlp_base([share_obs], [critic.base])
+            with torch.no_grad():
+                fa, = mlp_base([obs], [actor.base])
+        return lambda net, x: fa if net is actor else fc
+
+    def _fused_rnn_forward(self, share_obs, obs, rnn, update_actor, base):
         """(mu, std, values) with base -> gru_sequence -> rnn.norm -> head: the networks that need gradients in one grouped call, the actor
         alone under no_grad when it is not updated"""
         actor, critic = self.policy.actor, self.policy.critic
         head = actor.act.action_out
         if update_actor:
-            (ya, _), (yc, _) = gru_sequence([_base(actor.base, obs), _base(critic.base, share_obs)], [rnn[0], rnn[1]], rnn[2], [actor.rnn.rnn, critic.rnn.rnn])
+            (ya, _), (yc, _) = gru_sequence([base(actor, obs), base(critic, share_obs)], [rnn[0], rnn[1]], rnn[2], [actor.rnn.rnn, critic.rnn.rnn])
             mu = head.fc_mean(actor.rnn.norm(ya))
             std = torch.sigmoid(head.log_std / head.std_x_coef) * head.std_y_coef
         else:
-            (yc, _), = gru_sequence([_base(critic.base, share_obs)], [rnn[1]], rnn[2], [critic.rnn.rnn])
+            (yc, _), = gru_sequence([base(critic, share_obs)], [rnn[1]], rnn[2], [critic.rnn.rnn])
             with torch.no_grad():
-                (ya, _), = gru_sequence([_base(actor.base, obs)], [rnn[0]], rnn[2], [actor.rnn.rnn])
+                (ya, _), = gru_sequence([base(actor, obs)], [rnn[0]], rnn[2], [actor.rnn.rnn])
                 mu = head.fc_mean(actor.rnn.norm(ya))
                 std = torch.sigmoid(head.log_std / head.std_x_coef) * head.std_y_coef
         return mu, std, critic.v_out(critic.rnn.norm(yc))

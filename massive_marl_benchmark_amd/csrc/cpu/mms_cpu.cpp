@@ -27,6 +27,7 @@
 #include "../sac_grad_lane.h"
 #include "../gru_lane.h"
 #include "../gru_grad_lane.h"
+#include "../elu_ln_lane.h"
 #include "lane_step.h"
 
 #define MMS_API extern "C" __attribute__((visibility("default")))
@@ -1089,6 +1090,80 @@ MMS_API int mms_gru_gates_grad_group(int device, int32_t groups, int64_t M, int3
                 double s = 0.0;
                 for (int64_t c = 0; c < nchunks; c++) s += part[c * C + q];
                 db[q] = (float)s;
+            }
+    }
+    return 0;
+}
+// The ELU + LayerNorm block behind its product (include/mms.h: mms_elu_ln_group) over ../elu_ln_lane.h: per row, the two sums in double
+// over ascending columns.
+MMS_API int mms_elu_ln_group(int device, int32_t groups, int64_t M, int32_t H, float eps, const float* const* z, int64_t z_pitch, const float* const* bias,
+                             const float* const* gamma, const float* const* beta, float* const* y, int64_t y_pitch, float* const* stat, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_elu_ln_group(groups, M, H, eps, z, z_pitch, bias, gamma, beta, y, y_pitch, stat))) return 1;
+    for (int g = 0; g < groups; g++) {
+#pragma omp parallel for schedule(static)
+        for (int64_t m = 0; m < M; m++) {
+            float a[mms::kEluLnMaxH];
+            const float* zr = z[g] + m * z_pitch;
+            double s = 0.0, v = 0.0;
+            for (int j = 0; j < H; j++) { a[j] = mms::elu_ln_act(mms::elu_ln_u(zr[j], bias[g][j])); s += (double)a[j]; }
+            const float mean = mms::elu_ln_mean(s, H);
+            for (int j = 0; j < H; j++) v += mms::elu_ln_dev2(a[j], mean);
+            const float rstd = mms::elu_ln_rstd(v, H, eps);
+            float* yr = y[g] + m * y_pitch;
+            for (int j = 0; j < H; j++) yr[j] = mms::elu_ln_out(mms::elu_ln_xhat(a[j], mean, rstd), gamma[g][j], beta[g][j]);
+            stat[g][2 * m] = mean;
+            stat[g][2 * m + 1] = rstd;
+        }
+    }
+    return 0;
+}
+// Its backward (include/mms.h: mms_elu_ln_grad_group).  The rows in the chunks of elu_ln_chunk_rows(M, H) (OpenMP over chunks): a
+// chunk's column sums in double over ascending rows, the chunks added in ascending order and rounded once -- the result does not depend
+// on the number of threads or on `groups`.  No workspace.  M == 0: zeros into dparams.
+MMS_API int mms_elu_ln_grad_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* z, int64_t z_pitch, const float* const* bias,
+                                  const float* const* gamma, const float* const* stat, const float* const* dy, int64_t dy_pitch, float* const* dz,
+                                  int64_t dz_pitch, float* const* dparams, void* workspace, int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_elu_ln_grad_group(groups, M, H, z, z_pitch, bias, gamma, stat, dy, dy_pitch, dz, dz_pitch, dparams, workspace, ws_bytes, 0))) return 1;
+    if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query
+    const int64_t chunk = mms::elu_ln_chunk_rows(M, H), nchunks = mms::elu_ln_chunks(M, H);
+    const int C = 3 * H;
+    for (int g = 0; g < groups; g++) {
+        float* dp = dparams ? dparams[g] : nullptr;
+        std::vector<double> part(dp ? (size_t)nchunks * C : 0, 0.0);
+#pragma omp parallel for schedule(static)
+        for (int64_t c = 0; c < nchunks; c++) {
+            double* p = dp ? part.data() + c * C : nullptr;
+            const int64_t end = (c + 1) * chunk < M ? (c + 1) * chunk : M;
+            float u[mms::kEluLnMaxH], a[mms::kEluLnMaxH];
+            double xh[mms::kEluLnMaxH];
+            for (int64_t m = c * chunk; m < end; m++) {
+                const float *zr = z[g] + m * z_pitch, *gy = dy[g] + m * dy_pitch;
+                const float mean = stat[g][2 * m], rstd = stat[g][2 * m + 1];
+                double s1 = 0.0, s2 = 0.0;
+                for (int j = 0; j < H; j++) {
+                    u[j] = mms::elu_ln_u(zr[j], bias[g][j]);
+                    a[j] = mms::elu_ln_act(u[j]);
+                    xh[j] = mms::elu_ln_xhat(a[j], mean, rstd);
+                    const double q = mms::elu_ln_q(gy[j], gamma[g][j]);
+                    s1 += q;
+                    s2 += q * xh[j];
+                }
+                const double c1 = mms::elu_ln_row_mean(s1, H), c2 = mms::elu_ln_row_mean(s2, H);
+                float* dr = dz[g] + m * dz_pitch;
+                for (int j = 0; j < H; j++) {
+                    const float o = mms::elu_ln_dz(u[j], a[j], xh[j], rstd, mms::elu_ln_q(gy[j], gamma[g][j]), c1, c2);
+                    dr[j] = o;
+                    if (p) { p[j] += (double)o; p[H + j] += (double)gy[j] * xh[j]; p[2 * H + j] += (double)gy[j]; }
+                }
+            }
+        }
+        if (dp)
+            for (int q = 0; q < C; q++) {
+                double s = 0.0;
+                for (int64_t c = 0; c < nchunks; c++) s += part[c * C + q];
+                dp[q] = (float)s;
             }
     }
     return 0;

@@ -14,6 +14,7 @@
 #include "gru_args.h"
 #include "gru_gates_args.h"
 #include "gru_grad_args.h"
+#include "elu_ln_args.h"
 
 namespace mms {
 hipError_t launch_step(const StepArgs& a, int task, hipStream_t stream);
@@ -773,6 +774,41 @@ __attribute__((visibility("default"))) int mms_gru_gates_grad_group(int device, 
     a.dg_pitch = dg_pitch; a.dh_pitch = dh_pitch;
     a.M = (int)M; a.H = H;
     MMS_FREE(mms::launch_gru_gates_grad_group(a, groups, (hipStream_t)s));
+    return 0;
+}
+
+// ---- the ELU + LayerNorm blocks of the MARL networks, forward and backward (elu_ln_kernels.hip) ------------------------------------
+
+__attribute__((visibility("default"))) int mms_elu_ln_group(int device, int32_t groups, int64_t M, int32_t H, float eps, const float* const* z, int64_t z_pitch,
+                                                            const float* const* bias, const float* const* gamma, const float* const* beta, float* const* y,
+                                                            int64_t y_pitch, float* const* stat, void* s) {
+    MMS_DEV(device)
+    if (refused(check_elu_ln_group(groups, M, H, eps, z, z_pitch, bias, gamma, beta, y, y_pitch, stat))) return 1;
+    mms::EluLnArgs a = {};
+    for (int g = 0; g < groups; g++) {
+        a.z[g] = z[g]; a.bias[g] = bias[g]; a.gamma[g] = gamma[g]; a.beta[g] = beta[g]; a.y[g] = y[g]; a.stat[g] = stat[g];
+    }
+    a.z_pitch = z_pitch; a.y_pitch = y_pitch; a.eps = eps; a.M = (int)M; a.H = H;
+    MMS_FREE(mms::launch_elu_ln_group(a, groups, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_elu_ln_grad_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* z, int64_t z_pitch,
+                                                                 const float* const* bias, const float* const* gamma, const float* const* stat,
+                                                                 const float* const* dy, int64_t dy_pitch, float* const* dz, int64_t dz_pitch,
+                                                                 float* const* dparams, void* workspace, int64_t* ws_bytes, void* s) {
+    MMS_DEV(device)
+    const int64_t need = elu_ln_shapes(groups, M, H) ? mms::elu_ln_grad_ws_bytes(groups, M, H) : 0;
+    if (refused(check_elu_ln_grad_group(groups, M, H, z, z_pitch, bias, gamma, stat, dy, dy_pitch, dz, dz_pitch, dparams, workspace, ws_bytes, need))) return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }                // the size query
+    mms::EluLnGradArgs a = {};
+    for (int g = 0; g < groups; g++) {
+        a.z[g] = z[g]; a.bias[g] = bias[g]; a.gamma[g] = gamma[g]; a.stat[g] = stat[g]; a.dy[g] = dy[g]; a.dz[g] = dz[g];
+        a.dparams[g] = dparams ? dparams[g] : nullptr;
+    }
+    a.part = static_cast<double*>(workspace);
+    a.z_pitch = z_pitch; a.dy_pitch = dy_pitch; a.dz_pitch = dz_pitch; a.M = (int)M; a.H = H;
+    MMS_FREE(mms::launch_elu_ln_grad_group(a, groups, (hipStream_t)s));
     return 0;
 }
 

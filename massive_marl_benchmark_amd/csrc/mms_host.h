@@ -785,6 +785,79 @@ static inline std::string check_gru_gates_grad_group(int32_t groups, int64_t M, 
     return {};
 }
 
+// the shapes of mms_elu_ln_group and mms_elu_ln_grad_group
+static inline bool elu_ln_shapes(int32_t groups, int64_t M, int32_t H) {
+    return groups >= 1 && groups <= MMS_MAX_GROUPS && M >= 0 && M <= 0x7fffffff && H >= 4 && (H % 4) == 0 && H <= 1024;
+}
+
+// mms_elu_ln_group: shapes, pitches, then per group the pointers, their alignment and every destination against every source and every
+// other destination over all groups
+static inline std::string check_elu_ln_group(int32_t groups, int64_t M, int32_t H, float eps, const float* const* z, int64_t z_pitch, const float* const* bias,
+                                             const float* const* gamma, const float* const* beta, float* const* y, int64_t y_pitch, float* const* stat) {
+    const char* who = "mms_elu_ln_group";
+    std::string bad = check_groups(who, groups);
+    if (!bad.empty()) return bad;
+    if (!elu_ln_shapes(groups, M, H)) return std::string(who) + ": bad shapes (0 <= M <= 2147483647, H a positive multiple of 4, H <= 1024)";
+    if (!(eps >= 0.f)) return std::string(who) + ": eps must be >= 0";
+    if (!z || !bias || !gamma || !beta || !y || !stat) return std::string(who) + ": null pointer (z, bias, gamma, beta, y and stat are required)";
+    if (z_pitch < H || y_pitch < H || (z_pitch % 4) != 0 || (y_pitch % 4) != 0) return std::string(who) + ": bad pitches (z_pitch, y_pitch >= H, each a multiple of 4)";
+    for (int g = 0; g < groups; g++) {
+        if (!z[g] || !bias[g] || !gamma[g] || !beta[g] || !y[g] || !stat[g]) return std::string(who) + ": null pointer in a group";
+        if (((addr(z[g]) | addr(bias[g]) | addr(gamma[g]) | addr(beta[g]) | addr(y[g])) & 15) != 0 || (addr(stat[g]) & 7) != 0)
+            return std::string(who) + ": misaligned pointer in a group (z, bias, gamma, beta, y 16-byte aligned, stat 8)";
+    }
+    for (int g = 0; g < groups; g++) {
+        if (y[g] == stat[g]) return std::string(who) + ": two destinations share an address";
+        for (int q = 0; q < groups; q++) {
+            const float* src[4] = {z[q], bias[q], gamma[q], beta[q]};
+            for (int l = 0; l < 4; l++)
+                if (y[g] == src[l] || stat[g] == src[l]) return std::string(who) + ": a destination (y, stat) must not be a source (z, bias, gamma, beta)";
+            if (q != g && (y[g] == y[q] || y[g] == stat[q] || stat[g] == stat[q])) return std::string(who) + ": two groups share a destination";
+        }
+    }
+    return {};
+}
+
+// mms_elu_ln_grad_group: ws_bytes and the shapes first (workspace NULL is the size query: nothing else is read), then as above.
+// `need`: the build's workspace size (the CPU build: 0).
+static inline std::string check_elu_ln_grad_group(int32_t groups, int64_t M, int32_t H, const float* const* z, int64_t z_pitch, const float* const* bias,
+                                                  const float* const* gamma, const float* const* stat, const float* const* dy, int64_t dy_pitch,
+                                                  float* const* dz, int64_t dz_pitch, float* const* dparams, const void* workspace, const int64_t* ws_bytes,
+                                                  int64_t need) {
+    const char* who = "mms_elu_ln_grad_group";
+    std::string bad = check_groups(who, groups);
+    if (!bad.empty()) return bad;
+    if (!ws_bytes) return std::string(who) + ": ws_bytes required";
+    if (!elu_ln_shapes(groups, M, H)) return std::string(who) + ": bad shapes (0 <= M <= 2147483647, H a positive multiple of 4, H <= 1024)";
+    if (!workspace) return {};
+    if (!z || !bias || !gamma || !stat || !dy || !dz) return std::string(who) + ": null pointer (z, bias, gamma, stat, dy and dz are required)";
+    if (z_pitch < H || dy_pitch < H || dz_pitch < H || (z_pitch % 4) != 0 || (dy_pitch % 4) != 0 || (dz_pitch % 4) != 0)
+        return std::string(who) + ": bad pitches (z_pitch, dy_pitch, dz_pitch >= H, each a multiple of 4)";
+    if (*ws_bytes < need) return std::string(who) + ": workspace too small (" + std::to_string(*ws_bytes) + " bytes, needs " + std::to_string(need) + ")";
+    if (addr(workspace) & 255) return std::string(who) + ": workspace must be 256-byte aligned";
+    for (int g = 0; g < groups; g++) {
+        if (!z[g] || !bias[g] || !gamma[g] || !stat[g] || !dy[g] || !dz[g]) return std::string(who) + ": null pointer in a group";
+        if (((addr(z[g]) | addr(bias[g]) | addr(gamma[g]) | addr(dy[g]) | addr(dz[g])) & 15) != 0 || (addr(stat[g]) & 7) != 0 ||
+            ((dparams ? addr(dparams[g]) : 0) & 3) != 0)
+            return std::string(who) + ": misaligned pointer in a group (z, bias, gamma, dy, dz 16-byte aligned, stat 8, dparams 4)";
+    }
+    for (int g = 0; g < groups; g++) {
+        const float* dst[2] = {dz[g], dparams ? dparams[g] : nullptr};
+        if (dst[0] == dst[1]) return std::string(who) + ": two destinations share an address";
+        for (int k = 0; k < 2; k++) {
+            if (!dst[k]) continue;
+            for (int q = 0; q < groups; q++) {
+                const float* src[5] = {z[q], bias[q], gamma[q], stat[q], dy[q]};
+                for (int l = 0; l < 5; l++)
+                    if (dst[k] == src[l]) return std::string(who) + ": a destination (dz, dparams) must not be a source (z, bias, gamma, stat, dy)";
+                if (q == g) continue;
+                if (dst[k] == dz[q] || (dparams && dst[k] == dparams[q])) return std::string(who) + ": two groups share a destination";
+            }
+        }
+    }
+    return {};
+}
+
 // mms_mlp_grad and mms_mlp_grad_rop: the shapes, then (workspace NULL is the size query: nothing else is read) the operands.  The
 // workspace's size and alignment are the HIP build's own; the CPU build needs none.
 static inline std::string check_mlp_shapes(const char* entry, int32_t layers, int64_t M, const int32_t* dims, const int64_t* ws_bytes) {
