@@ -1283,6 +1283,7 @@ def test_split_layers_error(torch_cuda):
             ref = acts[act](torch.nn.functional.linear(x[g].double(), w[g].double(), b[g].double()))
             scale = x[g].abs().double() @ w[g].abs().double().t() + b[g].abs().double()
             assert float(((out.double() - ref).abs() / scale).max()) < 5e-7, (M, N, K, act, g)
+            assert float(((y32[g].double() - ref).abs() / scale).max()) < 5e-7, ("the yardstick itself", M, N, K, act, g)
             e_split.append(out.double() - ref)
             e_f32.append(y32[g].double() - ref)
         es, ef = torch.cat(e_split), torch.cat(e_f32)
@@ -1445,6 +1446,7 @@ def test_split16_layers_error(torch_cuda):
             scale = x[g].abs().double() @ w[g].abs().double().t() + b[g].abs().double()
             # (+ 1.2e-7: ELU is evaluated as expf(v) - 1 in both kernels, half an ulp of 1 whatever |v| -- visible only in the tiny row)
             assert float(((out - ref).abs() - 5e-7 * scale).max()) < 1.2e-7 * max(1.0, wscale), (M, N, K, act, g)
+            assert float(((y32[g].double() - ref).abs() - 5e-7 * scale).max()) < 1.2e-7 * max(1.0, wscale), ("the yardstick itself", M, N, K, act, g)
             keep = torch.ones(M, dtype=torch.bool, device="cuda")
             keep[1] = keep[2] = False                               # (the two rescaled rows would dominate / vanish in an rms over all rows)
             e_split.append((out - ref)[keep])
