@@ -44,6 +44,8 @@
  *   MLPLayer's Linear + ELU + LayerNorm blocks in ppo_update and         mms_elu_ln_group (forward),
  *     autograd's backward of them (algorithms/utils/mlp.py:19-35;          mms_elu_ln_grad_group (backward); opt-in,
  *     reached from marl/mappo_trainer.py:124-130, happo_trainer.py:115)    config key fused_block_update
+ *   ... with the blocks' forward products on the two-plane fp16 layer     mms_elu_ln_planes16_group (forward, leaves y as
+ *     kernel instead of the library                                        fp32 and as H32 planes); opt-in, config key block_products
  *   SquashedGaussianMLPActor heads + rsample + log-probability          mms_sac_heads_act
  *     (algorithms/rl/sac/module.py:23-61; sac.py:166, 374-376)
  *   autograd's backward of that head's epilogue in compute_loss_pi      mms_sac_heads_grad
@@ -624,6 +626,24 @@ int mms_gru_gates_grad_group(int device, int32_t groups, int64_t M, int32_t H, c
 int mms_elu_ln_group(int device, int32_t groups, int64_t M, int32_t H, float eps, const float* const* z, int64_t z_pitch,
                      const float* const* bias, const float* const* gamma, const float* const* beta, float* const* y, int64_t y_pitch,
                      float* const* stat, void* hip_stream);
+
+/* mms_elu_ln_group that leaves y_g in both forms: as fp32 (what the backward's library products read) and as the H32 operand planes of
+ * mms_linear_group_act_split16 (below), which then multiplies the next block without a pass that re-reads and re-writes [M, H].
+ * z .. stat: exactly mms_elu_ln_group's arguments, and y_g, stat_g are bit for bit what it writes.  planes, scale, inv: HOST arrays of
+ * `groups` device pointers; planes_g receives the H32 split of y_g [M, H] (MMS_H32_BYTES(M, H) bytes, the columns from H to the next
+ * multiple of 32 written as zero), scale_g [M] the rows' powers of two (from the row's own largest |y|; an all-zero row keeps 1) and
+ * inv_g [M] their inverses (entries of these two arrays may be NULL).  All three are byte for byte what
+ *   mms_split_planes16_group(device, groups, M, H, y_pitch, y, planes, scale, inv, 0, 0, NULL, NULL, NULL, NULL, eps, stream)
+ * writes when it is run on that y.  The kernel is mms_elu_ln_group's with one more reduction over the row (a maximum: exact in any
+ * order) while a thread still holds its four y: no further read of [M, H], 4 more bytes written per element and 8 per row.
+ * H, pitches, alignments, M, groups: mms_elu_ln_group's rules; planes_g 16-byte aligned, scale_g and inv_g 4.  No destination (y_g,
+ * stat_g, planes_g, scale_g, inv_g) may be a source or another destination of any group.  Rows past M are never written; M == 0
+ * succeeds and touches nothing.  One launch on hip_stream, no atomics, no host synchronisation, the pointer tables in the kernel
+ * arguments; a row's outputs are a function of that row and the group's parameters alone.  Bad arguments return non-zero with
+ * mms_last_error(NULL) and write nothing. */
+int mms_elu_ln_planes16_group(int device, int32_t groups, int64_t M, int32_t H, float eps, const float* const* z, int64_t z_pitch,
+                              const float* const* bias, const float* const* gamma, const float* const* beta, float* const* y, int64_t y_pitch,
+                              float* const* stat, void* const* planes, float* const* scale, float* const* inv, void* hip_stream);
 
 /* The backward of mms_elu_ln_group.  z (z_pitch), bias, gamma: the forward's inputs; stat: the forward's output; u, a and
  * xhat = (a - mean) rstd are recomputed from them by the forward's statements and are bit for bit the forward's.  dy_g [M, H] at

@@ -37,6 +37,14 @@ the actor runs alone under no_grad.  The constructor raises NotImplementedError 
 that is not Linear with bias + ELU(alpha=1) + affine LayerNorm, differing eps, a hidden width that is not a multiple of 4 or above
 1024, non-fp32 parameters, an actor and a critic of unequal width or depth.
 
+`config["block_products"]` (absent in the reference's configs; "library" = the paragraph above, unchanged, or "f16x2"): who forms the
+forward products z = x W^T of those blocks.  "f16x2" sends them to the two-plane fp16 layer kernel of the collect paths
+(mms_linear_group_act_split16), all networks of a level in one launch, with mms_elu_ln_planes16_group leaving each level's output as
+the next level's operand planes (blocks.py); the backward and what is saved stay as they are.  It applies on all three routes, since
+all of them go through mlp_base.  It needs fused_block_update (NotImplementedError without it), a hidden width that is a multiple of
+128 (NotImplementedError in the constructor) and minibatches whose row count is a multiple of 128 (NotImplementedError at the call,
+naming M); any other value raises ValueError.  HATRPO does not read the key.
+
 `ppo_update` takes the reference's gathered tuple.  `train` draws the permutation exactly as feed_forward_generator does
 (torch.randperm(batch), the same slices), gathers only the network inputs (share_obs, obs) and the returns the normaliser's batch
 moments need, and hands the index vector and the buffer's own tensors to the loss: under the same torch seed it equals a loop of
@@ -137,8 +145,11 @@ class _Trainer:
             check_grus([policy.actor.rnn.rnn, policy.critic.rnn.rnn], "%s: fused_rnn_update" % name)
         # opt-in (likewise): the bases' ELU + LayerNorm blocks through blocks.mlp_base (module docstring)
         self._fused_block_update = bool(config.get("fused_block_update", False))
-        if self._fused_block_update:
-            check_blocks([getattr(policy.actor, "base", None), getattr(policy.critic, "base", None)], "%s: fused_block_update" % name)
+        self._block_products = config.get("block_products", "library")
+        if self._fused_block_update or self._block_products != "library":
+            check_blocks([getattr(policy.actor, "base", None), getattr(policy.critic, "base", None)], "%s: fused_block_update" % name, self._block_products)
+        if self._block_products != "library" and not self._fused_block_update:
+            raise NotImplementedError("%s: block_products=%r needs fused_block_update" % (name, self._block_products))
         head = getattr(getattr(policy.actor, "act", None), "action_out", None)
         if head is None or not (hasattr(head, "fc_mean") and hasattr(head, "log_std")):
             raise NotImplementedError("%s: only Box action spaces (ACTLayer.action_out = DiagGaussian) are covered" % name)
@@ -175,11 +186,11 @@ class _Trainer:
             return lambda net, x: _base(net.base, x)
         actor, critic = self.policy.actor, self.policy.critic
         if update_actor:
-            fa, fc = mlp_base([obs, share_obs], [actor.base, critic.base])
+            fa, fc = mlp_base([obs, share_obs], [actor.base, critic.base], self._block_products)
         else:
-            fc, = mlp_base([share_obs], [critic.base])
+            fc, = mlp_base([share_obs], [critic.base], self._block_products)
             with torch.no_grad():
-                fa, = mlp_base([obs], [actor.base])
+                fa, = mlp_base([obs], [actor.base], self._block_products)
         return lambda net, x: fa if net is actor else fc
 
     def _fused_rnn_forward(self, share_obs, obs, rnn, update_actor, base):

@@ -1096,10 +1096,10 @@ MMS_API int mms_gru_gates_grad_group(int device, int32_t groups, int64_t M, int3
 }
 // The ELU + LayerNorm block behind its product (include/mms.h: mms_elu_ln_group) over ../elu_ln_lane.h: per row, the two sums in double
 // over ascending columns.
-MMS_API int mms_elu_ln_group(int device, int32_t groups, int64_t M, int32_t H, float eps, const float* const* z, int64_t z_pitch, const float* const* bias,
-                             const float* const* gamma, const float* const* beta, float* const* y, int64_t y_pitch, float* const* stat, void*) {
-    if (cpu_only(device)) return 1;
-    if (refused(check_elu_ln_group(groups, M, H, eps, z, z_pitch, bias, gamma, beta, y, y_pitch, stat))) return 1;
+// planes != NULL (mms_elu_ln_planes16_group): each row of y is then split as mms_split_planes16_group splits it (split_row16).
+static void elu_ln_rows(int32_t groups, int64_t M, int32_t H, float eps, const float* const* z, int64_t z_pitch, const float* const* bias,
+                        const float* const* gamma, const float* const* beta, float* const* y, int64_t y_pitch, float* const* stat, void* const* planes,
+                        float* const* scale, float* const* inv) {
     for (int g = 0; g < groups; g++) {
 #pragma omp parallel for schedule(static)
         for (int64_t m = 0; m < M; m++) {
@@ -1114,8 +1114,27 @@ MMS_API int mms_elu_ln_group(int device, int32_t groups, int64_t M, int32_t H, f
             for (int j = 0; j < H; j++) yr[j] = mms::elu_ln_out(mms::elu_ln_xhat(a[j], mean, rstd), gamma[g][j], beta[g][j]);
             stat[g][2 * m] = mean;
             stat[g][2 * m + 1] = rstd;
+            if (!planes) continue;
+            float sc, iv;
+            split_row16((uint16_t*)planes[g], m, H, [&](int k) { return yr[k]; }, sc, iv);
+            if (scale[g]) scale[g][m] = sc;
+            if (inv[g]) inv[g][m] = iv;
         }
     }
+}
+MMS_API int mms_elu_ln_group(int device, int32_t groups, int64_t M, int32_t H, float eps, const float* const* z, int64_t z_pitch, const float* const* bias,
+                             const float* const* gamma, const float* const* beta, float* const* y, int64_t y_pitch, float* const* stat, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_elu_ln_group(groups, M, H, eps, z, z_pitch, bias, gamma, beta, y, y_pitch, stat))) return 1;
+    elu_ln_rows(groups, M, H, eps, z, z_pitch, bias, gamma, beta, y, y_pitch, stat, nullptr, nullptr, nullptr);
+    return 0;
+}
+MMS_API int mms_elu_ln_planes16_group(int device, int32_t groups, int64_t M, int32_t H, float eps, const float* const* z, int64_t z_pitch,
+                                      const float* const* bias, const float* const* gamma, const float* const* beta, float* const* y, int64_t y_pitch,
+                                      float* const* stat, void* const* planes, float* const* scale, float* const* inv, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_elu_ln_planes16_group(groups, M, H, eps, z, z_pitch, bias, gamma, beta, y, y_pitch, stat, planes, scale, inv))) return 1;
+    elu_ln_rows(groups, M, H, eps, z, z_pitch, bias, gamma, beta, y, y_pitch, stat, planes, scale, inv);
     return 0;
 }
 // Its backward (include/mms.h: mms_elu_ln_grad_group).  The rows in the chunks of elu_ln_chunk_rows(M, H) (OpenMP over chunks): a

@@ -1,4 +1,5 @@
-// elu_ln_args.h -- kernel arguments of mms_elu_ln_group and mms_elu_ln_grad_group (elu_ln_kernels.hip), shared with the C ABI file
+// elu_ln_args.h -- kernel arguments of mms_elu_ln_group, mms_elu_ln_planes16_group and mms_elu_ln_grad_group (elu_ln_kernels.hip), shared
+// with the C ABI file
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,6 +20,14 @@ struct EluLnArgs {
     int M, H;
 };
 
+// mms_elu_ln_planes16_group: the same call, which also leaves y_g as H32 planes (planes16_lane.h) with the rows' scales
+struct EluLnPlanesArgs {
+    EluLnArgs e;
+    void* planes[MMS_MAX_GROUPS];           // MMS_H32_BYTES(M, H) bytes
+    float* scale[MMS_MAX_GROUPS];           // [M], NULL: not stored
+    float* inv[MMS_MAX_GROUPS];             // [M], NULL: not stored
+};
+
 struct EluLnGradArgs {
     const float* z[MMS_MAX_GROUPS];         // the forward's inputs
     const float* bias[MMS_MAX_GROUPS];
@@ -35,6 +44,7 @@ struct EluLnGradArgs {
 
 int64_t elu_ln_grad_ws_bytes(int groups, int64_t M, int H);
 hipError_t launch_elu_ln_group(const EluLnArgs& a, int groups, hipStream_t s);
+hipError_t launch_elu_ln_planes16_group(const EluLnPlanesArgs& a, int groups, hipStream_t s);
 hipError_t launch_elu_ln_grad_group(const EluLnGradArgs& a, int groups, hipStream_t s);
 
 }  // namespace mms

@@ -1,6 +1,9 @@
 // elu_ln_kernels.hip -- what a `Linear + ELU + LayerNorm` block does besides its matrix products, forward and backward, for up to
-// MMS_MAX_GROUPS networks per call (mms_elu_ln_group, mms_elu_ln_grad_group, include/mms.h; the arithmetic is elu_ln_lane.h's):
+// MMS_MAX_GROUPS networks per call (mms_elu_ln_group, mms_elu_ln_planes16_group, mms_elu_ln_grad_group, include/mms.h; the arithmetic
+// is elu_ln_lane.h's, the operand format planes16_lane.h's):
 //   elu_ln_kernel          per row y = LayerNorm(ELU(z + bias)) and the row's (mean, rstd)
+//   elu_ln_planes_kernel   the same rows by the same statements, and y once more as the H32 operand planes of the two-plane fp16 layer
+//                          kernel (split16_kernels.hip) with the row's scale: what split16_planes_kernel would make of y, byte for byte
 //   elu_ln_grad_kernel     per row dz from z, bias, gamma, the saved (mean, rstd) and dy; per workgroup the 3H column sums
 //                          [dz | dy xhat | dy] of its rows, in double
 //   elu_ln_finish_kernel   one wave per column adds the workgroups' partials in a fixed order and rounds once: dparams [3H]
@@ -28,8 +31,11 @@
 
 #include "elu_ln_args.h"
 #include "elu_ln_lane.h"
+#include "planes16_lane.h"
 
 namespace mms {
+
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 int64_t elu_ln_grad_ws_bytes(int groups, int64_t M, int H) {
     return (((int64_t)groups * elu_ln_chunks(M, H) * 3 * H * (int64_t)sizeof(double)) + 255) & ~(int64_t)255;
@@ -76,13 +82,54 @@ __device__ __forceinline__ void row_sum(double (&v)[K], int q, int p, bool live,
     }
 }
 
-// blockIdx.x: a slot of P rows, walking the rows with the stride of the grid; blockIdx.y: the group
-__global__ void __launch_bounds__(kEluLnBlock) elu_ln_kernel(EluLnArgs a) {
-    __shared__ double s_red[2][1][kEluLnBlock];
+// v <- the largest v over the q threads of the caller's row, in row_sum's three shapes (a maximum does not depend on the order, so
+// the shape only decides who talks to whom).  s: a [256] LDS buffer of its own.
+__device__ __forceinline__ float row_max(float v, int q, int p, bool live, int tid, float* s) {
+    if ((q & (q - 1)) == 0) {
+        for (int m = (q < 64 ? q : 64) >> 1; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+        if (q <= 64) return v;
+        if ((tid & 63) == 0) s[tid >> 6] = v;
+        __syncthreads();
+        const int w0 = (p * q) >> 6, n = q >> 6;                    // w0 + n <= 4
+        float t = s[w0];
+        for (int i = 1; i < n; i++) t = fmaxf(t, s[w0 + i]);
+        return t;
+    }
+    s[tid] = v;
+    __syncthreads();
+    if (!live) return v;
+    const int t0 = p * q;                                           // t0 + q <= P q <= 256
+    float t = s[t0];
+    for (int i = 1; i < q; i++) t = fmaxf(t, s[t0 + i]);
+    return t;
+}
+
+// four columns of a row into its H32 planes (planes16_lane.h: element k of row `row`, its lo value 32 halves on), 8 bytes each
+__device__ __forceinline__ void el_store_planes(_Float16* planes, int64_t row, int KC, int k, float scale, float a, float b, float c, float d) {
+    const float t[4] = {a * scale, b * scale, c * scale, d * scale};
+    f16x4 hi, lo;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        hi[i] = (_Float16)t[i];
+        lo[i] = (_Float16)planes16_lo(t[i], (float)hi[i]);
+    }
+    _Float16* dst = planes16_elem(planes, row, KC, k);              // k a multiple of 4: 8-byte aligned, inside one 32-column chunk
+    *reinterpret_cast<f16x4*>(dst) = hi;
+    *reinterpret_cast<f16x4*>(dst + 32) = lo;
+}
+
+// blockIdx.x: a slot of P rows, walking the rows with the stride of the grid; blockIdx.y: the group.
+// PLANES (mms_elu_ln_planes16_group): the thread still holds its four y when they are stored, so one more reduction over the row -- its
+// largest |y| -- gives the row's power-of-two scale (pow2_scale), and the thread stores its four columns of the hi and of the lo plane
+// as well: what mms_split_planes16_group would make of y, without reading y again.  The columns from H to the next multiple of 32 are
+// written as zero by the row's first threads.  s_max: LDS of its own, the third buffer in turn.
+template <bool PLANES>
+__device__ __forceinline__ void elu_ln_rows(const EluLnArgs& a, const EluLnPlanesArgs* pl, double (*s_red)[1][kEluLnBlock], float* s_max) {
     const int g = blockIdx.y, tid = (int)threadIdx.x;
     const int H = a.H, q = H >> 2, P = kEluLnBlock / q;             // q <= 256 items per row, P >= 1 rows in flight
     const int p = tid / q, c = tid - p * q, j = 4 * c;              // j + 3 < H
     const bool live = p < P;
+    const int KC = (H + 31) >> 5;
     float4 b = make_float4(0.f, 0.f, 0.f, 0.f), ga = b, be = b;
     if (live) { b = el_load(a.bias[g] + j); ga = el_load(a.gamma[g] + j); be = el_load(a.beta[g] + j); }
     for (int64_t base = (int64_t)blockIdx.x * P; base < a.M; base += (int64_t)gridDim.x * P) {      // (the same trips for the whole workgroup)
@@ -98,12 +145,37 @@ __global__ void __launch_bounds__(kEluLnBlock) elu_ln_kernel(EluLnArgs a) {
         double v[1] = {on ? el_sum4(elu_ln_dev2(ax, mean), elu_ln_dev2(ay, mean), elu_ln_dev2(az, mean), elu_ln_dev2(aw, mean)) : 0.0};
         row_sum<1>(v, q, p, live, tid, s_red[1]);
         const float rstd = elu_ln_rstd(v[0], H, a.eps);
+        const float yx = elu_ln_out(elu_ln_xhat(ax, mean, rstd), ga.x, be.x), yy = elu_ln_out(elu_ln_xhat(ay, mean, rstd), ga.y, be.y);
+        const float yz = elu_ln_out(elu_ln_xhat(az, mean, rstd), ga.z, be.z), yw = elu_ln_out(elu_ln_xhat(aw, mean, rstd), ga.w, be.w);
         if (on) {
-            el_store(a.y[g] + row * a.y_pitch + j, elu_ln_out(elu_ln_xhat(ax, mean, rstd), ga.x, be.x), elu_ln_out(elu_ln_xhat(ay, mean, rstd), ga.y, be.y),
-                     elu_ln_out(elu_ln_xhat(az, mean, rstd), ga.z, be.z), elu_ln_out(elu_ln_xhat(aw, mean, rstd), ga.w, be.w));
+            el_store(a.y[g] + row * a.y_pitch + j, yx, yy, yz, yw);
             if (c == 0) *reinterpret_cast<float2*>(a.stat[g] + 2 * row) = make_float2(mean, rstd);
         }
+        if (PLANES) {
+            const float big = row_max(on ? fmaxf(fmaxf(fabsf(yx), fabsf(yy)), fmaxf(fabsf(yz), fabsf(yw))) : 0.f, q, p, live, tid, s_max);
+            if (!on) continue;
+            float scale, inv;
+            pow2_scale(big, scale, inv);
+            _Float16* planes = reinterpret_cast<_Float16*>(pl->planes[g]);
+            el_store_planes(planes, row, KC, j, scale, yx, yy, yz, yw);
+            for (int k = H + j; k < 32 * KC; k += H) el_store_planes(planes, row, KC, k, scale, 0.f, 0.f, 0.f, 0.f);     // the zero tail: at most 7 items
+            if (c == 0) {
+                if (pl->scale[g]) pl->scale[g][row] = scale;
+                if (pl->inv[g]) pl->inv[g][row] = inv;
+            }
+        }
     }
+}
+
+__global__ void __launch_bounds__(kEluLnBlock) elu_ln_kernel(EluLnArgs a) {
+    __shared__ double s_red[2][1][kEluLnBlock];
+    elu_ln_rows<false>(a, nullptr, s_red, nullptr);
+}
+
+__global__ void __launch_bounds__(kEluLnBlock) elu_ln_planes_kernel(EluLnPlanesArgs a) {
+    __shared__ double s_red[2][1][kEluLnBlock];
+    __shared__ float s_max[kEluLnBlock];
+    elu_ln_rows<true>(a.e, &a, s_red, s_max);
 }
 
 // blockIdx.x: the chunk of rows (elu_ln_lane.h: elu_ln_chunk_rows), blockIdx.y: the group
@@ -201,6 +273,16 @@ hipError_t launch_elu_ln_group(const EluLnArgs& a, int groups, hipStream_t s) {
     if (groups < 0 || groups > MMS_MAX_GROUPS || a.M < 0 || a.H < 4 || a.H > kEluLnMaxH || (a.H & 3)) return hipErrorInvalidValue;
     const int64_t P = kEluLnBlock / (a.H >> 2), slots = (a.M + 4 * P - 1) / (4 * P);                // about four trips per workgroup, 4096 slots at the most
     hipLaunchKernelGGL(elu_ln_kernel, dim3((unsigned)(slots < 4096 ? slots : 4096), (unsigned)groups), dim3(kEluLnBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+// the launch of a checked call (mms_host.h: check_elu_ln_planes16_group): elu_ln_kernel's grid
+hipError_t launch_elu_ln_planes16_group(const EluLnPlanesArgs& a, int groups, hipStream_t s) {
+    const EluLnArgs& e = a.e;
+    if (e.M == 0 || groups == 0) return hipSuccess;
+    if (groups < 0 || groups > MMS_MAX_GROUPS || e.M < 0 || e.H < 4 || e.H > kEluLnMaxH || (e.H & 3)) return hipErrorInvalidValue;
+    const int64_t P = kEluLnBlock / (e.H >> 2), slots = (e.M + 4 * P - 1) / (4 * P);
+    hipLaunchKernelGGL(elu_ln_planes_kernel, dim3((unsigned)(slots < 4096 ? slots : 4096), (unsigned)groups), dim3(kEluLnBlock), 0, s, a);
     return hipGetLastError();
 }
 

@@ -793,6 +793,22 @@ __attribute__((visibility("default"))) int mms_elu_ln_group(int device, int32_t 
     return 0;
 }
 
+__attribute__((visibility("default"))) int mms_elu_ln_planes16_group(int device, int32_t groups, int64_t M, int32_t H, float eps, const float* const* z,
+                                                                     int64_t z_pitch, const float* const* bias, const float* const* gamma,
+                                                                     const float* const* beta, float* const* y, int64_t y_pitch, float* const* stat,
+                                                                     void* const* planes, float* const* scale, float* const* inv, void* s) {
+    MMS_DEV(device)
+    if (refused(check_elu_ln_planes16_group(groups, M, H, eps, z, z_pitch, bias, gamma, beta, y, y_pitch, stat, planes, scale, inv))) return 1;
+    mms::EluLnPlanesArgs a = {};
+    for (int g = 0; g < groups; g++) {
+        a.e.z[g] = z[g]; a.e.bias[g] = bias[g]; a.e.gamma[g] = gamma[g]; a.e.beta[g] = beta[g]; a.e.y[g] = y[g]; a.e.stat[g] = stat[g];
+        a.planes[g] = planes[g]; a.scale[g] = scale[g]; a.inv[g] = inv[g];
+    }
+    a.e.z_pitch = z_pitch; a.e.y_pitch = y_pitch; a.e.eps = eps; a.e.M = (int)M; a.e.H = H;
+    MMS_FREE(mms::launch_elu_ln_planes16_group(a, groups, (hipStream_t)s));
+    return 0;
+}
+
 __attribute__((visibility("default"))) int mms_elu_ln_grad_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* z, int64_t z_pitch,
                                                                  const float* const* bias, const float* const* gamma, const float* const* stat,
                                                                  const float* const* dy, int64_t dy_pitch, float* const* dz, int64_t dz_pitch,

@@ -793,8 +793,8 @@ static inline bool elu_ln_shapes(int32_t groups, int64_t M, int32_t H) {
 // mms_elu_ln_group: shapes, pitches, then per group the pointers, their alignment and every destination against every source and every
 // other destination over all groups
 static inline std::string check_elu_ln_group(int32_t groups, int64_t M, int32_t H, float eps, const float* const* z, int64_t z_pitch, const float* const* bias,
-                                             const float* const* gamma, const float* const* beta, float* const* y, int64_t y_pitch, float* const* stat) {
-    const char* who = "mms_elu_ln_group";
+                                             const float* const* gamma, const float* const* beta, float* const* y, int64_t y_pitch, float* const* stat,
+                                             const char* who = "mms_elu_ln_group") {
     std::string bad = check_groups(who, groups);
     if (!bad.empty()) return bad;
     if (!elu_ln_shapes(groups, M, H)) return std::string(who) + ": bad shapes (0 <= M <= 2147483647, H a positive multiple of 4, H <= 1024)";
@@ -813,6 +813,41 @@ static inline std::string check_elu_ln_group(int32_t groups, int64_t M, int32_t 
             for (int l = 0; l < 4; l++)
                 if (y[g] == src[l] || stat[g] == src[l]) return std::string(who) + ": a destination (y, stat) must not be a source (z, bias, gamma, beta)";
             if (q != g && (y[g] == y[q] || y[g] == stat[q] || stat[g] == stat[q])) return std::string(who) + ": two groups share a destination";
+        }
+    }
+    return {};
+}
+
+// mms_elu_ln_planes16_group: mms_elu_ln_group's rules under its own name, then the three further destinations (scale_g and inv_g are
+// optional) against every source and every other destination over all groups
+static inline std::string check_elu_ln_planes16_group(int32_t groups, int64_t M, int32_t H, float eps, const float* const* z, int64_t z_pitch,
+                                                      const float* const* bias, const float* const* gamma, const float* const* beta, float* const* y,
+                                                      int64_t y_pitch, float* const* stat, void* const* planes, float* const* scale, float* const* inv) {
+    const char* who = "mms_elu_ln_planes16_group";
+    std::string bad = check_elu_ln_group(groups, M, H, eps, z, z_pitch, bias, gamma, beta, y, y_pitch, stat, who);
+    if (!bad.empty()) return bad;
+    if (!planes || !scale || !inv) return std::string(who) + ": null pointer (the planes, scale and inv arrays are required; scale and inv entries may be NULL)";
+    for (int g = 0; g < groups; g++) {
+        if (!planes[g]) return std::string(who) + ": null planes pointer in a group";
+        if ((addr(planes[g]) & 15) != 0 || ((addr(scale[g]) | addr(inv[g])) & 3) != 0)
+            return std::string(who) + ": misaligned pointer in a group (planes 16-byte aligned, scale and inv 4)";
+    }
+    for (int g = 0; g < groups; g++) {
+        const void* dst[3] = {planes[g], scale[g], inv[g]};
+        for (int k = 0; k < 3; k++) {
+            if (!dst[k]) continue;
+            for (int l = k + 1; l < 3; l++)
+                if (dst[k] == dst[l]) return std::string(who) + ": two destinations share an address";
+            for (int q = 0; q < groups; q++) {
+                const void* src[4] = {z[q], bias[q], gamma[q], beta[q]};
+                for (int l = 0; l < 4; l++)
+                    if (dst[k] == src[l]) return std::string(who) + ": a destination (planes, scale, inv) must not be a source (z, bias, gamma, beta)";
+                if (dst[k] == y[q] || dst[k] == stat[q]) return std::string(who) + ": two destinations share an address (planes, scale, inv against y, stat)";
+                if (q == g) continue;
+                const void* other[3] = {planes[q], scale[q], inv[q]};
+                for (int l = 0; l < 3; l++)
+                    if (dst[k] == other[l]) return std::string(who) + ": two groups share a destination";
+            }
         }
     }
     return {};
