@@ -6,9 +6,10 @@
 //     x w = hi_x hi_w + 2^-11 (hi_x lo_w + lo_x hi_w) + [2^-22 lo_x lo_w <= 2^-24 |x w|, dropped]
 // is THREE v_mfma_f32_16x16x32_f16 products instead of six bf16 ones, two thirds of the operand bytes, and at 48 KB per 256 x 128
 // k-step THREE LDS stages fit: a slice's DMA (buffer loads into LDS) is in flight across two barriers (counted vmcnt, raw s_barrier)
-// instead of every step draining the queue.  Since round 4 the k-loop keeps a slice's fragments in registers and issues the next
-// slice's ds_reads between the MFMAs (MMS_S16_ROLL, below).  What bounds it, measured with timing builds and an in-kernel clock probe
-// (MMS_S16_EXP / MMS_S16_STAMP; profiles/r04_split16_kloop_experiments.txt): the chip is power-limited in this kernel (1.55 GHz) and
+// instead of every step draining the queue.  The k-loop of a plain layer keeps a slice's fragments in registers and issues the next
+// slice's ds_reads between the MFMAs (the rolling step, below); the LayerNorm-fold variants read a step's fragments behind its barrier
+// (the barrier-then-read step).  What bounds it, measured with timing builds that left out parts of the k-loop and an in-kernel clock
+// probe (profiles/r04_split16_kloop_experiments.txt): the chip is power-limited in this kernel (1.55 GHz) and
 // the matrix pipe is busy 85 % of the k-loop's cycles.  Error against the float64 product, measured like the bf16 kernel's
 // (tests/test_gpu_parity.py::test_split16_layers_error): still below the exact-fp32 MFMA kernel's, whose k-ordered fma chain
 // rounds 16 times as often.
@@ -42,31 +43,6 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4_16 __attribute__((ext_vector_type(4)));
 
-// cache policy of the operand DMA (aux of global_load_lds: 0 default, 2 = nt); A/B knobs, the defaults are what measured fastest
-#ifndef MMS_S16_AUX_X
-#define MMS_S16_AUX_X 0
-#endif
-#ifndef MMS_S16_AUX_W
-#define MMS_S16_AUX_W 0
-#endif
-// the k-loop's form: 1 = rolling fragments (the ds_reads of slice k + 1 issued between the MFMAs of slice k), 0 = round 3's (every step
-// reads its fragments behind its barrier and waits for them); an A/B knob, bit-identical results
-// timing experiments (results INVALID; never in a shipped build): MMS_S16_EXP bit 0 = no operand DMA inside the k-loop, bit 1 = no MFMA
-// (the fragments are kept alive), bit 2 = no fragment reads inside the k-loop
-#ifndef MMS_S16_STAMP
-#define MMS_S16_STAMP 0
-#endif
-#ifndef MMS_S16_EXP
-#define MMS_S16_EXP 0
-#endif
-#if MMS_S16_EXP & 2
-#define MMS_S16_MFMA(a, b, c, x, y, z) ([&] { asm volatile("" ::"v"(a), "v"(b)); return c; }())
-#else
-#define MMS_S16_MFMA(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, x, y, z)
-#endif
-#ifndef MMS_S16_ROLL
-#define MMS_S16_ROLL 1
-#endif
 // ---- fp32 [rows, K] -> H32 planes + per-row scales -----------------------------------------------------------------------------
 // P lanes per row (a power of two, 64 / P rows per wave: a 46-wide row is 8 pieces of 8 k, eight rows share a wave), two passes over
 // the row (largest magnitude and sum, then the planes and the squared deviations): the second pass finds the row in L1 / L2.
@@ -404,10 +380,6 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
     // mms_layer_clock_probe: block 0 reports the clock the chip holds while this launch runs (shader cycles and 100-MHz ticks of its life)
     // (both counters read unconditionally: a branch on a.clock_probe here would put a kernel-argument round trip in front of everything else)
     const uint64_t probe_c0 = __builtin_readcyclecounter(), probe_r0 = __builtin_amdgcn_s_memrealtime();
-#if MMS_S16_STAMP   // phase stamps (timing experiments only: overwrites the first 32 bytes of the first output): shader clocks and 100-MHz ticks of block 0
-    const uint64_t stamp_c0 = __builtin_readcyclecounter(), stamp_r0 = __builtin_amdgcn_s_memrealtime();
-    uint64_t stamp_r12[2] = {0, 0};                  // ... first slice landed, k-loop done (last tile of the block)
-#endif
     const int wm = wave >> 1, wn = wave & 1;
     const int KC = a.KC, N = a.N;
     const int tiles_n = N / G::TN, tiles_m = a.M / G::TM, total = a.tiles;
@@ -456,8 +428,8 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
     // VGPR pairs per operand and added the slice's offset with a v_lshl_add_u64 per piece: 12-24 registers the rolling loop does not have.)
     auto dma_piece = [&](int i, int kc, int buf) {                       // (i: compile time after unrolling)
         const int so = kc * kChunk16;
-        if (i < G::NX) __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lptr16_t)(lds + buf * G::BUF + (wave + 8 * i) * 1024), 16, goff[i], so, 0, MMS_S16_AUX_X);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lptr16_t)(lds + buf * G::BUF + (wave + 8 * i) * 1024), 16, goff[i], so, 0, MMS_S16_AUX_W);
+        if (i < G::NX) __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lptr16_t)(lds + buf * G::BUF + (wave + 8 * i) * 1024), 16, goff[i], so, 0, 0);
+        else __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lptr16_t)(lds + buf * G::BUF + (wave + 8 * i) * 1024), 16, goff[i], so, 0, 0);
     };
     auto dma_slice = [&](int kc, int buf) {
 #pragma unroll
@@ -471,12 +443,11 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
 
     // `acc` takes hi hi, `lo` the two cross products (2^11 times their value); added once at the end
     f32x4 acc[MT][4], lo[MT][4];
-#ifndef MMS_S16_DMA_BEHIND
-#define MMS_S16_DMA_BEHIND (MT == 4)
-#endif
-    constexpr bool kDmaBehindFirstTile = MMS_S16_DMA_BEHIND;
+    // the barrier-then-read step issues the next DMA behind its first row tile's MFMAs (256-row tiles) or in front of the step (128-row tiles)
+    constexpr bool kDmaBehindFirstTile = MT == 4;
 
-    auto step = [&](int buf, bool more, int kc_next, int buf_next) {
+    // ---- the barrier-then-read form of a k-step (the LayerNorm-fold variants) ------------------------------------------------------
+    auto step =[&](int buf, bool more, int kc_next, int buf_next) {
         const uint8_t* base = lds + buf * G::BUF;
         if (!kDmaBehindFirstTile && more) dma_slice(kc_next, buf_next);
         f16x8 wf[4][2];
@@ -504,8 +475,8 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
         }
     };
 
-    // ---- the rolling form of a k-step (MMS_S16_ROLL) ----------------------------------------------------------------------------
-    // Round 3's step above opens with its fragment reads and waits for them: 10 ds_read_b128 behind the barrier, lgkmcnt(0), only then the
+    // ---- the rolling form of a k-step (plain layers) ------------------------------------------------------------------------------
+    // The barrier-then-read step above opens with its fragment reads and waits for them: 10 ds_read_b128 behind the barrier, lgkmcnt(0), only then the
     // first MFMA -- and the two waves of a SIMD do that in lockstep, so the matrix pipe idles for an LDS round trip (all eight waves'
     // reads at once) in every step: per step 1536 cycles of MFMA, ~600 of LDS and ~400 of waits added up to the 2570 measured
     // (profiles/r03_split16_layer_pmc.txt) instead of overlapping.  Here the fragments of slice k sit in registers when step k begins
@@ -527,48 +498,23 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
         xfr[mt][0] = *reinterpret_cast<const f16x8*>(base + (xfrag + mt * 16 * kChunk16));
         xfr[mt][1] = *reinterpret_cast<const f16x8*>(base + ((xfrag + mt * 16 * kChunk16) ^ 64));
     };
-    // Where a wave issues the DMA of slice k + 3 inside step k: behind row tile `qa` (waves 0-3) / `qb` (waves 4-7) -- -1 = in front of the
-    // step's first MFMA, MT - 1 = inside the last row tile, behind its first column pair.  The two waves of a SIMD are waves w and w + 4:
-    // with qa != qb their DMA issue phases (6 instructions that hold the wave's in-order stream for 60-185 cycles each,
-    // MI355X_MICROARCH.md) do not coincide, and one of them feeds the matrix pipe while the other issues.
-#ifndef MMS_S16_DMA_SPREAD
-#define MMS_S16_DMA_SPREAD 0
-#endif
-#ifndef MMS_S16_DMA_QA
-#define MMS_S16_DMA_QA (MT == 4 ? 0 : -1)
-#endif
-#ifndef MMS_S16_DMA_QB
-#define MMS_S16_DMA_QB MMS_S16_DMA_QA
-#endif
-    const int qd = wave >= 4 ? ((MMS_S16_DMA_QB) < MT ? (MMS_S16_DMA_QB) : MT - 1) : ((MMS_S16_DMA_QA) < MT ? (MMS_S16_DMA_QA) : MT - 1);
+    // Where a wave issues the DMA of slice k + 3 inside step k: behind row tile `qd`, -1 = in front of the step's first MFMA.  All NDMA
+    // instructions go together (each holds the wave's in-order stream for 60-185 cycles, MI355X_MICROARCH.md): behind the first row
+    // tile's MFMAs with 256-row tiles, in front of the step with 128-row ones.
+    constexpr int qd = MT == 4 ? 0 : -1;
     auto roll_step = [&](auto more_c, const uint8_t* next, bool dma, int kc_dma, int buf_dma) {
-        constexpr bool more = decltype(more_c)::value && !(MMS_S16_EXP & 4);
-        if (MMS_S16_EXP & 1) dma = false;
-        if (!(MMS_S16_DMA_SPREAD) && dma && qd < 0) dma_slice(kc_dma, buf_dma);
-        // MMS_S16_DMA_SPREAD: the pieces one at a time between the groups of four MFMAs of the first MT - 1 row tiles (piece i behind group
-        // i NG / NDMA, waves 4-7 one group later) instead of all NDMA together
-        constexpr int NG = 3 * (MT - 1);
-        auto spread = [&](int g) {                                       // g: compile time
-            if (!(MMS_S16_DMA_SPREAD) || !dma) return;
-#pragma unroll
-            for (int i = 0; i < G::NDMA; i++) {
-                const int ga = i * NG / G::NDMA, gb = ga + 1 < NG ? ga + 1 : NG - 1;
-                if ((wave >= 4 ? gb : ga) == g) dma_piece(i, kc_dma, buf_dma);
-            }
-        };
+        constexpr bool more = decltype(more_c)::value;
+        if (dma && qd < 0) dma_slice(kc_dma, buf_dma);
 #pragma unroll
         for (int mt = 0; mt < MT - 1; mt++) {
 #pragma unroll
-            for (int nt = 0; nt < 4; nt++) lo[mt][nt] = MMS_S16_MFMA(wfr[nt][1], xfr[mt][0], lo[mt][nt], 0, 0, 0);
-            if (MMS_S16_DMA_SPREAD) { __builtin_amdgcn_sched_barrier(0); spread(3 * mt); __builtin_amdgcn_sched_barrier(0); }
+            for (int nt = 0; nt < 4; nt++) lo[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfr[nt][1], xfr[mt][0], lo[mt][nt], 0, 0, 0);
 #pragma unroll
-            for (int nt = 0; nt < 4; nt++) lo[mt][nt] = MMS_S16_MFMA(wfr[nt][0], xfr[mt][1], lo[mt][nt], 0, 0, 0);
-            if (MMS_S16_DMA_SPREAD) { __builtin_amdgcn_sched_barrier(0); spread(3 * mt + 1); __builtin_amdgcn_sched_barrier(0); }
+            for (int nt = 0; nt < 4; nt++) lo[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfr[nt][0], xfr[mt][1], lo[mt][nt], 0, 0, 0);
 #pragma unroll
-            for (int nt = 0; nt < 4; nt++) acc[mt][nt] = MMS_S16_MFMA(wfr[nt][0], xfr[mt][0], acc[mt][nt], 0, 0, 0);
+            for (int nt = 0; nt < 4; nt++) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfr[nt][0], xfr[mt][0], acc[mt][nt], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            spread(3 * mt + 2);
-            if (!(MMS_S16_DMA_SPREAD) && dma && qd == mt) dma_slice(kc_dma, buf_dma);
+            if (dma && qd == mt) dma_slice(kc_dma, buf_dma);
             if constexpr (more) read_x(next, mt);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -576,25 +522,33 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
 #pragma unroll
         for (int p = 0; p < 2; p++) {
 #pragma unroll
-            for (int q = 0; q < 2; q++) lo[ml][2 * p + q] = MMS_S16_MFMA(wfr[2 * p + q][1], xfr[ml][0], lo[ml][2 * p + q], 0, 0, 0);
+            for (int q = 0; q < 2; q++) lo[ml][2 * p + q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfr[2 * p + q][1], xfr[ml][0], lo[ml][2 * p + q], 0, 0, 0);
 #pragma unroll
-            for (int q = 0; q < 2; q++) lo[ml][2 * p + q] = MMS_S16_MFMA(wfr[2 * p + q][0], xfr[ml][1], lo[ml][2 * p + q], 0, 0, 0);
+            for (int q = 0; q < 2; q++) lo[ml][2 * p + q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfr[2 * p + q][0], xfr[ml][1], lo[ml][2 * p + q], 0, 0, 0);
 #pragma unroll
-            for (int q = 0; q < 2; q++) acc[ml][2 * p + q] = MMS_S16_MFMA(wfr[2 * p + q][0], xfr[ml][0], acc[ml][2 * p + q], 0, 0, 0);
+            for (int q = 0; q < 2; q++) acc[ml][2 * p + q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfr[2 * p + q][0], xfr[ml][0], acc[ml][2 * p + q], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if (!(MMS_S16_DMA_SPREAD) && p == 0 && dma && qd == ml) dma_slice(kc_dma, buf_dma);
             if constexpr (more) { read_w(next, 2 * p); read_w(next, 2 * p + 1); }
             if constexpr (more) if (p == 1) read_x(next, ml);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    // (the LayerNorm-fold variants keep round 3's loop: their epilogue holds 24 more operand registers across the tile boundary, with the
-    //  rolling loop's 64 fragment registers they spill, and the grouped MAPPO pass measured no gain from it: 505 against 496-506 us)
-    constexpr bool kRoll = MMS_S16_ROLL != 0 && LN == 0;
+    // (the LayerNorm-fold variants keep the barrier-then-read step: their epilogue holds 24 more operand registers across the tile boundary,
+    //  with the rolling step's 64 fragment registers they spill, and the grouped MAPPO pass measured no gain from it: 505 against 496-506 us)
+    constexpr bool kRoll = LN == 0;
 
     // 16-byte output stores a lane issues per tile BEHIND the next tile's prefetch (the count the next tile's first wait may leave
     // outstanding besides its own second slice); out_mode 2 stores under a predicate: none counted, the wait then covers them too
     constexpr int kStores = OUT == 2 ? 0 : MT * 4;
+    // The wait at the top of a k-step: the slice it consumes has landed.  What may stay outstanding is younger than that slice: the
+    // previous tile's output stores (the first step of a later tile) and the next slice's DMA.
+    auto wait_landed = [&](bool behind_stores, bool next_in_flight) {
+        if (behind_stores) {
+            if (next_in_flight) wait_vm<G::NDMA + kStores>(); else wait_vm<kStores>();
+        } else {
+            if (next_in_flight) wait_vm<G::NDMA>(); else wait_vm<0>();
+        }
+    };
 
     int v = blockIdx.x;
     setup_tile(v);
@@ -618,9 +572,6 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
                 if (KC > 1) wait_vm<G::NDMA + kStores>(); else wait_vm<kStores>();
             }
             __builtin_amdgcn_s_barrier();                                // slice 0 is there for everyone; everyone has left the previous epilogue
-#if MMS_S16_STAMP
-            const uint64_t stamp_r1 = __builtin_amdgcn_s_memrealtime();
-#endif
             {
                 const int b2 = cur == 0 ? 2 : cur - 1;                   // (cur + 2) % 3
                 if (stores_in_flight && KC > 2) dma_slice(2, b2);
@@ -633,12 +584,7 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
             for (int kt = 0; kt + 1 < KC; kt++) {
                 const int nxt = cur == 2 ? 0 : cur + 1;                  // the buffer of slice kt + 1
                 // slice kt + 1 has to have landed; younger than it: the stores (kt = 0 of a later tile), slice kt + 2
-                const bool two = kt + 2 < KC;
-                if (kt == 0 && stores_in_flight) {
-                    if (two) wait_vm<G::NDMA + kStores>(); else wait_vm<kStores>();
-                } else {
-                    if (two) wait_vm<G::NDMA>(); else wait_vm<0>();
-                }
+                wait_landed(kt == 0 && stores_in_flight, kt + 2 < KC);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // this wave's reads of slice kt are complete
                 __builtin_amdgcn_s_barrier();
                 roll_step(std::true_type{}, lds + nxt * G::BUF, kt + 3 < KC, kt + 3, cur);
@@ -650,22 +596,13 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
             __builtin_amdgcn_s_barrier();
             roll_step(std::false_type{}, lds, false, 0, 0);
             cur = cur == 2 ? 0 : cur + 1;
-#if MMS_S16_STAMP
-            asm volatile("s_nop 0" ::: "memory");
-            stamp_r12[0] = stamp_r1 - stamp_r0;
-            stamp_r12[1] = __builtin_amdgcn_s_memrealtime() - stamp_r0;
-#endif
             blast = cur == 0 ? 2 : cur - 1;                              // the buffer of the last slice: free (see above)
         } else {
             for (int kt = 0; kt < KC; kt++) {
-                const bool ahead = kt + 1 < KC;                             // slice kt + 1 is in flight behind slice kt
+                // slice kt has to have landed; slice kt + 1 is in flight behind it
                 // (slice 1 of a following tile is older than the previous tile's stores as well, so step 1 could leave them outstanding too:
-                //  measured in round 4, no difference -- 0.498-0.506 against 0.495-0.501 ms per grouped MARL pass)
-                if (kt == 0 && stores_in_flight) {
-                    if (ahead) wait_vm<G::NDMA + kStores>(); else wait_vm<kStores>();
-                } else {
-                    if (ahead) wait_vm<G::NDMA>(); else wait_vm<0>();
-                }
+                //  measured, no difference -- 0.498-0.506 against 0.495-0.501 ms per grouped MARL pass)
+                wait_landed(kt == 0 && stores_in_flight, kt + 1 < KC);
                 __builtin_amdgcn_s_barrier();
                 const int nxt = cur == 0 ? 2 : cur - 1;                      // (cur + 2) % 3: the buffer step kt - 1 read
                 step(cur, kt + 2 < KC, kt + 2, nxt);
@@ -862,16 +799,6 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
                 }
             }
         }
-#if MMS_S16_STAMP
-        if (!has_next && blockIdx.x == 0 && t == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            uint64_t* dbg = reinterpret_cast<uint64_t*>(a.y[0]);
-            dbg[0] = __builtin_readcyclecounter() - stamp_c0;
-            dbg[1] = __builtin_amdgcn_s_memrealtime() - stamp_r0;
-            dbg[2] = stamp_r12[0];
-            dbg[3] = stamp_r12[1];
-        }
-#endif
         if (!has_next && a.clock_probe && blockIdx.x == 0 && t == 0) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the block's own stores have left
             a.clock_probe[0] = __builtin_readcyclecounter() - probe_c0;

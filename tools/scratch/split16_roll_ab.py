@@ -3,7 +3,7 @@
 (`ActorCritic.act` hidden layers + value path, 4096 rows, 388 -> 1024 -> 1024 -> 512) and the grouped MAPPO pass (ten agents, 4096 envs)
 return on fixed inputs -- a change of the k-loop's schedule must leave every bit alone -- and HIP-event timings of the same calls.
 
-    MMS_LIB=.../libmms_noroll.so python tools/scratch/split16_roll_ab.py ; python tools/scratch/split16_roll_ab.py
+    MMS_LIB=.../libmms_other.so python tools/scratch/split16_roll_ab.py ; python tools/scratch/split16_roll_ab.py
 """
 import hashlib
 import json
