@@ -8,7 +8,8 @@
 // k-step THREE LDS stages fit: a slice's DMA (buffer loads into LDS) is in flight across two barriers (counted vmcnt, raw s_barrier)
 // instead of every step draining the queue.  The k-loop of a plain layer keeps a slice's fragments in registers and issues the next
 // slice's ds_reads between the MFMAs (the rolling step, below); the LayerNorm-fold variants read a step's fragments behind its barrier
-// (the barrier-then-read step).  What bounds it, measured with timing builds that left out parts of the k-loop and an in-kernel clock
+// (the barrier-then-read step).  A plain layer launched with at most one tile per block ends in the tail (TAIL instantiations): its
+// last two slices row-tile-major, each row tile's epilogue between the MFMAs of the next.  What bounds it, measured with timing builds that left out parts of the k-loop and an in-kernel clock
 // probe (profiles/r04_split16_kloop_experiments.txt): the chip is power-limited in this kernel (1.55 GHz) and
 // the matrix pipe is busy 85 % of the k-loop's cycles.  Error against the float64 product, measured like the bf16 kernel's
 // (tests/test_gpu_parity.py::test_split16_layers_error): still below the exact-fp32 MFMA kernel's, whose k-ordered fma chain
@@ -366,12 +367,32 @@ typedef __attribute__((address_space(3))) void* lptr16_t;
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
+// f(integral_constant<int, I>) for I = I0 .. I1 - 1: the tail's schedule is laid out at compile time (which epilogue piece goes behind
+// which group of MFMAs), so every accumulator and operand index in it is a constant whatever the unroller decides
+template <int I0, int I1, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I0 < I1) {
+        f(std::integral_constant<int, I0>{});
+        static_for<I0 + 1, I1>(f);
+    }
+}
+
+// slices of a tile's k-range that the tail (linear_split16_kernel<..., TAIL = true>) takes from the rolling loop
+[[maybe_unused]] constexpr int kTailSlices = 2;
+// A row tile's epilogue is eight pieces: 0-3 = column tile nt rescaled, activated and written to the wave's scratch rows, 4-7 = a
+// quarter of those rows read back and stored.  Between the MFMAs of the next row tile there are three slots per slice (in front of each
+// group of four MFMAs), six in all; slot i takes pieces [tail_piece(i), tail_piece(i + 1)): the heavy pieces one per slot, the stores share.
+static_assert(kTailSlices == 2, "tail_piece deals eight pieces to 3 x kTailSlices = 6 slots");
+constexpr int tail_piece(int i) { return i < 4 ? i : 4 + 2 * (i - 4); }
+
 // OUT / LN as linear_split_kernel (split_kernels.hip).  The k-loop runs on THREE operand buffers: at the top of step k every wave
 // waits until at most the DMA of slice k + 1 (its own NDMA instructions, the youngest) is outstanding -- slice k has landed --, the
 // raw barrier makes that true for all waves and says that everyone is done reading slice k - 1, whose buffer then takes the DMA of
 // slice k + 2.  Nothing in the loop waits for vmcnt(0) except a tile's last step.
 // ELU: the activation is ELU (compile time: straight-line epilogue); false = a.act at run time (ReLU, tanh, identity: not on a hot path).
-template <int MT, int OUT, int LN, bool ELU>
+// TAIL (plain layers with OUT != 2, launches of at most one tile per block and KC >= kTailSlices -- the host decides): the tile's last kTailSlices slices
+// run row-tile-major behind one barrier, each row tile's epilogue between the MFMAs of the next row tile (the tail, below).
+template <int MT, int OUT, int LN, bool ELU, bool TAIL = false>
 __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)   // (the host pass only needs the launch stub; it has no __amdgpu_buffer_rsrc_t)
     using G = Geom16<MT>;
@@ -549,6 +570,163 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
             if (next_in_flight) wait_vm<G::NDMA>(); else wait_vm<0>();
         }
     };
+
+    // ---- one tile per block: the rolling loop stops kTailSlices early, the rest runs as the tail ----------------------------------
+    // With a single tile per block nothing overlaps the epilogue: ~8 vector instructions per output with the matrix pipe idle, behind
+    // a k-loop in which the vector ALU idles.  So the last T slices are taken row-tile-major: ONE wait + barrier says that they have
+    // landed for every wave (and that everyone has finished reading the slice before them, whose buffer becomes the scratch at
+    // MT = 4), then for mt = 0 .. MT - 1 the T x 12 MFMAs of row tile mt in ascending k and the rolling step's order inside a slice
+    // (wl xh, wh xl into `lo`, wh xh into `acc`) -- every accumulator sees its products in the order it always did, results are bit
+    // for bit those of the plain sequence -- and between them, piece by piece (tail_piece), the epilogue of row tile mt - 1, whose
+    // accumulators are final.  Only the last row tile's epilogue runs bare.  The fragments are re-read from LDS per (row tile, slice)
+    // -- 40 registers against the rolling loop's 64 --, which pays for the epilogue's operands (40), requested at the top of the tail
+    // where no DMA is in flight any more (an ordinary load's vmcnt(0) then drains nothing) and the first row tile's MFMAs hide them.
+    // Barriers per tile: KC - 1 instead of KC + 1.  KC = T is the tail alone; KC < T (one slice: twelve MFMAs per row tile to put ~126
+    // vector instructions behind) stays with the plain sequence -- as a second arm in here its accumulators meet the other arm's in phi
+    // nodes the allocator does not coalesce, 56-416 bytes of scratch in the 256-row instantiations.
+    if constexpr (TAIL) {
+        static_assert(LN == 0 && OUT != 2, "the tail serves the plain layers");
+        constexpr int T = kTailSlices;
+        static_assert(T == 2, "three operand buffers: T slices + the scratch (MT = 4)");
+        setup_tile(blockIdx.x);
+        dma_slice(0, 0);
+        dma_slice(1, 1);                                                // (KC >= T: the host's condition)
+        if (KC > 2) dma_slice(2, 2);
+#pragma unroll
+        for (int i = 0; i < MT; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) { acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; lo[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        int cur = 0;                                                    // the buffer of the tail's first slice
+        if (KC > T) {
+            wait_vm<2 * G::NDMA>();                                     // (KC >= 3: slices 0, 1, 2 are in the queue) slice 0 has landed
+            __builtin_amdgcn_s_barrier();
+#pragma unroll
+            for (int nt = 0; nt < 4; nt++) read_w(lds, nt);
+#pragma unroll
+            for (int mt = 0; mt < MT; mt++) read_x(lds, mt);
+            for (int kt = 0; kt + 1 < KC - T; kt++) {                   // steps that read the next slice's fragments: kt + 3 < KC in all of them
+                const int nxt = cur == 2 ? 0 : cur + 1;
+                wait_vm<G::NDMA>();                                     // slice kt + 1 has landed, slice kt + 2 is in flight behind it
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                roll_step(std::true_type{}, lds + nxt * G::BUF, true, kt + 3, cur);
+                cur = nxt;
+            }
+            roll_step(std::false_type{}, lds, false, 0, 0);             // slice KC - T - 1 from registers: no read, no DMA, no barrier
+            cur = cur == 2 ? 0 : cur + 1;
+        }
+        wait_vm<0>();                                                   // this wave's pieces of the last slices have landed
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                                   // ... everyone's have, and everyone has left the buffer in front of them
+
+        int lane_e = lane;
+        asm volatile("" : "+v"(lane_e));
+        const int r16 = lane_e & 15, g4 = lane_e >> 4;
+        const int mbase = m0 + wm * 16 * MT, nbase = n0 + wn * 64;
+        __builtin_amdgcn_sched_barrier(0);
+        const float* __restrict__ Bv = a.b[gi];
+        const float* __restrict__ Wi = a.winv[gi];
+        const float* __restrict__ Xi = a.xinv[gi];
+        float4 bias[4], wi[4];
+        float xi[MT], ys[MT];
+#pragma unroll
+        for (int nt = 0; nt < 4; nt++) {
+            bias[nt] = *reinterpret_cast<const float4*>(Bv + nbase + 16 * nt + 4 * g4);
+            wi[nt] = *reinterpret_cast<const float4*>(Wi + nbase + 16 * nt + 4 * g4);
+        }
+#pragma unroll
+        for (int mt = 0; mt < MT; mt++) {
+            xi[mt] = Xi[mbase + 16 * mt + r16];
+            ys[mt] = OUT == 1 ? a.yscale[gi][mbase + 16 * mt + r16] : 1.f;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const int act = a.act;
+        constexpr int RS = 2 * kChunk16 + 16;                           // scratch row: 256 bytes of one m (two plane chunks / 64 floats), padded
+        const int ypitch = OUT == 1 ? (N / 32) * kChunk16 : N * 4;
+        const int ycol = OUT == 1 ? (nbase / 32) * kChunk16 : nbase * 4;
+        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
+            reinterpret_cast<uint8_t*>(a.y[gi]) + (size_t)mbase * ypitch + (size_t)ycol, (short)0, 16 * MT * ypitch, 0x00020000);
+        const int yoff = (lane_e >> 4) * ypitch + (lane_e & 15) * 16;
+
+        {
+            // the scratch: at MT = 4 the operand buffer behind the tail's slices (free: see the barrier above), else a region of its own
+            int sb = cur + T;
+            if (sb >= 3) sb -= 3;
+            uint8_t* scr = lds + (G::SCRATCH_IN_BUF ? sb * G::BUF : 3 * G::BUF) + wave * (16 * RS);
+            // piece p of row tile mt's epilogue -- the arithmetic of the plain sequence's epilogue, statement for statement
+            auto piece = [&](auto mt_c, auto p_c) {
+                constexpr int mt = decltype(mt_c)::value, p = decltype(p_c)::value;
+                if constexpr (p < 4) {
+                    constexpr int nt = p;
+                    const f32x4 w4 = f32x4{wi[nt].x, wi[nt].y, wi[nt].z, wi[nt].w};
+                    f32x4 raw = ((acc[mt][nt] + lo[mt][nt] * (1.f / kLoScale)) * w4) * xi[mt];
+                    raw += f32x4{bias[nt].x, bias[nt].y, bias[nt].z, bias[nt].w};
+                    if constexpr (ELU) raw = elu16_4(raw);
+                    else {
+#pragma unroll
+                        for (int r = 0; r < 4; r++) raw[r] = act_apply(raw[r], act);
+                    }
+                    if constexpr (OUT == 1) {
+                        const float ys2k = ys[mt] * kLoScale;
+                        uint32_t h01, h23, l01, l23;
+                        planes16_4(raw, ys[mt], ys2k, h01, h23, l01, l23);
+                        uint8_t* d = scr + r16 * RS + (nt >> 1) * kChunk16 + (nt & 1) * 32 + g4 * 8;
+                        *reinterpret_cast<uint2*>(d) = make_uint2(h01, h23);
+                        *reinterpret_cast<uint2*>(d + 64) = make_uint2(l01, l23);
+                    } else {
+                        *reinterpret_cast<float4*>(scr + r16 * RS + (16 * nt + 4 * g4) * 4) = make_float4(raw[0], raw[1], raw[2], raw[3]);
+                    }
+                } else {
+                    constexpr int j = p - 4;
+                    const int idx = lane_e + 64 * j, row = idx >> 4, off = (idx & 15) * 16;
+                    const u32x4_16 d = *reinterpret_cast<const u32x4_16*>(scr + row * RS + off);
+                    __builtin_amdgcn_raw_buffer_store_b128(d, yr, yoff, (16 * mt + 4 * j) * ypitch, 0);
+                }
+            };
+            // slot i of row tile mt's MFMAs: the pieces of row tile mt - 1 that go there
+            auto slot = [&](auto mt_c, auto i_c) {
+                constexpr int mt = decltype(mt_c)::value, i = decltype(i_c)::value;
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (mt > 0)
+                    static_for<tail_piece(i), tail_piece(i + 1)>([&](auto p_c) { piece(std::integral_constant<int, mt - 1>{}, p_c); });
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            static_for<0, MT>([&](auto mt_c) {
+                constexpr int mt = decltype(mt_c)::value;
+                static_for<0, T>([&](auto s_c) {
+                    constexpr int s = decltype(s_c)::value;
+                    int b = cur + s;
+                    if (b >= 3) b -= 3;
+                    const uint8_t* base = lds + b * G::BUF;
+                    f16x8 wf[4][2], xf[2];
+#pragma unroll
+                    for (int nt = 0; nt < 4; nt++) {
+                        wf[nt][0] = *reinterpret_cast<const f16x8*>(base + (wfrag + nt * 16 * kChunk16));
+                        wf[nt][1] = *reinterpret_cast<const f16x8*>(base + ((wfrag + nt * 16 * kChunk16) ^ 64));
+                    }
+                    xf[0] = *reinterpret_cast<const f16x8*>(base + (xfrag + mt * 16 * kChunk16));
+                    xf[1] = *reinterpret_cast<const f16x8*>(base + ((xfrag + mt * 16 * kChunk16) ^ 64));
+                    slot(mt_c, std::integral_constant<int, 3 * s>{});
+#pragma unroll
+                    for (int nt = 0; nt < 4; nt++) lo[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt][1], xf[0], lo[mt][nt], 0, 0, 0);
+                    slot(mt_c, std::integral_constant<int, 3 * s + 1>{});
+#pragma unroll
+                    for (int nt = 0; nt < 4; nt++) lo[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt][0], xf[1], lo[mt][nt], 0, 0, 0);
+                    slot(mt_c, std::integral_constant<int, 3 * s + 2>{});
+#pragma unroll
+                    for (int nt = 0; nt < 4; nt++) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt][0], xf[0], acc[mt][nt], 0, 0, 0);
+                });
+            });
+            __builtin_amdgcn_sched_barrier(0);
+            static_for<0, 8>([&](auto p_c) { piece(std::integral_constant<int, MT - 1>{}, p_c); });
+        }
+        if (a.clock_probe && blockIdx.x == 0 && t == 0) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the block's own stores have left
+            a.clock_probe[0] = __builtin_readcyclecounter() - probe_c0;
+            a.clock_probe[1] = __builtin_amdgcn_s_memrealtime() - probe_r0;
+        }
+        return;
+    }
 
     int v = blockIdx.x;
     setup_tile(v);
@@ -832,13 +1010,19 @@ hipError_t launch_linear_split16(const Split16LinearArgs& a, int groups, hipStre
 #define MMS_LAUNCH_SPLIT16(MT, OUT, LNF)                                                                                       \
     {                                                                                                                          \
         const bool elu = LNF != 0 || a.act == 1;                                                                               \
-        auto kern = elu ? linear_split16_kernel<MT, OUT, LNF, true> : linear_split16_kernel<MT, OUT, LNF, false>;              \
-        if (hipError_t e = elu ? allow_large_lds<linear_split16_kernel<MT, OUT, LNF, true>>(Geom16<MT>::LDS)                   \
-                               : allow_large_lds<linear_split16_kernel<MT, OUT, LNF, false>>(Geom16<MT>::LDS);                 \
-            e != hipSuccess)                                                                                                   \
-            return e;                                                                                                          \
         Split16LinearArgs b = a;                                                                                               \
         b.tiles = (int)((int64_t)groups * (a.M / (64 * MT)) * (a.N / 128));                                                    \
+        /* one tile per block (plain layers): the instantiation whose epilogue runs between the last slices' MFMAs */          \
+        constexpr bool kTail = LNF == 0 && OUT != 2;                                                                           \
+        const bool tail = kTail && b.tiles <= cus && a.KC >= kTailSlices;                                                      \
+        auto kern = tail ? (elu ? linear_split16_kernel<MT, OUT, LNF, true, kTail> : linear_split16_kernel<MT, OUT, LNF, false, kTail>) \
+                         : (elu ? linear_split16_kernel<MT, OUT, LNF, true> : linear_split16_kernel<MT, OUT, LNF, false>);     \
+        if (hipError_t e = tail ? (elu ? allow_large_lds<linear_split16_kernel<MT, OUT, LNF, true, kTail>>(Geom16<MT>::LDS)    \
+                                       : allow_large_lds<linear_split16_kernel<MT, OUT, LNF, false, kTail>>(Geom16<MT>::LDS))  \
+                                : (elu ? allow_large_lds<linear_split16_kernel<MT, OUT, LNF, true>>(Geom16<MT>::LDS)           \
+                                       : allow_large_lds<linear_split16_kernel<MT, OUT, LNF, false>>(Geom16<MT>::LDS));        \
+            e != hipSuccess)                                                                                                   \
+            return e;                                                                                                          \
         b.clock_probe = g_probe_out ? g_probe_out + 2 * (g_probe_next++ % g_probe_slots) : nullptr;                           \
         const unsigned grid = (unsigned)(b.tiles < cus ? b.tiles : cus);        /* persistent: at most one block per CU */      \
         b.grid = (int)grid;                                                                                                    \
