@@ -36,6 +36,9 @@
  *                                                                        mms_marl_heads_finish
  *   Actor / Critic forward of every MAPPO / HAPPO agent                  mms_linear_group_act, mms_layernorm_group,
  *     (algorithms/marl/actor_critic.py:43-69, 137-155; runner.py:186-216)  mms_row_stats_group, mms_marl_heads_act
+ *   Actor.evaluate_actions before and after every agent's update and    mms_marl_heads_eval (behind the grouped layers)
+ *     the factor product of Runner.train (algorithms/marl/runner.py:282-313;
+ *     utils/act.py evaluate_actions; utils/distributions.py:31-34)
  *   RNNLayer's single-step branch of every recurrent agent              mms_gru_group, mms_gru_gates_group
  *     (algorithms/utils/rnn.py:25-29; marl/actor_critic.py:64-65, 164-165)
  *   RNNLayer's sequence branch in ppo_update and autograd's backward    mms_gru_gates_group (forward),
@@ -527,6 +530,33 @@ int mms_marl_heads_act(int device, int32_t groups, int64_t M, int32_t H, const f
                        const float* const* beta, const float* const* w, const float* const* b, const int32_t* A, const float* const* std,
                        float* const* out, float* const* logp, const int32_t* out_pitch, int64_t* const* counters, uint64_t seed,
                        int64_t row_offset, float eps, void* hip_stream);
+
+/* mms_marl_heads_act's front with the actions GIVEN: the tail of Actor.evaluate_actions (algorithms/utils/act.py evaluate_actions on
+ * a Box space; FixedNormal.log_probs, distributions.py:31-34) and the product that the Runner's train() forms from two such passes per
+ * agent (runner.py:282-313: factor *= prod_j exp(new_logp - old_logp)), in one launch for up to MMS_MAX_GROUPS networks.  h, gamma,
+ * beta, eps, w, b, A as in mms_marl_heads_act (H <= 1024, A[g] <= 16; eps < 0: no LayerNorm, gamma / beta not read); std[g] [A[g]] and
+ * act[g] [M, A[g]] (row pitch act_pitch[g] floats) are required.  With mean_j = b_g[j] + sum_k w_g[j, k] LN(h_g[r])[k]:
+ *   logp_g[r, j]    = log N(act_g[r, j] | mean_j, std_g[j])                 PER DIMENSION, [M, A[g]] at pitch logp_pitch[g]; not summed.
+ *                                                                            logp == NULL or logp[g] == NULL: not stored.
+ *   factor_out_g[r] = factor_in_g[r] * exp(sum_j (logp_g[r, j] - old_logp_g[r, j]))
+ *                                                                            where factor_out[g] != NULL; old_logp[g] ([M, A[g]] at pitch
+ *                                                                            old_pitch[g]) is then required; factor_in == NULL or
+ *                                                                            factor_in[g] == NULL stands for 1; factor_out[g] ==
+ *                                                                            factor_in[g] is the in-place form.  [M] floats each.
+ * Everything between the fp32 inputs and the two outputs is double (csrc/marl_eval_lane.h, one arithmetic for both builds): the
+ * LayerNorm, the head's sums over H, the log-density -- logp is one rounding of it --, the sum over ascending j of the differences
+ * between the fp32 values logp_g[r, j] that are (or would be) stored and old_logp_g[r, j], and the exp, with one rounding to fp32 at
+ * the product: the factor's bits do not depend on whether logp is stored, and with old_logp written by this entry from parameters that
+ * have not moved since, factor_out is factor_in bit for bit.  A pitch array that is NULL stands for A[g].  No atomics; a row's results are a function of that row and network g's
+ * parameters only, not of M, groups or where the row sits.  logp[g] must not be act[g] or old_logp[g].  M >= 0 (M == 0 succeeds and
+ * touches nothing); groups 1..MMS_MAX_GROUPS.  One launch on hip_stream, no host synchronisation.  Bad arguments (A[g] > 16, H > 1024,
+ * groups out of range, a required pointer NULL, a pitch below A[g], factor_out without old_logp) return non-zero with
+ * mms_last_error(NULL) and write nothing. */
+int mms_marl_heads_eval(int device, int32_t groups, int64_t M, int32_t H, const float* const* h, const float* const* gamma,
+                        const float* const* beta, const float* const* w, const float* const* b, const int32_t* A, const float* const* std,
+                        const float* const* act, const int32_t* act_pitch, float* const* logp, const int32_t* logp_pitch,
+                        const float* const* old_logp, const int32_t* old_pitch, const float* const* factor_in, float* const* factor_out,
+                        float eps, void* hip_stream);
 
 /* One GRU cell step for up to MMS_MAX_GROUPS networks in one launch: one layer of the reference's RNNLayer in its single-step
  * branch (algorithms/utils/rnn.py:25-29: nn.GRU on hxs * masks; built into every recurrent actor and critic at

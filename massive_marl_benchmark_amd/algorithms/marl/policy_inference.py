@@ -39,6 +39,9 @@ every base block and both GRU products as split + mms_linear_group_act_split16 i
 layer, a mix of recurrent and feed-forward networks, and non-Box action spaces are not covered: the constructor raises, nothing falls
 back silently.
 
+`evaluate_actions` is the actors-only pass over GIVEN actions that Runner.train asks for before and after every agent's update
+(runner.py:282-313): the same grouped layers, then mms_marl_heads_eval (the log-density and HAPPO's factor product) -- see there.
+
 The noise stream is this build's counter-based generator (seed + agent, global env row, per-row draw counter), as in
 rl/ppo/module.py: the sampled actions differ from torch's draw for the same torch seed, their distribution and the returned
 log-probabilities do not.
@@ -821,6 +824,135 @@ class GroupedPolicyInference:
         if self.recurrent_N:
             return values, actions, (None if deterministic else logp), new_a, new_c
         return values, actions, (None if deterministic else logp)
+
+    # -- the log-density of stored actions (Runner.train's factor passes) -----------------------------------------------------------
+    def _eval_buffers(self, M, planes):
+        """Scratch of evaluate_actions for M rows, its own (the collect step's buffers of another M stay where the cached launches of
+        `_get_actions_planned` point): normalised observations, the actors' two activation buffers, the log-probabilities; for the plane
+        route the operands' planes and row scales, and the unit affine of a LayerNorm that leaves xhat."""
+        E = getattr(self, "_E", None)
+        if E is not None and E["M"] == M and (E["planes"] or not planes):
+            return E
+        dev, n, H = self.device, self.n, self.hidden
+        z = lambda *s, **k: torch.empty(*s, device=dev, **k)
+        ub = lambda t: list(t.unbind(0))
+        E = {"M": M, "planes": bool(planes), "x": ub(z(n, M, self.kp_a)), "h": [ub(z(n, M, H)), ub(z(n, M, H))], "logp": ub(z(n, M, self.act_dim))}
+        if planes:
+            u8 = lambda K: [torch.empty(_lib.h32_bytes(M, K), dtype=torch.uint8, device=dev) for _ in range(n)]
+            W = max(self.kp_a, H)
+            E.update(sx=u8(self.obs_dim), sh=u8(H), xs=ub(z(n, M)), xi=ub(z(n, M)), one=torch.ones(W, device=dev), zero=torch.zeros(W, device=dev))
+        self._E = E
+        return E
+
+    @torch.no_grad()
+    def evaluate_actions(self, obs, actions, agents=None, old_logp=None, factor=None, out=None):
+        """log pi_k(actions_k | obs_k) for the agents `agents` (indices; None: all) from the actors alone -- what the reference's
+        Runner.train asks of `policy.actor.evaluate_actions` before and after every agent's update (runner.py:282-310;
+        actor_critic.py evaluate_actions -> utils/act.py evaluate_actions; FixedNormal.log_probs, distributions.py:31-34) -- in one set of
+        grouped launches: the hidden layers, then mms_marl_heads_eval (the last LayerNorm, fc_mean, the log-density).
+        obs, actions: lists with one [M, obs_dim] / [M, act_dim] float32 view per SELECTED agent, in the order of `agents`; rows may be
+        strided with one common pitch per list (`buffer[k].obs[:-1].reshape(M, -1)`, or agent k's rows of an [M, agents, K] block).
+        Returns the per-agent [M, act_dim] log-probabilities, per dimension (views of a buffer the next call overwrites, or the `out`
+        destinations: a list of [M, act_dim] views with dense rows).
+        old_logp (list of [M, act_dim]) and factor (list of contiguous [M, 1] float32; one tensor for a single agent) together: factor_k
+        *= exp(sum_j (logp_k - old_logp_k)) in place, in the same launch (runner.py:312-313; the sum and the exp in double).
+        The route is get_actions' for that M: two-plane fp16 products where `_split_applies` (split_format "f16x2"; each LayerNorm in
+        memory, without its affine, which the folded weights carry, and every layer's output in fp32: the layer kernel has no fp32 output
+        behind a folded LayerNorm), else the exact-fp32 grouped layers; `eval_route` names the last call's.  A network's tiles do
+        not depend on the group count: evaluate_actions(agents=[k]) returns the bits of entry k of the call over all agents.
+        Calls `_ensure_fresh()` first: a pass after an optimizer step computes with the new parameters.  Recurrent groups raise (the
+        sequence evaluation is RNNLayer's: algorithms/marl/rnn_seq.py)."""
+        if self.recurrent_N:
+            raise NotImplementedError("GroupedPolicyInference.evaluate_actions: recurrent policies evaluate whole sequences (RNNLayer); use the modules")
+        agents = list(range(self.n)) if agents is None else [int(k) for k in agents]
+        k = len(agents)
+        if k == 0 or len(set(agents)) != k or min(agents) < 0 or max(agents) >= self.n:
+            raise ValueError("GroupedPolicyInference.evaluate_actions: agents must be distinct indices below %d" % self.n)
+        if torch.is_tensor(factor):
+            factor = [factor]
+        if (old_logp is None) != (factor is None):
+            raise ValueError("GroupedPolicyInference.evaluate_actions: old_logp and factor come together")
+        for name, xs in (("obs", obs), ("actions", actions), ("old_logp", old_logp), ("factor", factor), ("out", out)):
+            if xs is not None and len(xs) != k:
+                raise ValueError("GroupedPolicyInference.evaluate_actions: %s needs one tensor per selected agent" % name)
+        self._ensure_fresh()
+        if self._chunks is not None:
+            res = [None] * k
+            for c, (lo, hi) in zip(self._chunks, self._ranges):
+                sel = [i for i, a in enumerate(agents) if lo <= a < hi]
+                if not sel:
+                    continue
+                pick = lambda xs: None if xs is None else [xs[i] for i in sel]
+                got = c.evaluate_actions(pick(obs), pick(actions), agents=[agents[i] - lo for i in sel], old_logp=pick(old_logp), factor=pick(factor), out=pick(out))
+                for i, t in zip(sel, got):
+                    res[i] = t
+                self.eval_route = c.eval_route
+            return res
+        M, H, A, n = obs[0].shape[0], self.hidden, self.act_dim, self.n
+        f32 = lambda t: t.detach() if t.dtype == torch.float32 else t.detach().float()
+        obs_f, act_f = [f32(t) for t in obs], [f32(t) for t in actions]                # (held until the launches below have been issued)
+        if any(tuple(t.shape) != (M, self.obs_dim) for t in obs_f) or any(tuple(t.shape) != (M, A) for t in act_f):
+            raise ValueError("GroupedPolicyInference.evaluate_actions: obs [M, %d] and actions [M, %d] per agent" % (self.obs_dim, A))
+        planes = self._split_applies(M, self.sobs_dim) and self.split_format == "f16x2"
+        self.eval_route = "f16x2" if planes else "fp32"
+        E = self._eval_buffers(M, planes)
+        logp = E["logp"] if out is None else None
+        dst = [logp[a] for a in agents] if out is None else list(out)
+        if any(tuple(t.shape) != (M, A) for t in dst):
+            raise ValueError("GroupedPolicyInference.evaluate_actions: out must be [M, %d] per agent" % A)
+        if M == 0:
+            return dst
+        obs_p, obs_pitch = _row_ptrs(obs_f)
+        act_p, act_pitch = _row_ptrs(act_f)
+        dst_p, dst_pitch = _row_ptrs(dst)
+        old_p = old_pitch = fac_p = None
+        if factor is not None:
+            old_f = [f32(t) for t in old_logp]
+            if any(tuple(t.shape) != (M, A) for t in old_f):
+                raise ValueError("GroupedPolicyInference.evaluate_actions: old_logp must be [M, %d] per agent" % A)
+            old_p, old_pitch = _row_ptrs(old_f)
+            if any(t.dtype != torch.float32 or t.numel() != M or not t.is_contiguous() for t in factor):
+                raise ValueError("GroupedPolicyInference.evaluate_actions: factor must be contiguous float32 [M, 1] per agent")
+            fac_p = (ctypes.c_void_p * k)(*[t.data_ptr() for t in factor])
+        if max(obs_pitch, act_pitch, dst_pitch, old_pitch or 0) >= 2 ** 31:
+            raise ValueError("GroupedPolicyInference.evaluate_actions: row pitches must fit 31 bits")
+        L, idx, stream = _lib.for_device(self.device)
+        p = self.p
+        chk = lambda rc, what: _lib.check(rc, None, what, L)
+        sub = lambda arr: (ctypes.c_void_p * k)(*[arr[a] for a in agents])             # (every parameter array lists the actors first)
+        own = lambda ts: (ctypes.c_void_p * k)(*[ts[a].data_ptr() for a in agents])
+        rep = lambda t: (ctypes.c_void_p * k)(*([t.data_ptr()] * k))
+        i32 = lambda v: (ctypes.c_int32 * k)(*([int(v)] * k))
+        x, h = own(E["x"]), [own(E["h"][0]), own(E["h"][1])]
+        cur = 0
+        if planes:
+            one, zero, sx, sh, xs, xi = rep(E["one"]), rep(E["zero"]), own(E["sx"]), own(E["sh"]), own(E["xs"]), own(E["xi"])
+
+            def layer(K, xp, w, b, y, winv):
+                chk(L.mms_linear_group_act_split16(idx, k, M, H, K, xp, w, b, y, xi, winv, None, 1, 0, None, None, None, None, None, None, stream),
+                    "mms_linear_group_act_split16")
+            chk(L.mms_layernorm_group(idx, k, M, self.obs_dim, self.kp_a, obs_pitch, obs_p, one, zero, x, self.eps, stream), "mms_layernorm_group")
+            chk(L.mms_split_planes16_group(idx, k, M, self.obs_dim, self.kp_a, x, sx, xs, xi, 0, 0, None, None, None, None, self.eps, stream), "mms_split_planes16_group")
+            layer(self.obs_dim, sx, sub(p["sw_a1"]), sub(p["fc1_a"]), h[0], sub(p["swi_a1"]))
+            for l in range(1, self.depth):
+                chk(L.mms_layernorm_group(idx, k, M, H, H, H, h[cur], one, zero, h[cur], self.eps, stream), "mms_layernorm_group")
+                chk(L.mms_split_planes16_group(idx, k, M, H, H, h[cur], sh, xs, xi, 0, 0, None, None, None, None, self.eps, stream), "mms_split_planes16_group")
+                layer(H, sh, sub(p["sw%d" % l]), sub(p["fc%d" % l]), h[1 - cur], sub(p["swi%d" % l]))
+                cur = 1 - cur
+        else:
+            chk(L.mms_layernorm_group(idx, k, M, self.obs_dim, self.kp_a, obs_pitch, obs_p, sub(p["fn_a_g"]), sub(p["fn_a_b"]), x, self.eps, stream), "mms_layernorm_group")
+            chk(L.mms_linear_group_act(idx, k, M, H, self.kp_a, x, sub(p["w1_a"]), sub(p["b1_a"]), h[0], 1, None, None, None, stream), "mms_linear_group_act")
+            for l in range(1, self.depth):
+                chk(L.mms_layernorm_group(idx, k, M, H, H, H, h[cur], sub(p["ln%d_g" % (l - 1)]), sub(p["ln%d_b" % (l - 1)]), h[cur], self.eps, stream), "mms_layernorm_group")
+                chk(L.mms_linear_group_act(idx, k, M, H, H, h[cur], sub(p["w%d" % l]), sub(p["b%d" % l]), h[1 - cur], 1, None, None, None, stream), "mms_linear_group_act")
+                cur = 1 - cur
+        last = self.depth - 1
+        chk(L.mms_marl_heads_eval(idx, k, M, H, h[cur], sub(p["ln%d_g" % last]), sub(p["ln%d_b" % last]), sub(p["hw"]), sub(p["hb"]), i32(A), sub(p["std"]),
+                                  act_p, i32(act_pitch), dst_p, i32(dst_pitch), old_p, None if old_p is None else i32(old_pitch), fac_p, fac_p, self.eps, stream),
+            "mms_marl_heads_eval")
+        return dst
+
+    eval_route = None
 
     # -- the Runner's collect step --------------------------------------------------------------------------------------------------
     @classmethod

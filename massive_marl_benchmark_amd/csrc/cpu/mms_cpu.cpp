@@ -28,6 +28,7 @@
 #include "../gru_lane.h"
 #include "../gru_grad_lane.h"
 #include "../elu_ln_lane.h"
+#include "../marl_eval_lane.h"
 #include "lane_step.h"
 
 #define MMS_API extern "C" __attribute__((visibility("default")))
@@ -1220,6 +1221,50 @@ MMS_API int mms_marl_heads_act(int device, int32_t groups, int64_t M, int32_t H,
                 out[g][m * op + j] = p;
             }
             if (sd && cnt) cnt[m] = c + 1;
+        }
+    }
+    return 0;
+}
+
+// include/mms.h: mms_marl_heads_eval -- marl_eval_lane.h's statements, a row's sums over ascending columns in double
+MMS_API int mms_marl_heads_eval(int device, int32_t groups, int64_t M, int32_t H, const float* const* h, const float* const* gamma,
+                                const float* const* beta, const float* const* w, const float* const* b, const int32_t* A, const float* const* std,
+                                const float* const* act, const int32_t* act_pitch, float* const* logp, const int32_t* logp_pitch,
+                                const float* const* old_logp, const int32_t* old_pitch, const float* const* factor_in, float* const* factor_out,
+                                float eps, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_marl_heads_eval(groups, M, H, h, gamma, beta, w, b, A, std, act, act_pitch, logp, logp_pitch, old_logp, old_pitch, factor_in,
+                                      factor_out, eps)))
+        return 1;
+    for (int g = 0; g < groups; g++) {
+        const int64_t ap = act_pitch ? act_pitch[g] : A[g], lpp = logp_pitch ? logp_pitch[g] : A[g], opp = old_pitch ? old_pitch[g] : A[g];
+        float* lp = logp ? logp[g] : nullptr;
+        float* fo = factor_out ? factor_out[g] : nullptr;
+        const float* fi = (fo && factor_in) ? factor_in[g] : nullptr;
+        const float* old = fo ? old_logp[g] : nullptr;
+#pragma omp parallel for schedule(static)
+        for (int64_t m = 0; m < M; m++) {
+            double xn[mms::kEvalMaxH];
+            const float* hr = h[g] + m * H;
+            if (eps >= 0.f) {
+                double s = 0.0, q = 0.0;
+                for (int k = 0; k < H; k++) s += (double)hr[k];
+                const double mean = mms::eval_mean(s, H);
+                for (int k = 0; k < H; k++) q += mms::eval_dev2(hr[k], mean);
+                const double rstd = mms::eval_rstd(q, H, eps);
+                for (int k = 0; k < H; k++) xn[k] = mms::eval_norm(hr[k], mean, rstd, gamma[g][k], beta[g][k]);
+            } else {
+                for (int k = 0; k < H; k++) xn[k] = hr[k];
+            }
+            double sum = 0.0;
+            for (int j = 0; j < A[g]; j++) {
+                double dot = 0.0;
+                for (int k = 0; k < H; k++) dot += mms::eval_term(xn[k], w[g][(int64_t)j * H + k]);
+                const float v = mms::eval_logp(act[g][m * ap + j], mms::eval_mu(dot, b[g][j]), std[g][j]);
+                if (fo) sum += mms::eval_diff(v, old[m * opp + j]);
+                if (lp) lp[m * lpp + j] = v;
+            }
+            if (fo) fo[m] = mms::eval_factor(fi ? fi[m] : 1.f, sum);
         }
     }
     return 0;

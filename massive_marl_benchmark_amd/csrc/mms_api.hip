@@ -15,6 +15,7 @@
 #include "gru_gates_args.h"
 #include "gru_grad_args.h"
 #include "elu_ln_args.h"
+#include "marl_eval_args.h"
 
 namespace mms {
 hipError_t launch_step(const StepArgs& a, int task, hipStream_t stream);
@@ -711,6 +712,33 @@ __attribute__((visibility("default"))) int mms_marl_heads_act(int device, int32_
     }
     a.seed = seed; a.M = M; a.row_offset = row_offset; a.H = H; a.eps = eps;
     MMS_FREE(mms::launch_marl_heads(a, groups, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_marl_heads_eval(int device, int32_t groups, int64_t M, int32_t H, const float* const* h,
+                                                               const float* const* gamma, const float* const* beta, const float* const* w,
+                                                               const float* const* b, const int32_t* A, const float* const* std,
+                                                               const float* const* act, const int32_t* act_pitch, float* const* logp,
+                                                               const int32_t* logp_pitch, const float* const* old_logp, const int32_t* old_pitch,
+                                                               const float* const* factor_in, float* const* factor_out, float eps, void* s) {
+    MMS_DEV(device)
+    if (refused(check_marl_heads_eval(groups, M, H, h, gamma, beta, w, b, A, std, act, act_pitch, logp, logp_pitch, old_logp, old_pitch, factor_in,
+                                      factor_out, eps)))
+        return 1;
+    mms::HeadsEvalArgs a = {};
+    for (int g = 0; g < groups; g++) {
+        a.h[g] = h[g]; a.gamma[g] = eps >= 0.f ? gamma[g] : nullptr; a.beta[g] = eps >= 0.f ? beta[g] : nullptr; a.w[g] = w[g]; a.b[g] = b[g];
+        a.A[g] = A[g]; a.std[g] = std[g]; a.act[g] = act[g];
+        a.logp[g] = logp ? logp[g] : nullptr;
+        a.factor_out[g] = factor_out ? factor_out[g] : nullptr;
+        a.old_logp[g] = (a.factor_out[g] && old_logp) ? old_logp[g] : nullptr;
+        a.factor_in[g] = (a.factor_out[g] && factor_in) ? factor_in[g] : nullptr;
+        a.act_pitch[g] = act_pitch ? act_pitch[g] : A[g];
+        a.logp_pitch[g] = logp_pitch ? logp_pitch[g] : A[g];
+        a.old_pitch[g] = old_pitch ? old_pitch[g] : A[g];
+    }
+    a.M = M; a.H = H; a.eps = eps;
+    MMS_FREE(mms::launch_marl_heads_eval(a, groups, (hipStream_t)s));
     return 0;
 }
 

@@ -684,6 +684,30 @@ static inline std::string check_marl_heads_act(int32_t groups, int64_t M, int32_
     return {};
 }
 
+// mms_marl_heads_eval: mms_marl_heads_act's front, the actions given.  Pitches: NULL = A[g].
+static inline std::string check_marl_heads_eval(int32_t groups, int64_t M, int32_t H, const float* const* h, const float* const* gamma,
+                                                const float* const* beta, const float* const* w, const float* const* b, const int32_t* A,
+                                                const float* const* std, const float* const* act, const int32_t* act_pitch, float* const* logp,
+                                                const int32_t* logp_pitch, const float* const* old_logp, const int32_t* old_pitch,
+                                                const float* const* factor_in, float* const* factor_out, float eps) {
+    std::string bad = check_groups("mms_marl_heads_eval", groups);
+    if (!bad.empty()) return bad;
+    const bool ln = eps >= 0.f;                          // eps < 0: the plain output layer -- gamma / beta are not read (NULL allowed)
+    if (!h || (ln && (!gamma || !beta)) || !w || !b || !A || !std || !act || M < 0 || M > 0x7fffffff || H <= 0 || H > 1024)
+        return "mms_marl_heads_eval: bad arguments (h, w, b, A, std and act are required; 1 <= H <= 1024)";
+    for (int g = 0; g < groups; g++) {
+        if (!h[g] || (ln && (!gamma[g] || !beta[g])) || !w[g] || !b[g] || !std[g] || !act[g] || A[g] < 1 || A[g] > 16)
+            return "mms_marl_heads_eval: null pointer in a group, or action dimensions outside 1..16";
+        if ((act_pitch && act_pitch[g] < A[g]) || (logp_pitch && logp_pitch[g] < A[g]) || (old_pitch && old_pitch[g] < A[g]))
+            return "mms_marl_heads_eval: a row pitch below the number of action dimensions";
+        if (factor_out && factor_out[g] && !(old_logp && old_logp[g])) return "mms_marl_heads_eval: factor_out needs old_logp";
+        if (logp && logp[g] && (logp[g] == act[g] || (old_logp && logp[g] == old_logp[g])))
+            return "mms_marl_heads_eval: logp must not be act or old_logp";
+    }
+    (void)factor_in;
+    return {};
+}
+
 // mms_gru_group.  A workgroup writes its rows of h_out / y while others still read those rows of x and h: no destination may be one of
 // the sources (compared as pointers over all groups: the layers of one [M, recurrent_N, H] slot interleave legitimately).
 static inline std::string check_gru_group(int32_t groups, int64_t M, int32_t K, int32_t H, const float* const* x, int64_t x_pitch, const float* const* h,
