@@ -35,6 +35,12 @@ def p32_bytes(rows, K):
     return rows * ((K + 31) // 32) * 192
 
 
+def ptr_array(tensors):
+    """HOST array of the tensors' device addresses, as the grouped entries take them (None: NULL).  Nothing is checked and no
+    reference is held: the caller keeps the tensors alive for as long as the array is in use."""
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
 def _bind(path):
     L = ctypes.CDLL(path)
     vp, ci, c64, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float

@@ -79,9 +79,7 @@ def check_blocks(bases, who="mlp_base", products="library"):
     return H, n, eps.pop()
 
 
-def _table(tensors):
-    """HOST array of device addresses (None: NULL)"""
-    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+_table = _lib.ptr_array                                        # HOST array of device addresses (None: NULL)
 
 
 class _Planes:

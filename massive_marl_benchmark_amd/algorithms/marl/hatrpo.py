@@ -59,8 +59,7 @@ from .utils.valuenorm import ValueNorm
 DEFAULT_FVP = "fisher"
 
 
-def _ptrs(ts):
-    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+_ptrs = _lib.ptr_array
 
 
 class _ActorMap:

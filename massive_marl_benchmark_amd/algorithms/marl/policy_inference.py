@@ -31,16 +31,15 @@ unconditionally -- the trainers update between rollouts, and the reference's HAT
 version counter or address has moved (an in-place optimizer step moves them).  What it cannot see: a write through `.data` outside a
 collect loop -- call `refresh()` after it (tests/test_marl_policy.py pins all three).  Recurrent policies
 (use_recurrent_policy / use_naive_recurrent_policy: every network carries `.rnn.rnn`, an nn.GRU of the hidden width, and `.rnn.norm`)
-run the exact-fp32 layers (the plane kernels are not used), their GRU parameters are read in place (no derived copies), and
-`get_actions` / `get_values` / `collect` / `collect_into` take and return the states (see there).  `rnn_format="f16x2"` (opt-in)
-moves a recurrent group's products onto the two-plane fp16 layer kernel where the shapes allow (`_rnn16_applies`, `_forward_rnn16`):
-every base block and both GRU products as split + mms_linear_group_act_split16 into fp32, the gates by mms_gru_gates_group;
-`rnn_route` names the route the last call took.  A recurrent flag without such a
-layer, a mix of recurrent and feed-forward networks, and non-Box action spaces are not covered: the constructor raises, nothing falls
-back silently.
+run the exact-fp32 layers, their GRU parameters are read in place (no derived copies), and `get_actions` / `get_values` / `collect` /
+`collect_into` take and return the states (see there); `rnn_format="f16x2"` (opt-in) moves their products onto the two-plane fp16
+layer kernel where the shapes allow, and `rnn_route` names the route the last call took.  A recurrent flag without such a layer, a
+mix of recurrent and feed-forward networks, and non-Box action spaces are not covered: the constructor raises, nothing falls back
+silently.
 
-`evaluate_actions` is the actors-only pass over GIVEN actions that Runner.train asks for before and after every agent's update
-(runner.py:282-313): the same grouped layers, then mms_marl_heads_eval (the log-density and HAPPO's factor product) -- see there.
+Which method states which launches -- the forward bodies `_forward_split`, `_forward_rnn16`, `_forward_fp32` and `evaluate_actions`
+(the actors-only pass over GIVEN actions of Runner.train, runner.py:282-313), the one `_tail` -- and which public call runs which:
+DESIGN.md, "Where each launch sequence lives".
 
 The noise stream is this build's counter-based generator (seed + agent, global env row, per-row draw counter), as in
 rl/ppo/module.py: the sampled actions differ from torch's draw for the same torch seed, their distribution and the returned
@@ -116,6 +115,13 @@ def _row_ptrs(tensors):
     return arr, pitch.pop()
 
 
+def _plane_bufs(G, rows, K, dev, h16=True):
+    """G byte buffers for the operand planes of a [rows, K] matrix each: two scaled fp16 planes, or (h16 = False) three bf16 planes.
+    Their pointer arrays come from _lib.ptr_array (bytes: _ptrs would refuse the dtype)."""
+    nbytes = (_lib.h32_bytes if h16 else _lib.p32_bytes)(rows, K)
+    return [torch.empty(nbytes, dtype=torch.uint8, device=dev) for _ in range(G)]
+
+
 def _critic_halves(table, n):
     """For every pointer array over all 2n networks (actors first, critics behind them) the array of its critic half, as `key/c`."""
     for key, arr in list(table.items()):
@@ -132,10 +138,17 @@ class GroupedPolicyInference:
         if rnn_format not in ("fp32", "f16x2"):
             raise ValueError("rnn_format: fp32 or f16x2")
         self.rnn_format = rnn_format
-        self._route = "fp32"
+        # All state that a method may find absent starts here, in the chunked parent and in a leaf alike (`_ensure_fresh` says which
+        # of it a moved parameter voids): the routes of the last calls; the chunks of more than sixteen agents; the parameter list,
+        # the (address, version) pairs the derived copies were built from, those copies (_D), the pointer arrays over parameters and
+        # copies (p), the batch size the buffers and their pointer arrays (q) stand for, and collect_into's cached operands; the noise
+        # counters per batch size; evaluate_actions' scratch; the tracked conditioning of the last folded pass; and the buffers that
+        # only some shapes allocate (stat with every batch size, ysc / yinv with the two-plane split path's).
+        self._route, self.eval_route = "fp32", None
         self._chunks = None
-        self._plans = None
-        self._plist = None
+        self._plist, self._versions, self._D, self.p, self._M, self._plans = None, (), None, None, None, None
+        self._counters_by_M, self._E, self._cond = {}, None, []
+        self.stat = self.ysc = self.yinv = None
         rec = [_is_recurrent(m) for m in list(actors) + list(critics)]
         if any(rec) and not all(rec):
             raise NotImplementedError("GroupedPolicyInference: recurrent and feed-forward networks in one group are not covered")
@@ -204,7 +217,6 @@ class GroupedPolicyInference:
                 raise NotImplementedError("GroupedPolicyInference: RNNLayer.norm must use the eps of the other LayerNorms")
             self.recurrent_N = layers.pop()
         self.device = self.actors[0].act.action_out.fc_mean.weight.device
-        self._M, self._D, self.p, self._versions, self._plans = None, None, None, (), None
         self.refresh()
 
     # -- parameters ---------------------------------------------------------------------------------------------------------------
@@ -226,10 +238,8 @@ class GroupedPolicyInference:
         both = self.a_blocks + self.c_blocks
         split = self.split_layers and self.fold_layernorm and self.sobs_dim % 4 == 0 and H % 128 == 0 and not self.recurrent_N
         h16 = self.split_format == "f16x2"
-        pbytes = _lib.h32_bytes if h16 else _lib.p32_bytes
-        u8 = lambda G, N, K: [torch.empty(pbytes(N, K), dtype=torch.uint8, device=dev) for _ in range(G)]
         D = {"split": split, "w1_a": z(n, H, self.kp_a), "w1_c": z(n, H, self.kp_c), "std": z(n, A), "fold": {}, "calls": [], "scale_jobs": []}
-        up = lambda ts: (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+        up = _lib.ptr_array                                       # (the tensors are held by D itself or by a call's `keep`)
         i64 = lambda v: (ctypes.c_int64 * len(v))(*v)
         i32 = lambda v: (ctypes.c_int32 * len(v))(*v)
 
@@ -238,7 +248,7 @@ class GroupedPolicyInference:
             G = len(ws)
             Nmax = max(N) if isinstance(N, (list, tuple)) else N
             st = {"G": G, "N": N, "K": K, "wt": z(G, Nmax, K) if want_wt else None, "s": z(G, Nmax), "c": z(G, Nmax), "rb": z(G, Nmax) if want_rb else None,
-                  "planes": u8(G, N, K) if want_planes else None, "inv": z(G, N) if (want_planes and h16) else None,
+                  "planes": _plane_bufs(G, N, K, dev, h16) if want_planes else None, "inv": z(G, N) if (want_planes and h16) else None,
                   "src": (ws, gammas, betas, biases)}
             return st
 
@@ -312,7 +322,7 @@ class GroupedPolicyInference:
         if self._rnn16_built():
             def wset(ws, N, K):
                 G = len(ws)
-                st = {"planes": u8(G, N, K), "scale": z(G, N), "inv": z(G, N)}
+                st = {"planes": _plane_bufs(G, N, K, dev), "scale": z(G, N), "inv": z(G, N)}
                 src = [d(w) for w in ws]
                 D["calls"].append((L.mms_weight_planes16_group, (idx, G, i64([N] * G), i32([K] * G), up(src), up(st["planes"]), up(list(st["scale"].unbind(0))),
                                                                  up(list(st["inv"].unbind(0))), None), "mms_weight_planes16_group", src))
@@ -371,8 +381,8 @@ class GroupedPolicyInference:
             return
         L, idx, stream = _lib.for_device(self.device)
         n = self.n
-        have_rows = self._M is not None and getattr(self, "ysc", None) is not None
-        up = lambda ts: (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+        have_rows = self._M is not None and self.ysc is not None
+        up = _lib.ptr_array
         for l, rbs in D["scale_jobs"]:
             ysc = list(self.ysc[l].unbind(0)) if have_rows else [None] * (2 * n)
             yinv = list(self.yinv[l].unbind(0)) if have_rows else [None] * (2 * n)
@@ -391,7 +401,14 @@ class GroupedPolicyInference:
                 c._ensure_fresh()
         elif self._versions != self._param_versions():
             if tuple(v[0] for v in self._versions) != tuple(v[0] for v in self._param_versions()):
-                self._D, self.p, self._M, self._plans = None, None, None, None      # the parameters moved: every cached address is void
+                # The parameters moved: every cached ADDRESS of a parameter is void.  That is the derived copies with the prebuilt
+                # launches that read the parameters (_D), the pointer arrays over parameters and copies (p), the batch-size buffers'
+                # validity (_M: _buffers allocates afresh and refills the row scales from the new _D) and collect_into's cached
+                # operands (_plans).  What survives holds no parameter address: evaluate_actions' scratch (_E) and the noise
+                # counters (_counters_by_M) -- those MUST survive, or the next draw would replay noise already used
+                # (tests/test_marl_policy.py: parameter_updates_are_followed) -- and the parameter list itself (_plist: the same
+                # nn.Parameter objects, whose addresses are read anew on every check).
+                self._D, self.p, self._M, self._plans = None, None, None, None
             self.refresh()
 
     def _bind(self):
@@ -402,9 +419,8 @@ class GroupedPolicyInference:
         fc = [c.base.feature_norm for c in self.critics]
         self._keep = []                                           # (tensors whose addresses sit in the pointer arrays)
 
-        def arr(ts):
-            ts = [None if t is None else t for t in ts]
-            self._keep.append(ts)
+        def arr(ts):                                              # checked fp32 operands; the byte planes below go through _lib.ptr_array
+            self._keep.append(list(ts))
             return _ptrs(ts)
         ub = lambda t: list(t.unbind(0))
         self._w1_a = ub(D["w1_a"]) if self.kp_a != self.obs_dim else [d(b[0][0].weight) for b in A]
@@ -449,12 +465,13 @@ class GroupedPolicyInference:
         self._sp = None
         if D["split"]:
             h16 = self.split_format == "f16x2"
-            up = lambda ts: (self._keep.append(ts), (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts]))[1]
             self._sp = {"a1": D["a1"], "heads": D["heads"], "scale1": D.get("scale1")}
-            self.p["sw_a1"], self.p["sw_c1"] = up(D["a1"]["planes"]), up(D["c1"]["planes"])
+            self._keep += [D["a1"]["planes"], D["c1"]["planes"]]
+            self.p["sw_a1"], self.p["sw_c1"] = _lib.ptr_array(D["a1"]["planes"]), _lib.ptr_array(D["c1"]["planes"])
             self.p["fs1_a"], self.p["fc1_a"] = arr(ub(D["a1"]["s"])), arr(ub(D["a1"]["c"]))
             for l, st in D["fold"].items():
-                self.p["sw%d" % l] = up(st["planes"])
+                self._keep.append(st["planes"])
+                self.p["sw%d" % l] = _lib.ptr_array(st["planes"])
             if h16:
                 self.p["swi_a1"], self.p["swi_c1"] = arr(ub(D["a1"]["inv"])), arr(ub(D["c1"]["inv"]))
                 for l, st in D["fold"].items():
@@ -463,11 +480,11 @@ class GroupedPolicyInference:
             self.p["hwt"], self.p["hs"], self.p["hc"] = arr(ub(hd["wt"])), arr(ub(hd["s"])), arr(ub(hd["c"]))
         if D["rnn16"] is not None:
             R = D["rnn16"]
-            raw = lambda ts: (self._keep.append(ts), (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts]))[1]
             sets = [("a1", R["a1"]), ("c1", R["c1"])] + [("w%d" % l, st) for l, st in R["w"].items()]
             sets += [("ih%d" % l, st) for l, st in R["ih"].items()] + [("hh%d" % l, st) for l, st in R["hh"].items()]
             for name, st in sets:
-                self.p["r16_" + name], self.p["r16i_" + name] = raw(st["planes"]), arr(ub(st["inv"]))
+                self._keep.append(st["planes"])
+                self.p["r16_" + name], self.p["r16i_" + name] = _lib.ptr_array(st["planes"]), arr(ub(st["inv"]))
             self.p["r16_zero"] = arr([R["zero"]] * (2 * self.n))
         self._A = (ctypes.c_int32 * (2 * self.n))(*([self.act_dim] * self.n + [1] * self.n))
         self._A1 = (ctypes.c_int32 * self.n)(*([1] * self.n))
@@ -484,8 +501,6 @@ class GroupedPolicyInference:
         self.actions, self.logp, self.values = z(n, M, self.act_dim), z(n, M, self.act_dim), z(n, M, 1)
         # draw counters of the noise stream (seed + agent, row, counter): one tensor per batch size, kept across re-allocations of the
         # other buffers, so that alternating batch sizes (training at M, evaluation at M', back to M) never replays noise already used
-        if not hasattr(self, "_counters_by_M"):
-            self._counters_by_M = {}
         if M not in self._counters_by_M:
             self._counters_by_M[M] = torch.zeros(n, M, dtype=torch.int64, device=dev)
         self.counters = self._counters_by_M[M]
@@ -505,14 +520,13 @@ class GroupedPolicyInference:
         }
         if self._sp is not None and M % 128 == 0:
             h16 = self.split_format == "f16x2"
-            u8 = lambda g, rows, K: [torch.empty((_lib.h32_bytes if h16 else _lib.p32_bytes)(rows, K), dtype=torch.uint8, device=dev) for _ in range(g)]
-            self.sx_a, self.sx_c = u8(n, M, self.obs_dim), u8(n, M, self.sobs_dim)
-            self.sh = [u8(2 * n, M, H), u8(2 * n, M, H)]
+            self.sx_a, self.sx_c = _plane_bufs(n, M, self.obs_dim, dev, h16), _plane_bufs(n, M, self.sobs_dim, dev, h16)
+            self.sh = [_plane_bufs(2 * n, M, H, dev, h16), _plane_bufs(2 * n, M, H, dev, h16)]
             self.stat_a = z(n, M, 2)
             # per-slot partial dot products of the output heads, rows of A rounded up to 4 floats: an actor's and a critic's differ
             self.head_part_a = z(n, max(1, H // 64), M, (self.act_dim + 3) & ~3)
             self.head_part_c = z(n, max(1, H // 64), M, 4)
-            up = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+            up = _lib.ptr_array                                   # (byte planes; every tensor is an attribute of self)
             self.q.update({"sx_a": up(self.sx_a), "sx_c": up(self.sx_c), "sx_c0": up([self.sx_c[0]] * n), "sh0": up(self.sh[0]), "sh1": up(self.sh[1]),
                            "sh0_a": up(self.sh[0][:n]), "sh0_c": up(self.sh[0][n:]), "stat_a": _ptrs(ub(self.stat_a)),
                            "hpart": _ptrs(ub(self.head_part_a) + ub(self.head_part_c)), "hpart_a": _ptrs(ub(self.head_part_a)), "hpart_c": _ptrs(ub(self.head_part_c))})
@@ -530,13 +544,12 @@ class GroupedPolicyInference:
         if self._D["rnn16"] is not None and M % 128 == 0:
             # the plane route's scratch: planes and row scales of the first layers' inputs, of a block's / GRU layer's x (0) and of the
             # state (1), and the two [M, 3H] pre-activation blocks per network
-            u8 = lambda g, K: [torch.empty(_lib.h32_bytes(M, K), dtype=torch.uint8, device=dev) for _ in range(g)]
-            up = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-            self.r16 = {"sx_a": u8(n, self.obs_dim), "sx_c": u8(n, self.sobs_dim), "sh0": u8(2 * n, H), "sh1": u8(2 * n, H),
+            self.r16 = {"sx_a": _plane_bufs(n, M, self.obs_dim, dev), "sx_c": _plane_bufs(n, M, self.sobs_dim, dev),
+                        "sh0": _plane_bufs(2 * n, M, H, dev), "sh1": _plane_bufs(2 * n, M, H, dev),
                         "xs_a": z(n, M), "xi_a": z(n, M), "xs_c": z(n, M), "xi_c": z(n, M), "hs0": z(2 * n, M), "hi0": z(2 * n, M), "hs1": z(2 * n, M),
                         "hi1": z(2 * n, M), "gi": z(2 * n, M, 3 * H), "gh": z(2 * n, M, 3 * H)}
             for key, t in self.r16.items():
-                self.q["r16_" + key] = up(t) if isinstance(t, list) else _ptrs(ub(t))
+                self.q["r16_" + key] = _lib.ptr_array(t) if isinstance(t, list) else _ptrs(ub(t))
         _critic_halves(self.q, n)
         self._M = M
         self._fill_scales()
@@ -633,6 +646,18 @@ class GroupedPolicyInference:
             raise ValueError("GroupedPolicyInference: recurrent policies need %s, one per agent" % what)
         return list(states)
 
+    def _check_states(self, M, tensors):
+        for t in tensors:
+            if t.dim() != 3 or tuple(t.shape) != (M, self.recurrent_N, self.hidden):
+                raise ValueError("GroupedPolicyInference: rnn states must be [M, recurrent_N, hidden] per agent")
+
+    def _new_states(self, rnn_out):
+        """(actors', critics') destinations of a recurrent pass's new states: the caller's `rnn_out`, or (None; get_values, which
+        drops the states, always) the two halves of `rnn_new`, which the next call overwrites"""
+        if rnn_out is not None:
+            return list(rnn_out[0]), list(rnn_out[1])
+        return list(self.rnn_new[:self.n].unbind(0)), list(self.rnn_new[self.n:].unbind(0))
+
     def _gru_stage(self, L, idx, stream, M, cur, sfx, states, masks, dsts):
         """RNNLayer's single-step branch (utils/rnn.py:25-29) behind the last block of the G networks whose pre-LayerNorm activations
         are in q["h<cur><sfx>"]: that block's LayerNorm in place, then one mms_gru_group per GRU layer -- layer l reads its state from
@@ -641,9 +666,7 @@ class GroupedPolicyInference:
         H, p, q, last = self.hidden, self.p, self.q, self.depth - 1
         G = len(states)
         chk = lambda rc, what: _lib.check(rc, None, what, L)
-        for t in list(states) + list(dsts):
-            if t.dim() != 3 or tuple(t.shape) != (M, self.recurrent_N, H):
-                raise ValueError("GroupedPolicyInference: rnn states must be [M, recurrent_N, hidden] per agent")
+        self._check_states(M, list(states) + list(dsts))
         mask_p, mask_pitch = _mask_ptrs(masks, M)
         x = q["h%d%s" % (cur, sfx)]
         chk(L.mms_layernorm_group(idx, G, M, H, H, H, x, p["ln%d_g%s" % (last, sfx)], p["ln%d_b%s" % (last, sfx)], x, self.eps, stream), "mms_layernorm_group")
@@ -673,9 +696,7 @@ class GroupedPolicyInference:
         chk = lambda rc, what: _lib.check(rc, None, what, L)
         sfx = "" if with_actors else "/c"
         G = len(states)
-        for t in list(states) + list(dsts):
-            if t.dim() != 3 or tuple(t.shape) != (M, self.recurrent_N, H):
-                raise ValueError("GroupedPolicyInference: rnn states must be [M, recurrent_N, hidden] per agent")
+        self._check_states(M, list(states) + list(dsts))
         mask_p, mask_pitch = _mask_ptrs(masks, M)
 
         def split(groups, K, pitch, src, dst, xs, xi):
@@ -718,6 +739,64 @@ class GroupedPolicyInference:
             cur = 1 - cur
         return cur
 
+    # -- the exact-fp32 layers, and the tail behind them and behind _forward_rnn16 ----------------------------------------------------
+    def _forward_fp32(self, L, idx, stream, M, obs_p, obs_pitch, sobs_p, sobs_pitch, with_actors):
+        """The base blocks on mms_linear_group_act, for every shape (what the plane routes do not take): the feature LayerNorms into
+        x_a / x_c (the critics' not when their first layer folds it: row moments of the raw rows instead), fc1 of the actors (K = obs,
+        padded) and of the critics (K = share_obs), then per hidden layer either the folded form (mms_row_stats_group, and a layer that
+        evaluates rstd (W~ h - mean s) + c and leaves the next LayerNorm's row sums) or the previous LayerNorm in place and a plain
+        layer.  The LAST block's LayerNorm is left to `_tail`.  with_actors = False: the critics alone, the same launches over the critic
+        half of every array.  Returns the index of the activation buffer with the last block's pre-LayerNorm output."""
+        n, H, p, q, depth = self.n, self.hidden, self.p, self.q, self.depth
+        chk = lambda rc, what: _lib.check(rc, None, what, L)
+        sfx = "" if with_actors else "/c"
+        G = 2 * n if with_actors else n
+        # The folds need 128-tiles and W~ in fp32.  The kp_a term belongs to the ACTORS' first layer, which must leave LayerNorm 0's row
+        # sums (ln_part_out: not below K = 8): a pass without that layer is not bound by it, so get_values folds where get_actions over
+        # the same networks does not.
+        fold = self.fold_layernorm and depth > 1 and M % 128 == 0 and H % 128 == 0 and self._has_wt and (self.kp_a >= 8 or not with_actors)
+        fold_c1 = fold and self._fold_c1 is not None and sobs_pitch == self.sobs_dim and self.sobs_dim >= 8
+        # recurrent policies: blocked summation where the generic layer kernel runs (mms.h: act + 16) -- the state carries a layer's error on
+        act = 17 if self.recurrent_N and not fold else 1
+        if with_actors:
+            chk(L.mms_layernorm_group(idx, n, M, self.obs_dim, self.kp_a, obs_pitch, obs_p, p["fn_a_g"], p["fn_a_b"], q["x_a"], self.eps, stream), "mms_layernorm_group")
+        if not fold_c1:
+            chk(L.mms_layernorm_group(idx, n, M, self.sobs_dim, self.kp_c, sobs_pitch, sobs_p, p["fn_c_g"], p["fn_c_b"], q["x_c"], self.eps, stream), "mms_layernorm_group")
+        if with_actors:
+            chk(L.mms_linear_group_act(idx, n, M, H, self.kp_a, q["x_a"], p["w1_a"], p["b1_a"], q["h0_a"], act, None, None, q["part_a"] if fold else None, stream), "mms_linear_group_act")
+        if fold_c1:
+            shared_rows = len({int(v) for v in sobs_p}) == 1                 # one centralised observation for all critics: one pass
+            chk(L.mms_row_moments_group(idx, 1 if shared_rows else n, M, self.sobs_dim, sobs_pitch, sobs_p, q["stat_c"], self.eps, stream), "mms_row_moments_group")
+            chk(L.mms_linear_group_act(idx, n, M, H, self.sobs_dim, sobs_p, p["fw1_c"], p["fc1_c"], q["h0_c"], 1, p["fs1_c"],
+                                       q["stat_c0"] if shared_rows else q["stat_c"], q["part_c"], stream), "mms_linear_group_act")
+        else:
+            chk(L.mms_linear_group_act(idx, n, M, H, self.kp_c, q["x_c"], p["w1_c"], p["b1_c"], q["h0_c"], act, None, None, q["part_c"] if fold else None, stream), "mms_linear_group_act")
+        cur = 0
+        for l in range(1, depth):
+            x, y = q["h%d%s" % (cur, sfx)], q["h%d%s" % (1 - cur, sfx)]
+            if fold:                                                # LayerNorm l - 1 folded in; leaves the statistics of LayerNorm l
+                chk(L.mms_row_stats_group(idx, G, M, H // 64, H, q["part" + sfx], q["stat" + sfx], self.eps, stream), "mms_row_stats_group")
+                chk(L.mms_linear_group_act(idx, G, M, H, H, x, p["fw%d%s" % (l, sfx)], p["fc%d%s" % (l, sfx)], y, 1, p["fs%d%s" % (l, sfx)], q["stat" + sfx],
+                                           q["part" + sfx] if l + 1 < depth else None, stream), "mms_linear_group_act")
+            else:
+                chk(L.mms_layernorm_group(idx, G, M, H, H, H, x, p["ln%d_g%s" % (l - 1, sfx)], p["ln%d_b%s" % (l - 1, sfx)], x, self.eps, stream), "mms_layernorm_group")
+                chk(L.mms_linear_group_act(idx, G, M, H, H, x, p["w%d%s" % (l, sfx)], p["b%d%s" % (l, sfx)], y, act, None, None, None, stream), "mms_linear_group_act")
+            cur = 1 - cur
+        return cur
+
+    def _tail(self, L, idx, stream, M, cur, with_actors, gru, std_p, out_p, logp_p, pitch_p, cnt_p):
+        """Behind the base blocks of _forward_fp32 and _forward_rnn16: the GRU stage when `gru` = (states, masks, destinations) is given
+        (the fp32 route of a recurrent group; _forward_rnn16 has run its own: None), then the one mms_marl_heads_act over activation
+        buffer `cur` -- the last LayerNorm, fc_mean / v_out, the sample and its log-probabilities.  The LayerNorm slot is chosen here:
+        RNNLayer.norm (utils/rnn.py:79) for recurrent groups, whose last block's LayerNorm the GRU stage has applied, else that block's."""
+        p, sfx = self.p, "" if with_actors else "/c"
+        if gru is not None:
+            cur = self._gru_stage(L, idx, stream, M, cur, sfx, *gru)
+        ln = "rn" if self.recurrent_N else "ln%d" % (self.depth - 1)
+        _lib.check(L.mms_marl_heads_act(idx, 2 * self.n if with_actors else self.n, M, self.hidden, self.q["h%d%s" % (cur, sfx)], p[ln + "_g" + sfx], p[ln + "_b" + sfx],
+                                        p["hw" + sfx], p["hb" + sfx], self._A if with_actors else self._A1, std_p, out_p, logp_p, pitch_p, cnt_p, self.seed,
+                                        self.row_offset, self.eps, stream), None, "mms_marl_heads_act", L)
+
     # -- inference ----------------------------------------------------------------------------------------------------------------
     def get_actions(self, share_obs, obs, deterministic=False, out=None, rnn_states=None, rnn_states_critic=None, masks=None, rnn_out=None):
         """share_obs, obs: per-agent lists of [M, share_obs_dim] / [M, obs_dim] float32 tensors (what the Runner hands agent i:
@@ -759,78 +838,36 @@ class GroupedPolicyInference:
         M = obs[0].shape[0]
         self._buffers(M)
         L, idx, stream = _lib.for_device(self.device)
-        p, q = self.p, self.q
-        chk = lambda rc, what: _lib.check(rc, None, what, L)
         f32 = lambda t: t.detach() if t.dtype == torch.float32 else t.detach().float()
         obs_f, sobs_f = [f32(t) for t in obs], [f32(t) for t in share_obs]     # (held until the launches below have been issued)
         obs_p, obs_pitch = _row_ptrs(obs_f)
         sobs_p, sobs_pitch = _row_ptrs(sobs_f)
+        values, actions, logp, out_p, logp_p, pitch = self._out_ptrs(out)
+        tail = (self.p["std_none"] if deterministic else self.p["std"], out_p, logp_p, pitch, self.q["cnt"])
+        if deterministic:
+            logp = None
         if self._split_applies(M, sobs_pitch):
-            values, actions, logp, out_p, logp_p, pitch = self._out_ptrs(out)
-            self._forward_split(L, idx, stream, M, obs_p, obs_pitch, sobs_p, True, p["std_none"] if deterministic else p["std"], out_p, logp_p, pitch, q["cnt"])
-            return values, actions, (None if deterministic else logp)
-        H = self.hidden
+            self._forward_split(L, idx, stream, M, obs_p, obs_pitch, sobs_p, True, *tail)
+            return values, actions, logp
         rnn16 = bool(self.recurrent_N) and self._rnn16_applies(M, sobs_pitch)
         self._route = "f16x2" if rnn16 else "fp32"
+        new, gru = (), None
+        if self.recurrent_N:
+            new = self._new_states(rnn_out)
+            gru = (rs_a + rs_c, mk + mk, new[0] + new[1])
         if rnn16:
-            values, actions, logp, out_p, logp_p, pitch = self._out_ptrs(out)
-            new_a = list(self.rnn_new[:n].unbind(0)) if rnn_out is None else list(rnn_out[0])
-            new_c = list(self.rnn_new[n:].unbind(0)) if rnn_out is None else list(rnn_out[1])
-            cur = self._forward_rnn16(L, idx, stream, M, obs_p, obs_pitch, sobs_p, True, rs_a + rs_c, mk + mk, new_a + new_c)
-            chk(L.mms_marl_heads_act(idx, 2 * n, M, H, q["h%d" % cur], p["rn_g"], p["rn_b"], p["hw"], p["hb"], self._A,
-                                     p["std_none"] if deterministic else p["std"], out_p, logp_p, pitch, q["cnt"], self.seed, self.row_offset, self.eps, stream),
-                "mms_marl_heads_act")
-            return values, actions, (None if deterministic else logp), new_a, new_c
-        chk(L.mms_layernorm_group(idx, n, M, self.obs_dim, self.kp_a, obs_pitch, obs_p, p["fn_a_g"], p["fn_a_b"], q["x_a"], self.eps, stream), "mms_layernorm_group")
-        fold = self.fold_layernorm and self.depth > 1 and M % 128 == 0 and H % 128 == 0 and self.kp_a >= 8 and self._has_wt
-        fold_c1 = fold and self._fold_c1 is not None and sobs_pitch == self.sobs_dim and self.sobs_dim >= 8
-        if not fold_c1:
-            chk(L.mms_layernorm_group(idx, n, M, self.sobs_dim, self.kp_c, sobs_pitch, sobs_p, p["fn_c_g"], p["fn_c_b"], q["x_c"], self.eps, stream), "mms_layernorm_group")
-        slots = H // 64
-        # recurrent policies: blocked summation where the generic layer kernel runs (mms.h: act + 16) -- the state carries a layer's error on
-        act = 17 if self.recurrent_N and not fold else 1
-        chk(L.mms_linear_group_act(idx, n, M, H, self.kp_a, q["x_a"], p["w1_a"], p["b1_a"], q["h0_a"], act, None, None, q["part_a"] if fold else None, stream), "mms_linear_group_act")
-        if fold_c1:
-            shared_rows = len({int(v) for v in sobs_p}) == 1                 # one centralised observation for all critics: one pass
-            chk(L.mms_row_moments_group(idx, 1 if shared_rows else n, M, self.sobs_dim, sobs_pitch, sobs_p, q["stat_c"], self.eps, stream), "mms_row_moments_group")
-            chk(L.mms_linear_group_act(idx, n, M, H, self.sobs_dim, sobs_p, p["fw1_c"], p["fc1_c"], q["h0_c"], 1, p["fs1_c"],
-                                       q["stat_c0"] if shared_rows else q["stat_c"], q["part_c"], stream), "mms_linear_group_act")
+            cur = self._forward_rnn16(L, idx, stream, M, obs_p, obs_pitch, sobs_p, True, *gru)
         else:
-            chk(L.mms_linear_group_act(idx, n, M, H, self.kp_c, q["x_c"], p["w1_c"], p["b1_c"], q["h0_c"], act, None, None, q["part_c"] if fold else None, stream), "mms_linear_group_act")
-        cur = 0
-        for l in range(self.depth):
-            if l > 0 and fold:                                      # LayerNorm l - 1 folded in; leaves the statistics of LayerNorm l
-                chk(L.mms_row_stats_group(idx, 2 * n, M, slots, H, q["part"], q["stat"], self.eps, stream), "mms_row_stats_group")
-                chk(L.mms_linear_group_act(idx, 2 * n, M, H, H, q["h%d" % cur], p["fw%d" % l], p["fc%d" % l], q["h%d" % (1 - cur)], 1, p["fs%d" % l], q["stat"],
-                                           q["part"] if l + 1 < self.depth else None, stream), "mms_linear_group_act")
-                cur = 1 - cur
-                continue
-            if l > 0:
-                chk(L.mms_linear_group_act(idx, 2 * n, M, H, H, q["h%d" % cur], p["w%d" % l], p["b%d" % l], q["h%d" % (1 - cur)], act, None, None, None, stream), "mms_linear_group_act")
-                cur = 1 - cur
-            if l + 1 < self.depth and not fold:                     # (the last LayerNorm runs inside the heads kernel)
-                chk(L.mms_layernorm_group(idx, 2 * n, M, H, H, H, q["h%d" % cur], p["ln%d_g" % l], p["ln%d_b" % l], q["h%d" % cur], self.eps, stream), "mms_layernorm_group")
-        last = self.depth - 1
-        values, actions, logp, out_p, logp_p, pitch = self._out_ptrs(out)
-        ln_g, ln_b = p["ln%d_g" % last], p["ln%d_b" % last]
-        if self.recurrent_N:
-            new_a = list(self.rnn_new[:n].unbind(0)) if rnn_out is None else list(rnn_out[0])
-            new_c = list(self.rnn_new[n:].unbind(0)) if rnn_out is None else list(rnn_out[1])
-            cur = self._gru_stage(L, idx, stream, M, cur, "", rs_a + rs_c, mk + mk, new_a + new_c)
-            ln_g, ln_b = p["rn_g"], p["rn_b"]                        # RNNLayer.norm (utils/rnn.py:79) in the heads' LayerNorm slot
-        chk(L.mms_marl_heads_act(idx, 2 * n, M, H, q["h%d" % cur], ln_g, ln_b, p["hw"], p["hb"], self._A,
-                                 p["std_none"] if deterministic else p["std"], out_p, logp_p, pitch, q["cnt"], self.seed, self.row_offset, self.eps, stream),
-            "mms_marl_heads_act")
-        if self.recurrent_N:
-            return values, actions, (None if deterministic else logp), new_a, new_c
-        return values, actions, (None if deterministic else logp)
+            cur = self._forward_fp32(L, idx, stream, M, obs_p, obs_pitch, sobs_p, sobs_pitch, True)
+        self._tail(L, idx, stream, M, cur, True, None if rnn16 else gru, *tail)
+        return (values, actions, logp) + new
 
     # -- the log-density of stored actions (Runner.train's factor passes) -----------------------------------------------------------
     def _eval_buffers(self, M, planes):
         """Scratch of evaluate_actions for M rows, its own (the collect step's buffers of another M stay where the cached launches of
         `_get_actions_planned` point): normalised observations, the actors' two activation buffers, the log-probabilities; for the plane
         route the operands' planes and row scales, and the unit affine of a LayerNorm that leaves xhat."""
-        E = getattr(self, "_E", None)
+        E = self._E
         if E is not None and E["M"] == M and (E["planes"] or not planes):
             return E
         dev, n, H = self.device, self.n, self.hidden
@@ -838,9 +875,8 @@ class GroupedPolicyInference:
         ub = lambda t: list(t.unbind(0))
         E = {"M": M, "planes": bool(planes), "x": ub(z(n, M, self.kp_a)), "h": [ub(z(n, M, H)), ub(z(n, M, H))], "logp": ub(z(n, M, self.act_dim))}
         if planes:
-            u8 = lambda K: [torch.empty(_lib.h32_bytes(M, K), dtype=torch.uint8, device=dev) for _ in range(n)]
             W = max(self.kp_a, H)
-            E.update(sx=u8(self.obs_dim), sh=u8(H), xs=ub(z(n, M)), xi=ub(z(n, M)), one=torch.ones(W, device=dev), zero=torch.zeros(W, device=dev))
+            E.update(sx=_plane_bufs(n, M, self.obs_dim, dev), sh=_plane_bufs(n, M, H, dev), xs=ub(z(n, M)), xi=ub(z(n, M)), one=torch.ones(W, device=dev), zero=torch.zeros(W, device=dev))
         self._E = E
         return E
 
@@ -913,7 +949,7 @@ class GroupedPolicyInference:
             old_p, old_pitch = _row_ptrs(old_f)
             if any(t.dtype != torch.float32 or t.numel() != M or not t.is_contiguous() for t in factor):
                 raise ValueError("GroupedPolicyInference.evaluate_actions: factor must be contiguous float32 [M, 1] per agent")
-            fac_p = (ctypes.c_void_p * k)(*[t.data_ptr() for t in factor])
+            fac_p = _lib.ptr_array(factor)
         if max(obs_pitch, act_pitch, dst_pitch, old_pitch or 0) >= 2 ** 31:
             raise ValueError("GroupedPolicyInference.evaluate_actions: row pitches must fit 31 bits")
         L, idx, stream = _lib.for_device(self.device)
@@ -941,18 +977,18 @@ class GroupedPolicyInference:
                 cur = 1 - cur
         else:
             chk(L.mms_layernorm_group(idx, k, M, self.obs_dim, self.kp_a, obs_pitch, obs_p, sub(p["fn_a_g"]), sub(p["fn_a_b"]), x, self.eps, stream), "mms_layernorm_group")
-            chk(L.mms_linear_group_act(idx, k, M, H, self.kp_a, x, sub(p["w1_a"]), sub(p["b1_a"]), h[0], 1, None, None, None, stream), "mms_linear_group_act")
-            for l in range(1, self.depth):
-                chk(L.mms_layernorm_group(idx, k, M, H, H, H, h[cur], sub(p["ln%d_g" % (l - 1)]), sub(p["ln%d_b" % (l - 1)]), h[cur], self.eps, stream), "mms_layernorm_group")
-                chk(L.mms_linear_group_act(idx, k, M, H, H, h[cur], sub(p["w%d" % l]), sub(p["b%d" % l]), h[1 - cur], 1, None, None, None, stream), "mms_linear_group_act")
-                cur = 1 - cur
+            K, src, nxt, w, b = self.kp_a, x, 0, "w1_a", "b1_a"                         # fc1; then block l behind LayerNorm l - 1 in place
+            for l in range(self.depth):
+                if l > 0:
+                    K, src, nxt, w, b = H, h[cur], 1 - cur, "w%d" % l, "b%d" % l
+                    chk(L.mms_layernorm_group(idx, k, M, H, H, H, src, sub(p["ln%d_g" % (l - 1)]), sub(p["ln%d_b" % (l - 1)]), src, self.eps, stream), "mms_layernorm_group")
+                chk(L.mms_linear_group_act(idx, k, M, H, K, src, sub(p[w]), sub(p[b]), h[nxt], 1, None, None, None, stream), "mms_linear_group_act")
+                cur = nxt
         last = self.depth - 1
         chk(L.mms_marl_heads_eval(idx, k, M, H, h[cur], sub(p["ln%d_g" % last]), sub(p["ln%d_b" % last]), sub(p["hw"]), sub(p["hb"]), i32(A), sub(p["std"]),
                                   act_p, i32(act_pitch), dst_p, i32(dst_pitch), old_p, None if old_p is None else i32(old_pitch), fac_p, fac_p, self.eps, stream),
             "mms_marl_heads_eval")
         return dst
-
-    eval_route = None
 
     # -- the Runner's collect step --------------------------------------------------------------------------------------------------
     @classmethod
@@ -1073,9 +1109,9 @@ class GroupedPolicyInference:
             vals = [c.fold_conditioning() for c in self._chunks]
             vals = [v for v in vals if v is not None]
             return torch.stack(vals).max() if vals else None
-        if self._M is None or not hasattr(self, "stat"):
+        if self._M is None or self.stat is None:
             return None
-        if getattr(self, "_cond", None):
+        if self._cond:
             return torch.stack(self._cond).max()
         st = self.stat                                                  # [2n, M, 2] = (mean, 1 / sqrt(var + eps)) of the last hidden LayerNorm's input
         return (st[..., 0].abs() * st[..., 1]).max()
@@ -1099,61 +1135,23 @@ class GroupedPolicyInference:
         M = share_obs[0].shape[0]
         self._buffers(M)
         L, idx, stream = _lib.for_device(self.device)
-        p, q = self.p, self.q
-        chk = lambda rc, what: _lib.check(rc, None, what, L)
         f32 = lambda t: t.detach() if t.dtype == torch.float32 else t.detach().float()
-        sobs_f = [f32(t) for t in share_obs]                                  # (held until the launches below have been issued)
+        sobs_f = [f32(t) for t in share_obs]                               # (held until the launches below have been issued)
         sobs_p, sobs_pitch = _row_ptrs(sobs_f)
-        H = self.hidden
-        if self._split_applies(M, sobs_pitch):
-            values = list(self.values.unbind(0)) if out is None else list(out)
-            vp, v_pitch = _row_ptrs(values)
-            self._forward_split(L, idx, stream, M, None, 0, sobs_p, False, None, vp, None, (ctypes.c_int32 * n)(*([v_pitch] * n)), None)
-            return values
-        rnn16 = bool(self.recurrent_N) and self._rnn16_applies(M, sobs_pitch)
-        self._route = "f16x2" if rnn16 else "fp32"
-        if rnn16:
-            values = list(self.values.unbind(0)) if out is None else list(out)
-            vp, v_pitch = _row_ptrs(values)
-            cur = self._forward_rnn16(L, idx, stream, M, None, 0, sobs_p, False, rs_c, mk, list(self.rnn_new[n:].unbind(0)))
-            chk(L.mms_marl_heads_act(idx, n, M, H, q["h%d/c" % cur], p["rn_g/c"], p["rn_b/c"], p["hw/c"], p["hb/c"], self._A1,
-                                     None, vp, None, (ctypes.c_int32 * n)(*([v_pitch] * n)), None, self.seed, self.row_offset, self.eps, stream), "mms_marl_heads_act")
-            return values
-        fold = self.fold_layernorm and self.depth > 1 and M % 128 == 0 and H % 128 == 0 and self._has_wt
-        fold_c1 = fold and self._fold_c1 is not None and sobs_pitch == self.sobs_dim and self.sobs_dim >= 8
-        slots = H // 64
-        act = 17 if self.recurrent_N and not fold else 1                       # (as in get_actions)
-        if fold_c1:
-            shared_rows = len({int(v) for v in sobs_p}) == 1
-            chk(L.mms_row_moments_group(idx, 1 if shared_rows else n, M, self.sobs_dim, sobs_pitch, sobs_p, q["stat_c"], self.eps, stream), "mms_row_moments_group")
-            chk(L.mms_linear_group_act(idx, n, M, H, self.sobs_dim, sobs_p, p["fw1_c"], p["fc1_c"], q["h0_c"], 1, p["fs1_c"],
-                                       q["stat_c0"] if shared_rows else q["stat_c"], q["part_c"], stream), "mms_linear_group_act")
-        else:
-            chk(L.mms_layernorm_group(idx, n, M, self.sobs_dim, self.kp_c, sobs_pitch, sobs_p, p["fn_c_g"], p["fn_c_b"], q["x_c"], self.eps, stream), "mms_layernorm_group")
-            chk(L.mms_linear_group_act(idx, n, M, H, self.kp_c, q["x_c"], p["w1_c"], p["b1_c"], q["h0_c"], act, None, None, q["part_c"] if fold else None, stream), "mms_linear_group_act")
-        cur = 0
-        for l in range(self.depth):
-            if l > 0 and fold:
-                chk(L.mms_row_stats_group(idx, n, M, slots, H, q["part/c"], q["stat/c"], self.eps, stream), "mms_row_stats_group")
-                chk(L.mms_linear_group_act(idx, n, M, H, H, q["h%d/c" % cur], p["fw%d/c" % l], p["fc%d/c" % l], q["h%d/c" % (1 - cur)], 1, p["fs%d/c" % l],
-                                           q["stat/c"], q["part/c"] if l + 1 < self.depth else None, stream), "mms_linear_group_act")
-                cur = 1 - cur
-                continue
-            if l > 0:
-                chk(L.mms_linear_group_act(idx, n, M, H, H, q["h%d/c" % cur], p["w%d/c" % l], p["b%d/c" % l], q["h%d/c" % (1 - cur)], act, None, None, None, stream), "mms_linear_group_act")
-                cur = 1 - cur
-            if l + 1 < self.depth and not fold:
-                chk(L.mms_layernorm_group(idx, n, M, H, H, H, q["h%d/c" % cur], p["ln%d_g/c" % l], p["ln%d_b/c" % l], q["h%d/c" % cur], self.eps, stream), "mms_layernorm_group")
-        last = self.depth - 1
         values = list(self.values.unbind(0)) if out is None else list(out)
         vp, v_pitch = _row_ptrs(values)
         pitch = (ctypes.c_int32 * n)(*([v_pitch] * n))
-        ln_g, ln_b = p["ln%d_g/c" % last], p["ln%d_b/c" % last]
-        if self.recurrent_N:
-            cur = self._gru_stage(L, idx, stream, M, cur, "/c", rs_c, mk, list(self.rnn_new[n:].unbind(0)))
-            ln_g, ln_b = p["rn_g/c"], p["rn_b/c"]
-        chk(L.mms_marl_heads_act(idx, n, M, H, q["h%d/c" % cur], ln_g, ln_b, p["hw/c"], p["hb/c"], self._A1,
-                                 None, vp, None, pitch, None, self.seed, self.row_offset, self.eps, stream), "mms_marl_heads_act")
+        if self._split_applies(M, sobs_pitch):
+            self._forward_split(L, idx, stream, M, None, 0, sobs_p, False, None, vp, None, pitch, None)
+            return values
+        rnn16 = bool(self.recurrent_N) and self._rnn16_applies(M, sobs_pitch)
+        self._route = "f16x2" if rnn16 else "fp32"
+        gru = (rs_c, mk, self._new_states(None)[1]) if self.recurrent_N else None
+        if rnn16:
+            cur = self._forward_rnn16(L, idx, stream, M, None, 0, sobs_p, False, *gru)
+        else:
+            cur = self._forward_fp32(L, idx, stream, M, None, 0, sobs_p, sobs_pitch, False)
+        self._tail(L, idx, stream, M, cur, False, None if rnn16 else gru, None, vp, None, pitch, None)
         return values
 
     @torch.no_grad()

@@ -138,6 +138,23 @@ def check_three_agents(device, hidden, recurrent_N, M):
     parity.record("%s/marl_rnn_three_agents_H%d_R%d_M%d" % (_where(device), hidden, recurrent_N, M), **ratios)
 
 
+def check_get_values_repeats_get_actions(device, M, hidden, rnn_format, recurrent_N=2):
+    """get_values returns the BITS of the values get_actions returned for the same inputs: both run one body over the critics'
+    arrays (policy_inference.py: _forward_fp32 / _forward_rnn16 and the one tail), and a network's result does not depend on how many
+    networks share its launch.  (M 24, hidden 64) takes the unfolded fp32 layers, (M 128, hidden 128) the folded ones or, with
+    rnn_format "f16x2", the plane route."""
+    n = 3
+    actors, critics = make_agents(n, hidden, recurrent_N, device, seed=hidden + 7 * recurrent_N + M)
+    x = make_inputs(n, M, hidden, recurrent_N, device, seed=M + hidden)
+    g = GroupedPolicyInference(actors, critics, seed=3, rnn_format=rnn_format)
+    first = [v.clone() for v in g.get_actions(x["sobs"], x["obs"], rnn_states=x["rs"], rnn_states_critic=x["rsc"], masks=x["masks"])[0]]
+    route = g.rnn_route
+    assert route == (rnn_format if M % 128 == 0 else "fp32")
+    only = g.get_values(x["sobs"], rnn_states_critic=x["rsc"], masks=x["masks"])
+    assert g.rnn_route == route
+    assert all(bool(torch.isfinite(a).all()) and torch.equal(a, b) for a, b in zip(first, only)), (M, hidden, rnn_format)
+
+
 # ---- Runner.collect over SeparatedReplayBuffers ---------------------------------------------------------------------------------------
 def check_collect(device, hidden=64, recurrent_N=2, envs=5, steps=3):
     """Three collect steps with the reference's insert logic (runner.py:229-255) between them, env 2 done after step 1: every step's values

@@ -21,6 +21,11 @@ def test_three_agents_against_float64(hidden, recurrent_N, M):
     rc.check_three_agents("cpu", hidden, recurrent_N, M)
 
 
+@pytest.mark.parametrize("M,hidden,rnn_format", [(24, 64, "fp32"), (128, 128, "fp32"), (128, 128, "f16x2")])
+def test_get_values_repeats_get_actions(M, hidden, rnn_format):
+    rc.check_get_values_repeats_get_actions("cpu", M, hidden, rnn_format)
+
+
 def test_collect_steps_with_a_done_env():
     rc.check_collect("cpu")
 

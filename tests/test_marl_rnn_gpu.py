@@ -27,6 +27,11 @@ def test_three_agents_against_float64(cuda, hidden, recurrent_N, M):
     rc.check_three_agents(cuda, hidden, recurrent_N, M)
 
 
+@pytest.mark.parametrize("M,hidden,rnn_format", [(24, 64, "fp32"), (128, 128, "fp32"), (128, 128, "f16x2")])
+def test_get_values_repeats_get_actions(cuda, M, hidden, rnn_format):
+    rc.check_get_values_repeats_get_actions(cuda, M, hidden, rnn_format)
+
+
 def test_collect_steps_with_a_done_env(cuda):
     rc.check_collect(cuda)
 
