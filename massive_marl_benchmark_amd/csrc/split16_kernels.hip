@@ -384,6 +384,13 @@ __device__ __forceinline__ void static_for(F&& f) {
 // group of four MFMAs), six in all; slot i takes pieces [tail_piece(i), tail_piece(i + 1)): the heavy pieces one per slot, the stores share.
 static_assert(kTailSlices == 2, "tail_piece deals eight pieces to 3 x kTailSlices = 6 slots");
 constexpr int tail_piece(int i) { return i < 4 ? i : 4 + 2 * (i - 4); }
+// Cache policy of the tail's output stores (the aux operand of raw_buffer_store: 0 = plain, 1 = sc0, 2 = nt, 16 = sc1).  A plain store
+// leaves its line dirty in the XCD's L2 until the kernel boundary, which then writes all of them back with every CU idle (33.5 MB
+// behind a 1024-wide planes launch); an sc1 store leaves L2 when it is issued.  Covered = row tiles 0 .. MT - 2, whose stores have the
+// next row tile's MFMAs behind them and no operand DMA beside them; last = row tile MT - 1, stored behind the last MFMA.  Both measured
+// per policy (profiles/split16_store_policy_ab.jsonl): write-through wins for the last row tile too -- its lines drain
+// while the block's other waves still store, instead of at the boundary.
+[[maybe_unused]] constexpr int kTailStoreCovered = 16, kTailStoreLast = 16;
 
 // OUT / LN as linear_split_kernel (split_kernels.hip).  The k-loop runs on THREE operand buffers: at the top of step k every wave
 // waits until at most the DMA of slice k + 1 (its own NDMA instructions, the youngest) is outstanding -- slice k has landed --, the
@@ -680,7 +687,8 @@ __global__ void __launch_bounds__(512, 2) linear_split16_kernel(Split16LinearArg
                     constexpr int j = p - 4;
                     const int idx = lane_e + 64 * j, row = idx >> 4, off = (idx & 15) * 16;
                     const u32x4_16 d = *reinterpret_cast<const u32x4_16*>(scr + row * RS + off);
-                    __builtin_amdgcn_raw_buffer_store_b128(d, yr, yoff, (16 * mt + 4 * j) * ypitch, 0);
+                    constexpr int policy = mt < MT - 1 ? kTailStoreCovered : kTailStoreLast;
+                    __builtin_amdgcn_raw_buffer_store_b128(d, yr, yoff, (16 * mt + 4 * j) * ypitch, policy);
                 }
             };
             // slot i of row tile mt's MFMAs: the pieces of row tile mt - 1 that go there
