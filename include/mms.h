@@ -68,6 +68,8 @@
  *   MAPPO / HAPPO ppo_update's loss head: surrogate, entropy, PopArt /   mms_marl_ppo_loss
  *     Huber value loss, masks and their backward
  *     (algorithms/marl/mappo_trainer.py:63-179, happo_trainer.py:48-170)
+ *   ... for every agent of a MAPPO run at once (the agents' updates      mms_marl_ppo_loss_group
+ *     are independent: base_runner.py / runner.py's train loop)
  *   MADDPG: every agent's deterministic actor head, exploration noise    mms_det_heads_act_group
  *     and the joint action row (algorithms/marl/maddpg/module.py:36-46,
  *     :165-175); every agent's Q target tail (:218-219)                  mms_q_heads_backup_group
@@ -987,6 +989,40 @@ int mms_marl_ppo_loss(int device, int64_t M, int32_t A, const float* mu, const f
                       int32_t use_huber, int32_t clipped_value, int32_t policy_masks, int32_t value_masks, int32_t use_norm,
                       const float* norm_mean, const float* norm_var, float* out, float* dmu, float* dstd, float* dvalue, float* row_logp,
                       void* workspace, int64_t* ws_bytes, void* hip_stream);
+
+/* mms_marl_ppo_loss for up to MMS_MAX_GROUPS agents in one call: the loss heads of a MAPPO run's agents, whose updates do not depend
+ * on each other.  M, A, the four scalars and the five flags are shared; `table` is a HOST array of `groups` structs with what
+ * mms_marl_ppo_loss takes per call: indices may be NULL per group, dmu / dstd / dvalue are all three or none per group, row_logp may
+ * be NULL per group, norm_mean / norm_var are read only with use_norm, the fields as in the single entry (per-group bases and pitches:
+ * separate buffers as well as the agents' views of one [T, N, agents, A] block).
+ * Group g's outputs are bit-identical to mms_marl_ppo_loss called with group g's arguments (the rule of mms_q_heads_backup_group), on
+ * both builds: the same lane roles, the same order of every sum, the mask sum over group g's masks alone, per-block partials in
+ * double added in the single entry's order and rounded once.  No atomics, no memset, bit-identical run to run.
+ * Launches: three on hip_stream whatever `groups` is, the group on the grid's second dimension; no host synchronisation, no copy:
+ * the call is stream-ordered and can be captured in a graph.  How the table travels: one struct per group (18 pointers and 7
+ * pitches, 200 bytes) is 6.4 KB for 32 groups, and as arrays per member the rows pass alone reads 16 pointers and 7 pitches per
+ * group (5.9 KB), more than the 4 KB of kernel arguments.  So every pass carries in its own kernel arguments the per-group arrays
+ * it can (as mms_marl_heads_eval and mms_gru_group carry theirs: 2.8 KB for the rows pass, 0.8 KB for the finish pass), and the 12
+ * words per group that do not fit beside the rows pass's (std, norm_mean, norm_var, the bases of active_masks and factor, the seven
+ * pitches: 3 KB) travel in the arguments of the FIRST launch, which stores them at the head of the workspace, where the rows pass
+ * reads them; with a mask flag that first launch is the mask-sum pass, without one it does only this.  (A host-to-device copy of
+ * the table would read a host buffer that a captured graph outlives.)  Two launches without a mask flag would need the rows pass to
+ * hold all 23 words per group.
+ * workspace / ws_bytes: mms_mlp_grad's convention for this groups, M and A (NULL stores the bytes needed and returns 0 -- nothing
+ * else is read, not even table; 256-byte aligned; a smaller one is an error; the CPU build needs 0 and runs on any aligned non-NULL
+ * workspace).  No initialisation needed.  Errors: the single entry's per group, groups outside 1..MMS_MAX_GROUPS, table NULL; any
+ * error returns non-zero with mms_last_error(NULL) and writes nothing for any group. */
+typedef struct {
+    const float *mu, *std, *value;
+    const int64_t* indices;
+    mms_marl_loss_fields fields;
+    const float *norm_mean, *norm_var;
+    float *out, *dmu, *dstd, *dvalue, *row_logp;
+} mms_marl_loss_group;
+int mms_marl_ppo_loss_group(int device, int32_t groups, int64_t M, int32_t A, const mms_marl_loss_group* table, float clip,
+                            float value_loss_coef, float entropy_coef, float huber_delta, int32_t use_huber, int32_t clipped_value,
+                            int32_t policy_masks, int32_t value_masks, int32_t use_norm, void* workspace, int64_t* ws_bytes,
+                            void* hip_stream);
 
 /* ---- the parameter step: gradient-norm clip + Adam + polyak in two launches ---------------------------------------------------
  * What every learner ends a minibatch with -- nn.utils.clip_grad_norm_, torch.optim.Adam.step() and, off-policy, the per-parameter

@@ -8,6 +8,7 @@ CPU tensors).
                                     clip_param=.., value_loss_coef=.., entropy_coef=.., huber_delta=.., use_huber_loss=..,
                                     use_clipped_value_loss=.., use_policy_active_masks=False, use_value_active_masks=False,
                                     norm_mean=None, norm_var=None, indices=None, row_logp=False)
+    objectives, info = marl_ppo_loss_group(mus, stds, values, fields, ...)       G independent agents (MAPPO) in one call: see there
 
 `mu` [M, A], `std` [A] and `value` [M] or [M, 1] are what the networks gave for the minibatch.  The stored fields are taken as the
 buffers hold them -- [T, N, A] / [T+1, N, 1] tensors of a SeparatedReplayBuffer, or one agent's strided views of SharedRolloutBuffers
@@ -30,9 +31,10 @@ import math
 import torch
 
 from ... import _lib
-from ...model import MmsMarlLossFields, MmsRows
+from ...model import MmsMarlLossFields, MmsMarlLossGroup, MmsRows
 
 MAX_A = 128              # include/mms.h: MMS_MARL_LOSS_MAX_A
+MAX_GROUPS = 32          # include/mms.h: MMS_MAX_GROUPS
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 
 _workspaces = {}         # device -> uint8 tensor (grown on demand; every call on a device runs in stream order on the caller's stream)
@@ -192,3 +194,120 @@ def marl_ppo_loss(mu, std, value, actions, old_logp, adv, value_preds, returns, 
     if row_logp:
         info["row_logp"] = out[5]
     return out[0], info
+
+
+# ---- every agent of a MAPPO run in one call (mms_marl_ppo_loss_group) ---------------------------------------------------------------
+
+class _MarlPpoLossGroup(torch.autograd.Function):
+    """forward(ctx, setup, mu_0, std_0, value_0, mu_1, ..): one entry call per MAX_GROUPS groups; returns the G objectives (0-d, the only
+    differentiable outputs), the [G, 5] rows of the entry's `out` and, when asked for, the G row_logp vectors."""
+
+    @staticmethod
+    def forward(ctx, setup, *nets):
+        indices, fields, pitches, scalars, flags, norms, want_row_logp = setup
+        G = len(nets) // 3
+        mus, stds, values = nets[0::3], nets[1::3], nets[2::3]
+        M, A = mus[0].shape
+        dev = mus[0].device
+        L, idx, stream = _lib.for_device(dev)
+        out = torch.empty(G, 5, device=dev)
+        need = ctx.needs_input_grad
+        grads = [any(need[1 + 3 * g:4 + 3 * g]) for g in range(G)]
+        dmu = [torch.empty_like(mus[g]) if grads[g] else None for g in range(G)]
+        dstd = [torch.empty_like(stds[g]) if grads[g] else None for g in range(G)]
+        dv = [torch.empty(M, device=dev) if grads[g] else None for g in range(G)]
+        logp = [torch.empty(M, device=dev) if want_row_logp else None for g in range(G)]
+        ptr = lambda t: None if t is None else t.data_ptr()
+        for lo in range(0, G, MAX_GROUPS):
+            n = min(MAX_GROUPS, G - lo)
+            table = (MmsMarlLossGroup * n)()
+            for k in range(n):
+                g, t = lo + k, table[k]
+                t.mu, t.std, t.value, t.indices = ptr(mus[g]), ptr(stds[g]), ptr(values[g]), ptr(indices[g])
+                for name, f, pitch in zip(MmsMarlLossFields.NAMES, fields[g], pitches[g]):
+                    if f is not None:
+                        setattr(t.fields, name, MmsRows(f.data_ptr(), pitch))
+                t.norm_mean, t.norm_var = (ptr(norms[g][0]), ptr(norms[g][1])) if norms is not None else (None, None)
+                t.out, t.dmu, t.dstd, t.dvalue, t.row_logp = out[g].data_ptr(), ptr(dmu[g]), ptr(dstd[g]), ptr(dv[g]), ptr(logp[g])
+            nbytes = ctypes.c_int64(-1)
+            head = (idx, n, M, A, ctypes.addressof(table), *scalars, *flags)
+            _lib.check(L.mms_marl_ppo_loss_group(*head, None, ctypes.byref(nbytes), stream), None, "mms_marl_ppo_loss_group size query", L)
+            ws = _workspace(nbytes.value, dev)
+            _lib.check(L.mms_marl_ppo_loss_group(*head, ctypes.c_void_p(ws), ctypes.byref(nbytes), stream), None, "mms_marl_ppo_loss_group", L)
+        ctx.saved = (dmu, dstd, dv, [v.shape for v in values])
+        objectives = out[:, 0].unbind(0)
+        rest = (out,) + (tuple(logp) if want_row_logp else ())
+        ctx.mark_non_differentiable(*rest)
+        return objectives + rest
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gs):
+        dmu, dstd, dv, vshapes = ctx.saved
+        need = ctx.needs_input_grad
+        res = [None]
+        for g in range(len(dmu)):
+            k = 1 + 3 * g
+            res += [gs[g] * dmu[g] if need[k] else None, gs[g] * dstd[g] if need[k + 1] else None,
+                    (gs[g] * dv[g]).view(vshapes[g]) if need[k + 2] else None]
+        return tuple(res)
+
+
+def marl_ppo_loss_group(mus, stds, values, fields, *, clip_param, value_loss_coef, entropy_coef, huber_delta, use_huber_loss, use_clipped_value_loss,
+                        use_policy_active_masks=False, use_value_active_masks=False, norms=None, indices=None, row_logp=False):
+    """marl_ppo_loss for G agents whose updates do not depend on each other (MAPPO's), one mms_marl_ppo_loss_group call per 32 of them.
+    mus, stds, values: G tensors each, of one shape per kind; fields: G tuples (actions, old_logp, adv, value_preds, returns,
+    active_masks, factor) as marl_ppo_loss takes them; norms: None, or G pairs (norm_mean, norm_var); indices: None, or G entries
+    (None or an int64 device tensor of M rows).  The scalars and flags are shared.
+    Returns (objectives, info): G 0-d tensors, objective g differentiable with respect to (mus[g], stds[g], values[g]) and equal, bit
+    for bit, to marl_ppo_loss on agent g's arguments; info = {"policy_loss", "value_loss", "dist_entropy", "ratio"}: [G] device
+    tensors, and "row_logp": G [M] tensors when asked for.  Nothing is read back to the host.
+    Inputs the entry does not take (marl_ppo_loss's list) raise NotImplementedError: evaluate such agents one by one."""
+    mus, stds, values, fields = list(mus), list(stds), list(values), [tuple(f) for f in fields]
+    G = len(mus)
+    if G < 1 or not (len(stds) == len(values) == len(fields) == G):
+        raise ValueError("marl_ppo_loss_group: one std, value and tuple of fields per mu, at least one")
+    indices = [None] * G if indices is None else list(indices)
+    if len(indices) != G or (norms is not None and len(norms) != G):
+        raise ValueError("marl_ppo_loss_group: indices and norms hold one entry per agent")
+    masked = bool(use_policy_active_masks or use_value_active_masks)
+    dev = mus[0].device
+    if mus[0].dim() != 2:
+        raise NotImplementedError("marl_ppo_loss_group: mu must be [M, A]")
+    M, A = mus[0].shape
+    if not (1 <= A <= MAX_A and M >= 1):
+        raise NotImplementedError("marl_ppo_loss_group: 1 <= A <= %d and M >= 1" % MAX_A)
+    pitches = []
+    for g in range(G):
+        f = fields[g]
+        if len(f) != 7 or any(t is None for t in f[:5]) or (masked and f[5] is None):
+            raise ValueError("marl_ppo_loss_group: fields are (actions, old_logp, adv, value_preds, returns, active_masks, factor); active_masks with a mask flag")
+        f = fields[g] = tuple(t if (i != 5 or masked) else None for i, t in enumerate(f))      # (without a mask flag active_masks is not read)
+        if tuple(mus[g].shape) != (M, A) or stds[g].numel() != A or values[g].numel() != M:
+            raise ValueError("marl_ppo_loss_group: agent %d: mu [%d, %d], std [%d] and value [%d] expected" % (g, M, A, A, M))
+        if indices[g] is not None and not torch.is_tensor(indices[g]):
+            indices[g] = torch.as_tensor(indices[g], dtype=torch.int64, device=dev)
+        norm = () if norms is None else tuple(norms[g])
+        tensors = [t for t in (mus[g], stds[g], values[g]) + norm + f if t is not None]
+        ok = (all(t.dtype == torch.float32 and t.device == dev for t in tensors) and mus[g].is_contiguous() and stds[g].is_contiguous()
+              and values[g].is_contiguous() and len(norm) in (0, 2) and all(t is not None for t in norm)
+              and (indices[g] is None or (indices[g].dtype == torch.int64 and indices[g].is_contiguous() and indices[g].device == dev
+                                          and indices[g].numel() == M)))
+        rows = [None if t is None else field_rows(t, A if i < 2 else 1) for i, t in enumerate(f)] if ok else None
+        if not ok or any(r is None for r, t in zip(rows, f) if t is not None):
+            raise NotImplementedError("marl_ppo_loss_group: agent %d: float32 tensors on one device, dense mu / std / value, stored fields with dense rows "
+                                      "and int64 indices of M rows (marl_ppo_loss serves the rest, agent by agent)" % g)
+        if indices[g] is None and any(r[1] < M for r in rows if r is not None):
+            raise ValueError("marl_ppo_loss_group: agent %d: without indices the stored fields hold the minibatch's own rows first" % g)
+        pitches.append(tuple(0 if r is None else r[0] for r in rows))
+    scalars = (float(clip_param), float(value_loss_coef), float(entropy_coef), float(huber_delta))
+    flags = (int(bool(use_huber_loss)), int(bool(use_clipped_value_loss)), int(bool(use_policy_active_masks)), int(bool(use_value_active_masks)),
+             int(norms is not None))
+    setup = (indices, fields, pitches, scalars, flags, None if norms is None else [tuple(n) for n in norms], bool(row_logp))
+    nets = [t for g in range(G) for t in (mus[g], stds[g], values[g])]
+    res = _MarlPpoLossGroup.apply(setup, *nets)
+    out = res[G]
+    info = {"policy_loss": out[:, 1], "value_loss": out[:, 2], "dist_entropy": out[:, 3], "ratio": out[:, 4]}
+    if row_logp:
+        info["row_logp"] = list(res[G + 1:])
+    return res[:G], info

@@ -28,6 +28,15 @@ stored rows, `buffer.after_update()`.  The two log-probability passes per agent:
     policy raises.
 `train_infos` is in UPDATE order, as in the reference (its log_train labels entry i "agent i" all the same).
 
+`config["grouped_update"]` (absent in the reference's configs; default False = the loop above, unchanged; mappo only): MAPPO's surrogate
+does not read the factor and each agent has its own policy, buffer and normaliser, so the agents' updates do not depend on each other.
+True runs them in lockstep BEFORE the loop -- `MAPPO.train_group` over the trainers and buffers in `order` (trainer.py: the bases in
+grouped calls, one mms_marl_ppo_loss_group call per minibatch step, one host read per train()) -- and then walks `order` exactly as
+above without the `trainer.train` call: agent a's buffer receives the running factor, the factor takes agent a's ratio through the same
+call.  Another agent's update does not change agent a's log-probabilities, so every buffer's factor, `last_factor`, the policies and
+`train_infos` (in `order`) equal the loop's.  happo and hatrpo raise (their agents are sequential by definition: each surrogate carries
+the factor of the agents updated before it), so do recurrent policies and trainers without `fused_block_update`.
+
 `config["shared_buffers"]` (absent in the reference's configs; default False = one SeparatedReplayBuffer per agent): True runs on one
 SharedRolloutBuffers (utils/shared_buffer.py) with `collect_into` / `env_step` / `insert_step` / `values_into`: observations, actions,
 log-probabilities and values are read and written in the rollout slots where they lie.  `self.buffer` is then the list of its per-agent
@@ -107,6 +116,16 @@ class Runner:
         self.fused_factor = bool(config.get("fused_factor", not self.recurrent))
         if self.fused_factor and self.recurrent:
             raise NotImplementedError("Runner: fused_factor covers feed-forward policies; recurrent ones evaluate sequences through the modules")
+        # opt-in (the reference's config has no such key): MAPPO's agents updated in lockstep through MAPPO.train_group (train below)
+        self.grouped_update = bool(config.get("grouped_update", False))
+        if self.grouped_update:
+            if self.algorithm_name != "mappo":
+                raise NotImplementedError("Runner: grouped_update covers mappo; %s updates its agents one after another by definition (each agent's "
+                                          "surrogate carries the factor of those updated before it)" % self.algorithm_name)
+            if self.recurrent:
+                raise NotImplementedError("Runner: grouped_update covers feed-forward policies (a recurrent minibatch is a set of sequences)")
+            if not config.get("fused_block_update", False):
+                raise NotImplementedError("Runner: grouped_update needs fused_block_update (the grouped step runs the bases through blocks.mlp_base)")
         self.run_dir = config["run_dir"]
         self.log_dir = str(self.run_dir + '/' + self.env_name + '/' + self.algorithm_name + '/logs_seed{}'.format(self.seed))
         os.makedirs(self.log_dir, exist_ok=True)
@@ -251,13 +270,23 @@ class Runner:
         if self.fused_factor:
             obs, acts = [_rows(b.obs[:-1]) for b in self.buffer], [_rows(b.actions) for b in self.buffer]
             old = [t.clone() for t in self.grouped.evaluate_actions(obs, acts)]
+        group_infos = None
+        if self.grouped_update:
+            # every agent's update at once (no agent's update reads another's policy, buffer or factor), then the loop below as ever:
+            # agent a's log-probabilities before and after its own update are what they are in the sequential order
+            ids = [int(a) for a in order]
+            for a in ids:
+                self.trainer[a].prep_training()
+            if not self.fused_factor:
+                old_module = {a: self._module_logp(a) for a in ids}
+            group_infos = dict(zip(ids, type(self.trainer[0]).train_group([self.trainer[a] for a in ids], [self.buffer[a] for a in ids])))
         for agent_id in order:
             a = int(agent_id)
             self.trainer[a].prep_training()
             self.buffer[a].update_factor(factor)
             if not self.fused_factor:
-                old_logp = self._module_logp(a)
-            train_info = self.trainer[a].train(self.buffer[a])
+                old_logp = old_module[a] if self.grouped_update else self._module_logp(a)
+            train_info = group_infos[a] if self.grouped_update else self.trainer[a].train(self.buffer[a])
             if self.fused_factor:
                 self.grouped.evaluate_actions([obs[a]], [acts[a]], agents=[a], old_logp=[old[a]], factor=factor.view(-1, 1))
             else:

@@ -45,6 +45,11 @@ all of them go through mlp_base.  It needs fused_block_update (NotImplementedErr
 128 (NotImplementedError in the constructor) and minibatches whose row count is a multiple of 128 (NotImplementedError at the call,
 naming M); any other value raises ValueError.  HATRPO does not read the key.
 
+`MAPPO.train_group(trainers, buffers)` (no counterpart in the reference; what Runner's `grouped_update` calls): train() of several MAPPO
+trainers in lockstep, one loss.marl_ppo_loss_group call per minibatch step for all of them and the bases of all in grouped mlp_base
+calls; the permutations are drawn in the order of the loop over `trainer.train(buffer)` and every network runs through the same
+functions, so it leaves what that loop leaves.  It needs fused_block_update and one configuration and shape for all trainers.
+
 `ppo_update` takes the reference's gathered tuple.  `train` draws the permutation exactly as feed_forward_generator does
 (torch.randperm(batch), the same slices), gathers only the network inputs (share_obs, obs) and the returns the normaliser's batch
 moments need, and hands the index vector and the buffer's own tensors to the loss: under the same torch seed it equals a loop of
@@ -73,8 +78,8 @@ import torch
 import torch.nn as nn
 
 from ...optim import FusedAdam
-from .loss import marl_ppo_loss
-from .blocks import check_blocks, mlp_base
+from .loss import marl_ppo_loss, marl_ppo_loss_group
+from .blocks import MAX_GROUPS, check_blocks, mlp_base
 from .rnn_seq import check_grus, gru_sequence
 from .utils.valuenorm import ValueNorm
 
@@ -212,14 +217,7 @@ class _Trainer:
 
     def _update_tail(self, mu, std, values, returns_rows, fields, indices):
         """The normaliser, the loss, one backward, the clips and the steps of one update"""
-        actor, critic = self.policy.actor, self.policy.critic
-        norm = (None, None)
-        if self._use_valuenorm:
-            self.value_normalizer.update(returns_rows)                 # ... and the targets stay raw (module docstring)
-        if self._use_popart:
-            self.value_normalizer.update(returns_rows)
-            self.value_normalizer.update(returns_rows)
-            norm = self.value_normalizer.running_mean_var()
+        norm = self._update_normalizer(returns_rows)
         objective, info = self.loss_fn(mu, std, values, *fields, clip_param=self.clip_param, value_loss_coef=self.value_loss_coef,
                                        entropy_coef=self.entropy_coef, huber_delta=self.huber_delta, use_huber_loss=self._use_huber_loss,
                                        use_clipped_value_loss=self._use_clipped_value_loss, use_policy_active_masks=self._use_policy_active_masks,
@@ -227,22 +225,51 @@ class _Trainer:
         self.policy.actor_optimizer.zero_grad()
         self.policy.critic_optimizer.zero_grad()
         objective.backward()
+        actor_grad_norm, critic_grad_norm = self._clip_and_step()
+        return info["value_loss"], critic_grad_norm, info["policy_loss"], info["dist_entropy"], actor_grad_norm, info["ratio"]
+
+    def _clip_and_step(self, grad_norm=get_grad_norm):
+        """The two clips and the two steps behind a backward; returns (actor_grad_norm, critic_grad_norm).  grad_norm: what measures the
+        norm where nothing clips (train_group passes the same sum without the host read)"""
+        actor, critic = self.policy.actor, self.policy.critic
         if isinstance(self.policy.actor_optimizer, FusedAdam) and isinstance(self.policy.critic_optimizer, FusedAdam):
             # clip + step as one mms_param_step per network (optim.py; each optimizer holds its network's parameters, as the policies
             # build them); max_norm None: the norm is still computed and reported, nothing is clipped
             max_norm = self.max_grad_norm if self._use_max_grad_norm else None
             actor_grad_norm = self.policy.actor_optimizer.clip_and_step(max_norm)
             critic_grad_norm = self.policy.critic_optimizer.clip_and_step(max_norm)
-            return info["value_loss"], critic_grad_norm, info["policy_loss"], info["dist_entropy"], actor_grad_norm, info["ratio"]
+            return actor_grad_norm, critic_grad_norm
         if self._use_max_grad_norm:
             actor_grad_norm = nn.utils.clip_grad_norm_(actor.parameters(), self.max_grad_norm)
             critic_grad_norm = nn.utils.clip_grad_norm_(critic.parameters(), self.max_grad_norm)
         else:
-            actor_grad_norm = get_grad_norm(actor.parameters())
-            critic_grad_norm = get_grad_norm(critic.parameters())
+            actor_grad_norm = grad_norm(actor.parameters())
+            critic_grad_norm = grad_norm(critic.parameters())
         self.policy.actor_optimizer.step()
         self.policy.critic_optimizer.step()
-        return info["value_loss"], critic_grad_norm, info["policy_loss"], info["dist_entropy"], actor_grad_norm, info["ratio"]
+        return actor_grad_norm, critic_grad_norm
+
+    def _update_normalizer(self, returns_rows):
+        """The normaliser's updates of one minibatch; returns the (mean, variance) the loss normalises the targets with, or (None, None)"""
+        norm = (None, None)
+        if self._use_valuenorm:
+            self.value_normalizer.update(returns_rows)                 # ... and the targets stay raw (module docstring)
+        if self._use_popart:
+            self.value_normalizer.update(returns_rows)
+            self.value_normalizer.update(returns_rows)
+            norm = self.value_normalizer.running_mean_var()
+        return norm
+
+    def _advantages(self, buffer):
+        """train()'s normalised advantages of a buffer, [T, N, 1] contiguous"""
+        if self.value_normalizer is not None:
+            advantages = buffer.returns[:-1] - self.value_normalizer.denormalize(buffer.value_preds[:-1])
+        else:
+            advantages = buffer.returns[:-1] - buffer.value_preds[:-1]
+        advantages_copy = advantages.clone()
+        mean_advantages = torch.mean(advantages_copy)
+        std_advantages = torch.std(advantages_copy)
+        return ((advantages - mean_advantages) / (std_advantages + 1e-5)).contiguous()
 
     def ppo_update(self, sample, update_actor=True):
         """One update from the generators' gathered tuple; returns (value_loss, critic_grad_norm, policy_loss, dist_entropy,
@@ -256,14 +283,7 @@ class _Trainer:
 
     def train(self, buffer, update_actor=True):
         """The reference's train(): ppo_epoch passes over num_mini_batch random minibatches of the buffer; returns train_info."""
-        if self.value_normalizer is not None:
-            advantages = buffer.returns[:-1] - self.value_normalizer.denormalize(buffer.value_preds[:-1])
-        else:
-            advantages = buffer.returns[:-1] - buffer.value_preds[:-1]
-        advantages_copy = advantages.clone()
-        mean_advantages = torch.mean(advantages_copy)
-        std_advantages = torch.std(advantages_copy)
-        advantages = ((advantages - mean_advantages) / (std_advantages + 1e-5)).contiguous()
+        advantages = self._advantages(buffer)
         train_info = {k: 0 for k in ("value_loss", "policy_loss", "dist_entropy", "actor_grad_norm", "critic_grad_norm", "ratio")}
         if self._recurrent:                                            # mappo_trainer.py:210-227 with the recurrent generators
             for _ in range(self.ppo_epoch):
@@ -316,9 +336,134 @@ class _Trainer:
         self.policy.critic.eval()
 
 
+def _grad_norm_on_device(params):
+    """get_grad_norm without its host read: the same sum, its root in double on the device (math.sqrt takes the sum as a double too)"""
+    total = 0.0
+    for p in params:
+        if p.grad is not None:
+            total += p.grad.norm() ** 2
+    return torch.sqrt(total.double()) if torch.is_tensor(total) else total
+
+
+_GROUP_KEYS = ("clip_param", "ppo_epoch", "num_mini_batch", "value_loss_coef", "entropy_coef", "max_grad_norm", "huber_delta", "_use_valuenorm",
+               "_use_popart", "_use_max_grad_norm", "_use_clipped_value_loss", "_use_huber_loss", "_use_value_active_masks", "_use_policy_active_masks",
+               "_block_products")
+
+
+def _check_group(trainers, buffers):
+    """What MAPPO.train_group takes (its docstring), or NotImplementedError; nothing is changed"""
+    who = "MAPPO.train_group"
+    if not trainers or len(trainers) != len(buffers):
+        raise ValueError("%s: one buffer per trainer, at least one" % who)
+    first = trainers[0]
+    shapes = None
+    for t, b in zip(trainers, buffers):
+        if type(t) is not MAPPO:
+            raise NotImplementedError("%s: MAPPO trainers only (HAPPO's and HATRPO's agents are sequential: each surrogate carries the factor of those "
+                                      "updated before it), got %s" % (who, type(t).__name__))
+        if t._recurrent:
+            raise NotImplementedError("%s: feed-forward policies only (a recurrent minibatch is a set of sequences, not of rows)" % who)
+        if not t._fused_block_update:
+            raise NotImplementedError("%s: every trainer needs fused_block_update (the grouped step runs the bases through blocks.mlp_base)" % who)
+        if t.loss_fn is not marl_ppo_loss:
+            raise NotImplementedError("%s: a trainer's loss_fn was replaced; the grouped step evaluates loss.marl_ppo_loss_group" % who)
+        for k in _GROUP_KEYS:
+            if getattr(t, k) != getattr(first, k):
+                raise NotImplementedError("%s: one configuration for all trainers; %s differs (%r, %r)" % (who, k.lstrip("_"), getattr(first, k), getattr(t, k)))
+        actor, critic = t.policy.actor, t.policy.critic
+        sig = (check_blocks([actor.base, critic.base], who, t._block_products), actor.base.mlp.fc1[0].in_features, critic.base.mlp.fc1[0].in_features,
+               tuple(b.actions.shape), tuple(b.obs.shape), tuple(b.share_obs.shape), b.rewards.device, t.device)
+        if shapes is None:
+            shapes = sig
+        elif sig != shapes:
+            raise NotImplementedError("%s: one set of shapes for all trainers (hidden width, blocks, observation widths, actions, T, N, device): %r against %r"
+                                      % (who, shapes, sig))
+    T, N = buffers[0].rewards.shape[0:2]
+    if T * N < first.num_mini_batch:
+        raise NotImplementedError("%s: fewer rows (%d) than minibatches (%d)" % (who, T * N, first.num_mini_batch))
+
+
+def _train_group(trainers, buffers, update_actor):
+    trainers, buffers = list(trainers), list(buffers)
+    _check_group(trainers, buffers)
+    first, G = trainers[0], len(trainers)
+    T, N = buffers[0].rewards.shape[0:2]
+    batch = T * N
+    mini_batch_size = batch // first.num_mini_batch
+    device = buffers[0].rewards.device
+    advantages = [t._advantages(b) for t, b in zip(trainers, buffers)]
+    # the sequential loop's draws, in its order: trainer by trainer, one permutation per epoch
+    perms = [[torch.randperm(batch) for _ in range(first.ppo_epoch)] for _ in trainers]
+    fields = [(b.actions, b.action_log_probs, adv, b.value_preds, b.returns, b.active_masks, None) for b, adv in zip(buffers, advantages)]
+    rows = [(_rows(b.share_obs[:-1]), _rows(b.obs[:-1]), _rows(b.returns[:-1])) for b in buffers]
+    actors, critics = [t.policy.actor for t in trainers], [t.policy.critic for t in trainers]
+    heads = [a.act.action_out for a in actors]
+    products = first._block_products
+
+    def bases(xs, nets):
+        out = []
+        for i in range(0, len(nets), MAX_GROUPS):                     # (mlp_base takes 32 networks per call)
+            out += mlp_base(xs[i:i + MAX_GROUPS], [n.base for n in nets[i:i + MAX_GROUPS]], products)
+        return out
+
+    def actor_outputs(fa):
+        return ([h.fc_mean(f) for h, f in zip(heads, fa)], [torch.sigmoid(h.log_std / h.std_x_coef) * h.std_y_coef for h in heads])
+
+    sums = None                                                         # per key a [G] accumulator on the device
+    for e in range(first.ppo_epoch):
+        for b in range(first.num_mini_batch):
+            idx = [p[e][b * mini_batch_size:(b + 1) * mini_batch_size].to(device) for p in perms]
+            share = [r[0][i] for r, i in zip(rows, idx)]
+            obs = [r[1][i] for r, i in zip(rows, idx)]
+            if update_actor:                                            # actor and critic of an agent side by side, as _bases pairs them
+                both = bases([x for pair in zip(obs, share) for x in pair], [n for pair in zip(actors, critics) for n in pair])
+                fa, fc = both[0::2], both[1::2]
+                mus, stds = actor_outputs(fa)
+            else:
+                fc = bases(share, critics)
+                with torch.no_grad():
+                    mus, stds = actor_outputs(bases(obs, actors))
+            values = [c.v_out(f) for c, f in zip(critics, fc)]
+            norms = [t._update_normalizer(r[2][i]) for t, r, i in zip(trainers, rows, idx)]
+            objectives, info = marl_ppo_loss_group(mus, stds, values, fields, clip_param=first.clip_param, value_loss_coef=first.value_loss_coef,
+                                                   entropy_coef=first.entropy_coef, huber_delta=first.huber_delta, use_huber_loss=first._use_huber_loss,
+                                                   use_clipped_value_loss=first._use_clipped_value_loss,
+                                                   use_policy_active_masks=first._use_policy_active_masks, use_value_active_masks=first._use_value_active_masks,
+                                                   norms=norms if first._use_popart else None, indices=idx)
+            for t in trainers:
+                t.policy.actor_optimizer.zero_grad()
+                t.policy.critic_optimizer.zero_grad()
+            torch.stack(objectives).sum().backward()                    # (every objective receives the gradient 1, as objective.backward() gives it)
+            steps = [t._clip_and_step(_grad_norm_on_device) for t in trainers]
+            # (clip_grad_norm_ over parameters without a gradient returns a host zero: update_actor=False)
+            as_row = lambda xs: torch.stack([x.to(device) if torch.is_tensor(x) else torch.tensor(x, dtype=torch.float64, device=device) for x in xs])
+            # train()'s sums: the three .item() values add as Python floats (doubles), the norms and the ratio in the type they come in
+            step = {"value_loss": info["value_loss"].double(), "policy_loss": info["policy_loss"].double(), "dist_entropy": info["dist_entropy"].double(),
+                    "actor_grad_norm": as_row([s[0] for s in steps]), "critic_grad_norm": as_row([s[1] for s in steps]), "ratio": info["ratio"]}
+            sums = step if sums is None else {k: sums[k] + v for k, v in step.items()}
+    num_updates = first.ppo_epoch * first.num_mini_batch
+    keys = ("value_loss", "policy_loss", "dist_entropy", "actor_grad_norm", "critic_grad_norm", "ratio")
+    table = torch.stack([(sums[k] / num_updates).double() for k in keys]).cpu()          # the one host read
+    return [{k: float(table[j, g]) for j, k in enumerate(keys)} for g in range(G)]
+
+
 class MAPPO(_Trainer):
     """agents/algorithms/marl/mappo_trainer.py: MAPPO (module docstring)."""
     _has_valuenorm = True
+
+    @staticmethod
+    def train_group(trainers, buffers, update_actor=True):
+        """train() of several MAPPO trainers in lockstep: MAPPO's agents do not depend on each other (no factor in the surrogate), so one
+        (epoch, minibatch) step of all of them is the bases in grouped calls of up to 32 networks, ONE loss.marl_ppo_loss_group call,
+        one backward of the objectives' sum and each policy's own clips and steps; the gathers, feature_norm, the two heads and the
+        normalisers stay per agent.  Returns the train_info dictionaries in the trainers' order, their values train()'s under float();
+        the statistics add up on the device and are read once, behind the last step.
+        The permutations are drawn as the loop `for t, b: t.train(b)` draws them (trainer by trainer, one per epoch), so every agent sees
+        the minibatches it would have seen there and torch's generator ends in the same state; every network runs through the same
+        functions on the same values, so parameters, optimizer states and normalisers end as that loop leaves them.
+        Taken: feed-forward policies, fused_block_update on, one configuration (scalars, flags, block_products) and one set of shapes
+        for all trainers.  Anything else raises NotImplementedError before anything is drawn or changed."""
+        return _train_group(trainers, buffers, update_actor)
 
 
 class HAPPO(_Trainer):

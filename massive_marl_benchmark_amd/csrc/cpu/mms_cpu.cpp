@@ -1599,17 +1599,10 @@ MMS_API int mms_ppo_loss(int device, int64_t M, int32_t A, const float* mu, cons
 // ---- the MAPPO / HAPPO update's loss head (include/mms.h: mms_marl_ppo_loss) over ../marl_loss_lane.h -------------------------------
 // Chunks and sums as mms_ppo_loss above: a row's sums in double over ascending columns, a chunk's partials in double over ascending
 // rows, the chunks added in ascending order and rounded once; the mask sum in double over ascending rows.  No workspace.
-MMS_API int mms_marl_ppo_loss(int device, int64_t M, int32_t A, const float* mu, const float* std, const float* value, const int64_t* indices,
-                              const mms_marl_loss_fields* fields, float clip, float value_loss_coef, float entropy_coef, float huber_delta,
-                              int32_t use_huber, int32_t clipped_value, int32_t policy_masks, int32_t value_masks, int32_t use_norm,
-                              const float* norm_mean, const float* norm_var, float* out, float* dmu, float* dstd, float* dvalue, float* row_logp,
-                              void* workspace, int64_t* ws_bytes, void*) {
-    if (cpu_only(device)) return 1;
-    if (refused(check_marl_ppo_loss(M, A, mu, std, value, fields, policy_masks, value_masks, use_norm, norm_mean, norm_var, out, dmu, dstd, dvalue,
-                                    workspace, ws_bytes, 0)))
-        return 1;
-    if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query
-    const mms_marl_loss_fields f = *fields;
+static void marl_ppo_loss_one(int64_t M, int32_t A, const float* mu, const float* std, const float* value, const int64_t* indices,
+                              const mms_marl_loss_fields& f, float clip, float value_loss_coef, float entropy_coef, float huber_delta, int32_t use_huber,
+                              int32_t clipped_value, int32_t policy_masks, int32_t value_masks, int32_t use_norm, const float* norm_mean,
+                              const float* norm_var, float* out, float* dmu, float* dstd, float* dvalue, float* row_logp) {
     const bool grads = dmu != nullptr, pm = policy_masks != 0, vm = value_masks != 0;
     int64_t chunk = (M + 1023) / 1024;
     chunk = chunk < 256 ? 256 : chunk;
@@ -1669,5 +1662,34 @@ MMS_API int mms_marl_ppo_loss(int device, int64_t M, int32_t A, const float* mu,
     mms::marl_finish_scalars(tot[0], tot[1], tot[2], entropy, pm ? msum : (double)M, vm ? msum : (double)M, ent_scale, M, value_loss_coef, entropy_coef, out);
     if (grads)
         for (int j = 0; j < A; j++) dstd[j] = mms::marl_finish_dstd(tot[3 + j], std[j], entropy_coef, ent_scale);
+}
+
+MMS_API int mms_marl_ppo_loss(int device, int64_t M, int32_t A, const float* mu, const float* std, const float* value, const int64_t* indices,
+                              const mms_marl_loss_fields* fields, float clip, float value_loss_coef, float entropy_coef, float huber_delta,
+                              int32_t use_huber, int32_t clipped_value, int32_t policy_masks, int32_t value_masks, int32_t use_norm,
+                              const float* norm_mean, const float* norm_var, float* out, float* dmu, float* dstd, float* dvalue, float* row_logp,
+                              void* workspace, int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_marl_ppo_loss(M, A, mu, std, value, fields, policy_masks, value_masks, use_norm, norm_mean, norm_var, out, dmu, dstd, dvalue,
+                                    workspace, ws_bytes, 0)))
+        return 1;
+    if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query
+    marl_ppo_loss_one(M, A, mu, std, value, indices, *fields, clip, value_loss_coef, entropy_coef, huber_delta, use_huber, clipped_value, policy_masks,
+                      value_masks, use_norm, norm_mean, norm_var, out, dmu, dstd, dvalue, row_logp);
+    return 0;
+}
+
+// one group after the other, each as the single entry evaluates it: group g's bits are mms_marl_ppo_loss's on group g's arguments
+MMS_API int mms_marl_ppo_loss_group(int device, int32_t groups, int64_t M, int32_t A, const mms_marl_loss_group* table, float clip,
+                                    float value_loss_coef, float entropy_coef, float huber_delta, int32_t use_huber, int32_t clipped_value,
+                                    int32_t policy_masks, int32_t value_masks, int32_t use_norm, void* workspace, int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_marl_ppo_loss_group(groups, M, A, table, policy_masks, value_masks, use_norm, workspace, ws_bytes, 0))) return 1;
+    if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query
+    for (int g = 0; g < groups; g++) {
+        const mms_marl_loss_group& t = table[g];
+        marl_ppo_loss_one(M, A, t.mu, t.std, t.value, t.indices, t.fields, clip, value_loss_coef, entropy_coef, huber_delta, use_huber, clipped_value,
+                          policy_masks, value_masks, use_norm, t.norm_mean, t.norm_var, t.out, t.dmu, t.dstd, t.dvalue, t.row_logp);
+    }
     return 0;
 }

@@ -39,6 +39,8 @@ hipError_t launch_ppo_loss(int64_t, int, const float*, const float*, const float
 int64_t marl_loss_ws_bytes(int64_t, int);
 hipError_t launch_marl_ppo_loss(int64_t, int, const float*, const float*, const float*, const int64_t*, const mms_marl_loss_fields&, float, float, float,
                                 float, int, int, int, int, int, const float*, const float*, float*, float*, float*, float*, float*, void*, hipStream_t);
+int64_t marl_loss_group_ws_bytes(int, int64_t, int);
+hipError_t launch_marl_ppo_loss_group(int, int64_t, int, const mms_marl_loss_group*, float, float, float, float, int, int, int, int, int, void*, hipStream_t);
 hipError_t launch_param_step(const ParamArgs&, hipStream_t);
 int64_t sac_grad_ws_bytes(int64_t, int);
 hipError_t launch_sac_heads_grad(int64_t, int, float, float, const float*, const float*, const float*, const float*, const float*, float*, float*, void*,
@@ -972,6 +974,20 @@ __attribute__((visibility("default"))) int mms_marl_ppo_loss(int device, int64_t
     MMS_FREE(mms::launch_marl_ppo_loss(M, A, mu, std, value, indices, *fields, clip, value_loss_coef, entropy_coef, huber_delta, use_huber, clipped_value,
                                        policy_masks, value_masks, use_norm, norm_mean, norm_var, out, dmu, dstd, dvalue, row_logp, workspace,
                                        (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_marl_ppo_loss_group(int device, int32_t groups, int64_t M, int32_t A, const mms_marl_loss_group* table,
+                                                                   float clip, float value_loss_coef, float entropy_coef, float huber_delta,
+                                                                   int32_t use_huber, int32_t clipped_value, int32_t policy_masks, int32_t value_masks,
+                                                                   int32_t use_norm, void* workspace, int64_t* ws_bytes, void* s) {
+    MMS_DEV(device)
+    const bool shapes = groups >= 1 && groups <= MMS_MAX_GROUPS && M >= 1 && M <= 0x7fffffff && A >= 1 && A <= MMS_MARL_LOSS_MAX_A;
+    const int64_t need = shapes ? mms::marl_loss_group_ws_bytes(groups, M, A) : 0;
+    if (refused(check_marl_ppo_loss_group(groups, M, A, table, policy_masks, value_masks, use_norm, workspace, ws_bytes, need))) return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }                // the size query
+    MMS_FREE(mms::launch_marl_ppo_loss_group(groups, M, A, table, clip, value_loss_coef, entropy_coef, huber_delta, use_huber, clipped_value, policy_masks,
+                                             value_masks, use_norm, workspace, (hipStream_t)s));
     return 0;
 }
 

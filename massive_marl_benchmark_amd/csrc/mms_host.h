@@ -466,6 +466,26 @@ static inline std::string check_marl_ppo_loss(int64_t M, int32_t A, const float*
     return {};
 }
 
+// mms_marl_ppo_loss_group: the shared shapes and the table, then check_marl_ppo_loss per group (the first refusal names its group).
+static inline std::string check_marl_ppo_loss_group(int32_t groups, int64_t M, int32_t A, const mms_marl_loss_group* table, int32_t policy_masks,
+                                                    int32_t value_masks, int32_t use_norm, const void* workspace, const int64_t* ws_bytes, int64_t need) {
+    const std::string name = "mms_marl_ppo_loss_group";
+    if (!ws_bytes) return name + ": ws_bytes required";
+    std::string bad = check_groups(name.c_str(), groups);
+    if (!bad.empty()) return bad;
+    if (M < 1 || M > 0x7fffffff) return name + ": M must be in 1..2147483647";
+    if (A < 1 || A > MMS_MARL_LOSS_MAX_A) return name + ": A must be in 1.." + std::to_string(MMS_MARL_LOSS_MAX_A);
+    if (!workspace) return {};
+    if (!table) return name + ": table is NULL";
+    for (int g = 0; g < groups; g++) {
+        const mms_marl_loss_group& t = table[g];
+        bad = check_marl_ppo_loss(M, A, t.mu, t.std, t.value, &t.fields, policy_masks, value_masks, use_norm, t.norm_mean, t.norm_var, t.out, t.dmu, t.dstd,
+                                  t.dvalue, workspace, ws_bytes, need);
+        if (!bad.empty()) return name + ": group " + std::to_string(g) + ": " + bad;
+    }
+    return {};
+}
+
 static inline std::string check_linear2_act(int64_t M, int32_t N, int32_t K, const float* x0, const float* w0, const float* b0, const float* y0,
                                             const float* x1, const float* w1, const float* b1, const float* y1, int32_t act) {
     if (!x0 || !w0 || !b0 || !y0 || M < 0 || M > 0x7fffffff || N <= 0 || K <= 0 || (K % 4) != 0 || act < 0 || act > 3)

@@ -94,6 +94,12 @@ class MmsMarlLossFields(ctypes.Structure):
     _fields_ = [(n, MmsRows) for n in NAMES]
 
 
+class MmsMarlLossGroup(ctypes.Structure):
+    """struct mms_marl_loss_group (include/mms.h): one agent's arguments of mms_marl_ppo_loss_group."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("mu", "std", "value", "indices")] + [("fields", MmsMarlLossFields)] +
+                [(n, ctypes.c_void_p) for n in ("norm_mean", "norm_var", "out", "dmu", "dstd", "dvalue", "row_logp")])
+
+
 # ----------------------------------------------------------------------------------------------
 # ant description (restated from nv_ant.xml; see module docstring)
 # ----------------------------------------------------------------------------------------------

@@ -18,9 +18,15 @@ the factor-only loop on identical parameters (a check that they compute the same
 The kernel alone: mms_marl_heads_eval on 10 networks x `--kernel-rows` rows (default 32768) of width 512, 8 actions, with and without the
 factor, timed the same way (us per launch, and the GB/s of the [rows, 512] fp32 activations it reads).
 
+`--series grouped`: instead of the above, MAPPO's `Runner.train()` with `grouped_update` off (the agent loop) and on (MAPPO.train_group: the
+agents in lockstep, one mms_marl_ppo_loss_group call per step) at the same shapes, both with fused_block_update, FusedAdam optimizers
+and fused_factor, from the same rollout, alternating in this process: `train_sequential_ms`, `train_grouped_ms`, the same windows and
+verdict rule (profiles/marl_grouped_update_bench.jsonl).
+
 One JSON line per measurement on stdout, appended to --out when given.
 
     python tools/bench_marl_runner.py [--envs 4096,80] [--algos mappo,happo] [--rounds 5] [--calls 2] [--out profiles/marl_runner_bench.jsonl]
+    python tools/bench_marl_runner.py --series grouped [--envs 80,4096] [--out profiles/marl_grouped_update_bench.jsonl]
 """
 import argparse
 import ctypes
@@ -45,6 +51,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--kernel-rows", type=int, default=32768)
     ap.add_argument("--out", default="")
+    ap.add_argument("--series", default="factor", choices=("factor", "grouped"))
     args = ap.parse_args()
     import torch
     import marl_runner_check as rc
@@ -106,6 +113,44 @@ def main():
                 new_logp = r._module_logp(a)
                 factor = factor * torch.exp((new_logp - old_logp).reshape(T, N, -1).sum(dim=-1, keepdim=True))
         return factor
+
+    def rollout_into(first, others):
+        """one rollout on `first`, so that the buffers hold what a run leaves in them; the others receive copies of it and of the parameters"""
+        first.warmup()
+        for step in range(first.episode_length):
+            values, actions, logp, rs, rsc = first.collect(step)
+            obs, share_obs, rewards, dones, infos, _ = first.envs.step(actions)
+            first.insert((obs, share_obs, rewards, dones, infos, values, actions, logp, rs, rsc))
+        first.compute()
+        for r in others:
+            for a in range(first.num_agents):
+                r.policy[a].actor.load_state_dict(first.policy[a].actor.state_dict())
+                r.policy[a].critic.load_state_dict(first.policy[a].critic.state_dict())
+                if r.trainer[a].value_normalizer is not None:
+                    r.trainer[a].value_normalizer.load_state_dict(first.trainer[a].value_normalizer.state_dict())
+                for k, v in vars(first.buffer[a]).items():
+                    if torch.is_tensor(v):
+                        getattr(r.buffer[a], k).copy_(v)
+
+    if args.series == "grouped":
+        from massive_marl_benchmark_amd.optim import FusedAdam
+        for n in [int(v) for v in args.envs.split(",") if v]:
+            env = rc.make_env("cuda", n)
+            torch.manual_seed(1)
+            over = dict(run_dir=tempfile.mkdtemp(), n_rollout_threads=n, hidden_size=512, ppo_epoch=5, num_env_steps=8 * n, fused_block_update=True)
+            pair = {"sequential": Runner(env, rc.config("mappo", grouped_update=False, **over)), "grouped": Runner(env, rc.config("mappo", grouped_update=True, **over))}
+            for r in pair.values():
+                for pol in r.policy:
+                    pol.actor_optimizer, pol.critic_optimizer = FusedAdam.from_torch(pol.actor_optimizer), FusedAdam.from_torch(pol.critic_optimizer)
+            rollout_into(pair["sequential"], [pair["grouped"]])
+            trn = timed({k: r.train for k, r in pair.items()}, args.calls, args.warmup)
+            emit({"bench": "marl_grouped_update", "algo": "mappo", "envs": n, "rows": 8 * n, "agents": pair["grouped"].num_agents, "hidden": 512, "ppo_epoch": 5,
+                  "num_mini_batch": 1, "fused_block_update": True, "optimizer": "FusedAdam", "rounds": args.rounds, "calls": args.calls,
+                  "train_sequential_ms": win(trn["sequential"]), "train_grouped_ms": win(trn["grouped"]),
+                  "train_speedup_median": round(trn["sequential"][0] / trn["grouped"][0], 3), "train_verdict": verdict(trn["sequential"], trn["grouped"])})
+            del pair, env
+            torch.cuda.empty_cache()
+        return
 
     for n in [int(v) for v in args.envs.split(",") if v]:
         env = rc.make_env("cuda", n)
