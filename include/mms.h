@@ -49,6 +49,9 @@
  *     reached from marl/mappo_trainer.py:124-130, happo_trainer.py:115)    config key fused_block_update
  *   ... with the blocks' forward products on the two-plane fp16 layer     mms_elu_ln_planes16_group (forward, leaves y as
  *     kernel instead of the library                                        fp32 and as H32 planes); opt-in, config key block_products
+ *   DiagGaussian.fc_mean with its std expression and Critic.v_out in     mms_marl_heads_fwd_group (forward),
+ *     ppo_update, and autograd's backward of them                          mms_marl_heads_grad_group (backward); opt-in,
+ *     (algorithms/utils/distributions.py:94-117; actor_critic.py)          config key fused_head_update
  *   SquashedGaussianMLPActor heads + rsample + log-probability          mms_sac_heads_act
  *     (algorithms/rl/sac/module.py:23-61; sac.py:166, 374-376)
  *   autograd's backward of that head's epilogue in compute_loss_pi      mms_sac_heads_grad
@@ -699,6 +702,47 @@ int mms_elu_ln_grad_group(int device, int32_t groups, int64_t M, int32_t H, cons
                           const float* const* bias, const float* const* gamma, const float* const* stat, const float* const* dy,
                           int64_t dy_pitch, float* const* dz, int64_t dz_pitch, float* const* dparams, void* workspace,
                           int64_t* ws_bytes, void* hip_stream);
+
+/* ---- the output heads of the MAPPO / HAPPO networks in an update, forward and backward (csrc/marl_heads_grad_kernels.hip) ----------
+ * DiagGaussian.fc_mean = Linear(H, A) with std = sigmoid(log_std / std_x_coef) std_y_coef (agents/algorithms/utils/distributions.py)
+ * and Critic.v_out = Linear(H, 1), for up to MMS_MAX_GROUPS networks per call (algorithms/marl/heads.py).  Network g is
+ * (f_g [M, H] at f_pitch, w_g [A[g], H], b_g [A[g]]) with A[g] in 1..16; a critic is the A = 1 case.  For g < groups, r < M, j < A[g]:
+ *   out_g[r, j] = b_g[j] + sum_k w_g[j, k] f_g[r, k]                                     ([M, A[g]], dense)
+ *   std_g[j] = sigmoid(log_std_g[j] / x_coef) y_coef                                     (where log_std_g != NULL; [A[g]])
+ * Arithmetic (csrc/marl_heads_grad_lane.h): every product is formed in double from the fp32 values (exact), every sum is accumulated
+ * in double and rounded to fp32 once, behind the bias; std in double, rounded once.  The order of a row's sum is a function of H
+ * alone, so out_g[r, :] is a function of row r and of network g's parameters only, not of M, groups or where the row sits.
+ * f, w, b, log_std, out, std: HOST arrays of `groups` device pointers (log_std and std may be NULL as a whole, log_std per entry);
+ * A: HOST array; pitches in floats.  H a positive multiple of 4 up to 1024; f_pitch >= H and a multiple of 4; f_g, w_g 16-byte
+ * aligned; M >= 0 (M == 0 writes std only); groups 1..MMS_MAX_GROUPS.  No destination (out_g, std_g) may be a source or another
+ * destination of any group.  One launch on hip_stream, no atomics, no host synchronisation, the pointer tables in the kernel
+ * arguments.  Bad arguments return non-zero with mms_last_error(NULL) and write nothing. */
+int mms_marl_heads_fwd_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* f, int64_t f_pitch,
+                             const float* const* w, const float* const* b, const int32_t* A, const float* const* log_std, float x_coef,
+                             float y_coef, float* const* out, float* const* std, void* hip_stream);
+
+/* The backward of mms_marl_heads_fwd_group.  dout_g [M, A[g]] (dense) is d loss / d out_g, dstd_g [A[g]] is d loss / d std_g:
+ *   df_g[r, k] = sum_j dout_g[r, j] w_g[j, k], j ascending                                ([M, H] at df_pitch)
+ *   dw_g[j, k] = sum_r dout_g[r, j] f_g[r, k];   db_g[j] = sum_r dout_g[r, j]             ([A[g], H], [A[g]])
+ *   dlog_std_g[j] = dstd_g[j] y_coef s (1 - s) / x_coef,  s = sigmoid(log_std_g[j] / x_coef)
+ * with the forward's arithmetic: products and sums in double, one rounding.  df, dw with db, and dlog_std may each be NULL as a whole
+ * or per group (dw_g and db_g together): what is NULL is not computed and the other outputs keep their bits.  df_g[r, :] is a function
+ * of row r and w_g alone.  dw, db: per-workgroup partials in double in the workspace over a partition of the rows that is a function
+ * of (M, H), one finish pass in a fixed order, rounded once, no atomics -- bit-identical run to run and independent of `groups`: group
+ * g's outputs are bit for bit those of a call with groups = 1 on its arguments.  M == 0 succeeds and writes zeros into dw_g and db_g
+ * (and dlog_std_g), nothing else.
+ * Workspace as for mms_elu_ln_grad_group: workspace == NULL stores the bytes needed (a function of groups, M, H and A; the CPU build:
+ * 0) in *ws_bytes and returns 0 without reading anything but A; otherwise 256-byte aligned with *ws_bytes at least that.  At most two
+ * launches on hip_stream, no memset, no host synchronisation; the pointer tables travel in the kernel arguments.
+ * H, M, groups, A, f_pitch: the forward's rules; df_pitch >= H and a multiple of 4; f_g, w_g, df_g 16-byte aligned.  No destination
+ * (df_g, dw_g, db_g, dlog_std_g) may be a source (f_q, w_q, dout_q, log_std_q, dstd_q) or another destination of any group.  Rows past
+ * M and whatever lies between pitched rows are never written.  Bad arguments return non-zero with mms_last_error(NULL) and write
+ * nothing. */
+int mms_marl_heads_grad_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* f, int64_t f_pitch,
+                              const float* const* w, const int32_t* A, const float* const* dout, const float* const* log_std,
+                              const float* const* dstd, float x_coef, float y_coef, float* const* df, int64_t df_pitch,
+                              float* const* dw, float* const* db, float* const* dlog_std, void* workspace, int64_t* ws_bytes,
+                              void* hip_stream);
 
 /* ---- the same layers on the bf16 matrix pipe with fp32 operands carried as three bf16 planes (csrc/split_kernels.hip) -----------
  * An fp32 number is exactly a0 + a1 + a2 with a0 = bf16(a), a1 = bf16(a - a0), a2 = bf16(a - a0 - a1); the product is formed as the six

@@ -45,6 +45,15 @@ all of them go through mlp_base.  It needs fused_block_update (NotImplementedErr
 128 (NotImplementedError in the constructor) and minibatches whose row count is a multiple of 128 (NotImplementedError at the call,
 naming M); any other value raises ValueError.  HATRPO does not read the key.
 
+`config["fused_head_update"]` (absent in the reference's configs; default False = unchanged): the three places that form mu, std and the
+values -- the feed-forward and RNNLayer routes of `_update`, `_fused_rnn_forward` and `train_group` -- run fc_mean, the std expression and
+v_out through heads.update_heads instead: ONE mms_marl_heads_fwd_group call for the heads of a step and ONE mms_marl_heads_grad_group
+call for their backward (df, dW, db, dlog_std; sums in double in a fixed order), in place of two addmm, three element-wise launches and,
+backward, four products, two column sums and the std expression's backward per agent.  The recurrent routes hand over the output of
+rnn.norm.  With update_actor=False the actor's features are formed under no_grad and its head is left out of the backward call.  The
+constructor raises NotImplementedError for what update_heads refuses (heads.check_heads): more than 16 actions, a hidden width that is
+not a multiple of 4 or above 1024, non-fp32 parameters, a head without a bias.  HATRPO does not read the key.
+
 `MAPPO.train_group(trainers, buffers)` (no counterpart in the reference; what Runner's `grouped_update` calls): train() of several MAPPO
 trainers in lockstep, one loss.marl_ppo_loss_group call per minibatch step for all of them and the bases of all in grouped mlp_base
 calls; the permutations are drawn in the order of the loop over `trainer.train(buffer)` and every network runs through the same
@@ -72,6 +81,7 @@ The reference is mirrored as it runs:
     their mean and std over the whole buffer.
   * `imp_weights`, the last element of ppo_update's tuple, is the [M, 1] tensor of ratios in the reference, of which train() takes
     .mean(); here it is that mean, a device scalar (its .mean() is itself)."""
+import contextlib
 import math
 
 import torch
@@ -80,6 +90,7 @@ import torch.nn as nn
 from ...optim import FusedAdam
 from .loss import marl_ppo_loss, marl_ppo_loss_group
 from .blocks import MAX_GROUPS, check_blocks, mlp_base
+from .heads import check_heads, update_heads
 from .rnn_seq import check_grus, gru_sequence
 from .utils.valuenorm import ValueNorm
 
@@ -96,6 +107,11 @@ def _base(base, x):
     for layer in base.mlp.fc2:
         x = layer(x)
     return x
+
+
+def _grad_if(flag):
+    """The context of an actor's forward: as it is where the actor is updated, no_grad where it is not"""
+    return contextlib.nullcontext() if flag else torch.no_grad()
 
 
 def _is_rnn_layer(layer):
@@ -158,6 +174,10 @@ class _Trainer:
         head = getattr(getattr(policy.actor, "act", None), "action_out", None)
         if head is None or not (hasattr(head, "fc_mean") and hasattr(head, "log_std")):
             raise NotImplementedError("%s: only Box action spaces (ACTLayer.action_out = DiagGaussian) are covered" % name)
+        # opt-in (likewise): fc_mean, the std expression and v_out through heads.update_heads (module docstring)
+        self._fused_head_update = bool(config.get("fused_head_update", False))
+        if self._fused_head_update:
+            check_heads([policy.actor], [policy.critic], "%s: fused_head_update" % name)
         self.value_normalizer = ValueNorm(1, device=self.device) if (self._use_popart or self._use_valuenorm) else None
         self.loss_fn = marl_ppo_loss            # (a benchmark swaps in marl_ppo_loss_torch)
 
@@ -173,6 +193,11 @@ class _Trainer:
             return self._update_tail(*self._fused_rnn_forward(share_obs, obs, rnn, update_actor, base), returns_rows, fields, indices)
         else:
             features = lambda net, x, states: net.rnn(base(net, x), states, rnn[2])[0]             # actor_critic.py:64-65, 164-165
+        if self._fused_head_update:
+            fc = features(critic, share_obs, None if rnn is None else rnn[1])
+            with _grad_if(update_actor):
+                fa = features(actor, obs, None if rnn is None else rnn[0])
+            return self._update_tail(*self._fused_heads(fa, fc, update_actor), returns_rows, fields, indices)
         values = critic.v_out(features(critic, share_obs, None if rnn is None else rnn[1]))
         if update_actor:
             mu = head.fc_mean(features(actor, obs, None if rnn is None else rnn[0]))
@@ -198,6 +223,11 @@ class _Trainer:
                 fa, = mlp_base([obs], [actor.base], self._block_products)
         return lambda net, x: fa if net is actor else fc
 
+    def _fused_heads(self, fa, fc, update_actor):
+        """(mu, std, values) of this policy's two heads on the actor's features fa and the critic's fc through heads.update_heads"""
+        mus, stds, values = update_heads([fa], [fc], [self.policy.actor], [self.policy.critic], update_actor)
+        return mus[0], stds[0], values[0]
+
     def _fused_rnn_forward(self, share_obs, obs, rnn, update_actor, base):
         """(mu, std, values) with base -> gru_sequence -> rnn.norm -> head: the networks that need gradients in one grouped call, the actor
         alone under no_grad when it is not updated"""
@@ -205,14 +235,17 @@ class _Trainer:
         head = actor.act.action_out
         if update_actor:
             (ya, _), (yc, _) = gru_sequence([base(actor, obs), base(critic, share_obs)], [rnn[0], rnn[1]], rnn[2], [actor.rnn.rnn, critic.rnn.rnn])
-            mu = head.fc_mean(actor.rnn.norm(ya))
-            std = torch.sigmoid(head.log_std / head.std_x_coef) * head.std_y_coef
         else:
             (yc, _), = gru_sequence([base(critic, share_obs)], [rnn[1]], rnn[2], [critic.rnn.rnn])
             with torch.no_grad():
                 (ya, _), = gru_sequence([base(actor, obs)], [rnn[0]], rnn[2], [actor.rnn.rnn])
-                mu = head.fc_mean(actor.rnn.norm(ya))
+        with _grad_if(update_actor):
+            fa = actor.rnn.norm(ya)
+            if not self._fused_head_update:
+                mu = head.fc_mean(fa)
                 std = torch.sigmoid(head.log_std / head.std_x_coef) * head.std_y_coef
+        if self._fused_head_update:
+            return self._fused_heads(fa, critic.rnn.norm(yc), update_actor)
         return mu, std, critic.v_out(critic.rnn.norm(yc))
 
     def _update_tail(self, mu, std, values, returns_rows, fields, indices):
@@ -347,7 +380,7 @@ def _grad_norm_on_device(params):
 
 _GROUP_KEYS = ("clip_param", "ppo_epoch", "num_mini_batch", "value_loss_coef", "entropy_coef", "max_grad_norm", "huber_delta", "_use_valuenorm",
                "_use_popart", "_use_max_grad_norm", "_use_clipped_value_loss", "_use_huber_loss", "_use_value_active_masks", "_use_policy_active_masks",
-               "_block_products")
+               "_block_products", "_fused_head_update")
 
 
 def _check_group(trainers, buffers):
@@ -418,12 +451,16 @@ def _train_group(trainers, buffers, update_actor):
             if update_actor:                                            # actor and critic of an agent side by side, as _bases pairs them
                 both = bases([x for pair in zip(obs, share) for x in pair], [n for pair in zip(actors, critics) for n in pair])
                 fa, fc = both[0::2], both[1::2]
-                mus, stds = actor_outputs(fa)
             else:
                 fc = bases(share, critics)
                 with torch.no_grad():
-                    mus, stds = actor_outputs(bases(obs, actors))
-            values = [c.v_out(f) for c, f in zip(critics, fc)]
+                    fa = bases(obs, actors)
+            if first._fused_head_update:                                # all 2 G heads in one call (chunks of 32), their backward in one as well
+                mus, stds, values = update_heads(fa, fc, actors, critics, update_actor)
+            else:
+                with _grad_if(update_actor):
+                    mus, stds = actor_outputs(fa)
+                values = [c.v_out(f) for c, f in zip(critics, fc)]
             norms = [t._update_normalizer(r[2][i]) for t, r, i in zip(trainers, rows, idx)]
             objectives, info = marl_ppo_loss_group(mus, stds, values, fields, clip_param=first.clip_param, value_loss_coef=first.value_loss_coef,
                                                    entropy_coef=first.entropy_coef, huber_delta=first.huber_delta, use_huber_loss=first._use_huber_loss,
@@ -455,8 +492,9 @@ class MAPPO(_Trainer):
     def train_group(trainers, buffers, update_actor=True):
         """train() of several MAPPO trainers in lockstep: MAPPO's agents do not depend on each other (no factor in the surrogate), so one
         (epoch, minibatch) step of all of them is the bases in grouped calls of up to 32 networks, ONE loss.marl_ppo_loss_group call,
-        one backward of the objectives' sum and each policy's own clips and steps; the gathers, feature_norm, the two heads and the
-        normalisers stay per agent.  Returns the train_info dictionaries in the trainers' order, their values train()'s under float();
+        one backward of the objectives' sum and each policy's own clips and steps; the gathers, feature_norm, the two heads (with
+        fused_head_update: all 2 G of them in one heads.update_heads call) and the normalisers stay per agent.  Returns the
+        train_info dictionaries in the trainers' order, their values train()'s under float();
         the statistics add up on the device and are read once, behind the last step.
         The permutations are drawn as the loop `for t, b: t.train(b)` draws them (trainer by trainer, one per epoch), so every agent sees
         the minibatches it would have seen there and torch's generator ends in the same state; every network runs through the same

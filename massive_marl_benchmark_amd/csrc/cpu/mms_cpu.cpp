@@ -28,6 +28,7 @@
 #include "../gru_lane.h"
 #include "../gru_grad_lane.h"
 #include "../elu_ln_lane.h"
+#include "../marl_heads_grad_lane.h"
 #include "../marl_eval_lane.h"
 #include "lane_step.h"
 
@@ -1184,6 +1185,78 @@ MMS_API int mms_elu_ln_grad_group(int device, int32_t groups, int64_t M, int32_t
                 double s = 0.0;
                 for (int64_t c = 0; c < nchunks; c++) s += part[c * C + q];
                 dp[q] = (float)s;
+            }
+    }
+    return 0;
+}
+// The update's output heads (include/mms.h: mms_marl_heads_fwd_group) over ../marl_heads_grad_lane.h: a row's sums over ascending columns
+// in double, the bias behind them, one rounding.
+MMS_API int mms_marl_heads_fwd_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* f, int64_t f_pitch, const float* const* w,
+                                     const float* const* b, const int32_t* A, const float* const* log_std, float x_coef, float y_coef, float* const* out,
+                                     float* const* std_out, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_marl_heads_fwd_group(groups, M, H, f, f_pitch, w, b, A, log_std, x_coef, out, std_out))) return 1;
+    for (int g = 0; g < groups; g++) {
+        const int n = A[g];
+        if (log_std && log_std[g])
+            for (int j = 0; j < n; j++) std_out[g][j] = mms::heads_std(log_std[g][j], x_coef, y_coef);
+#pragma omp parallel for schedule(static)
+        for (int64_t m = 0; m < M; m++) {
+            const float* fr = f[g] + m * f_pitch;
+            for (int j = 0; j < n; j++) {
+                const float* wr = w[g] + (int64_t)j * H;
+                double s = 0.0;
+                for (int k = 0; k < H; k++) s += mms::heads_prod(fr[k], wr[k]);
+                out[g][m * n + j] = mms::heads_out(s, b[g][j]);
+            }
+        }
+    }
+    return 0;
+}
+// Their backward (include/mms.h: mms_marl_heads_grad_group).  The rows in the chunks of heads_chunk_rows(M, H) (OpenMP over chunks): a
+// chunk's sums over ascending rows in double, the chunks added in ascending order and rounded once -- the result does not depend on the
+// number of threads or on `groups`.  No workspace.  M == 0: zeros into dw and db.
+MMS_API int mms_marl_heads_grad_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* f, int64_t f_pitch, const float* const* w,
+                                      const int32_t* A, const float* const* dout, const float* const* log_std, const float* const* dstd, float x_coef,
+                                      float y_coef, float* const* df, int64_t df_pitch, float* const* dw, float* const* db, float* const* dlog_std,
+                                      void* workspace, int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_marl_heads_grad_group(groups, M, H, f, f_pitch, w, A, dout, log_std, dstd, x_coef, df, df_pitch, dw, db, dlog_std, workspace, ws_bytes, 0)))
+        return 1;
+    if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query
+    const int64_t chunk = mms::heads_chunk_rows(M, H), nchunks = mms::heads_chunks(M, H);
+    for (int g = 0; g < groups; g++) {
+        const int n = A[g];
+        const int64_t C = mms::heads_part_doubles(n, H);
+        float *dfg = df ? df[g] : nullptr, *dwg = dw ? dw[g] : nullptr, *dbg = db ? db[g] : nullptr;
+        if (dlog_std && dlog_std[g])
+            for (int j = 0; j < n; j++) dlog_std[g][j] = mms::heads_dlog_std(dstd[g][j], log_std[g][j], x_coef, y_coef);
+        std::vector<double> part(dwg ? (size_t)(nchunks * C) : 0, 0.0);
+#pragma omp parallel for schedule(static)
+        for (int64_t c = 0; c < nchunks; c++) {
+            double* p = dwg ? part.data() + c * C : nullptr;
+            const int64_t end = (c + 1) * chunk < M ? (c + 1) * chunk : M;
+            for (int64_t m = c * chunk; m < end; m++) {
+                const float *fr = f[g] + m * f_pitch, *d = dout[g] + m * n;
+                if (dfg)
+                    for (int k = 0; k < H; k++) {
+                        double s = 0.0;
+                        for (int j = 0; j < n; j++) s += mms::heads_prod(d[j], w[g][(int64_t)j * H + k]);
+                        dfg[m * df_pitch + k] = (float)s;
+                    }
+                if (p)
+                    for (int j = 0; j < n; j++) {
+                        for (int k = 0; k < H; k++) p[(int64_t)j * H + k] += mms::heads_prod(d[j], fr[k]);
+                        p[(int64_t)n * H + j] += (double)d[j];
+                    }
+            }
+        }
+        if (dwg)
+            for (int64_t q = 0; q < C; q++) {
+                double s = 0.0;
+                for (int64_t c = 0; c < nchunks; c++) s += part[c * C + q];
+                if (q < (int64_t)n * H) dwg[q] = (float)s;
+                else dbg[q - (int64_t)n * H] = (float)s;
             }
     }
     return 0;

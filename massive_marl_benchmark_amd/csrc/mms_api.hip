@@ -15,6 +15,7 @@
 #include "gru_gates_args.h"
 #include "gru_grad_args.h"
 #include "elu_ln_args.h"
+#include "marl_heads_grad_args.h"
 #include "marl_eval_args.h"
 
 namespace mms {
@@ -855,6 +856,49 @@ __attribute__((visibility("default"))) int mms_elu_ln_grad_group(int device, int
     a.part = static_cast<double*>(workspace);
     a.z_pitch = z_pitch; a.dy_pitch = dy_pitch; a.dz_pitch = dz_pitch; a.M = (int)M; a.H = H;
     MMS_FREE(mms::launch_elu_ln_grad_group(a, groups, (hipStream_t)s));
+    return 0;
+}
+
+// ---- the output heads of the MAPPO / HAPPO update, forward and backward (marl_heads_grad_kernels.hip) ------------------------------
+
+__attribute__((visibility("default"))) int mms_marl_heads_fwd_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* f, int64_t f_pitch,
+                                                                    const float* const* w, const float* const* b, const int32_t* A,
+                                                                    const float* const* log_std, float x_coef, float y_coef, float* const* out,
+                                                                    float* const* std_out, void* s) {
+    MMS_DEV(device)
+    if (refused(check_marl_heads_fwd_group(groups, M, H, f, f_pitch, w, b, A, log_std, x_coef, out, std_out))) return 1;
+    mms::MarlHeadsFwdArgs a = {};
+    for (int g = 0; g < groups; g++) {
+        a.f[g] = f[g]; a.w[g] = w[g]; a.b[g] = b[g]; a.out[g] = out[g]; a.A[g] = A[g];
+        a.log_std[g] = log_std ? log_std[g] : nullptr;
+        a.std[g] = a.log_std[g] ? std_out[g] : nullptr;
+    }
+    a.f_pitch = f_pitch; a.x_coef = x_coef; a.y_coef = y_coef; a.M = (int)M; a.H = H;
+    MMS_FREE(mms::launch_marl_heads_fwd_group(a, groups, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_marl_heads_grad_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* f, int64_t f_pitch,
+                                                                     const float* const* w, const int32_t* A, const float* const* dout,
+                                                                     const float* const* log_std, const float* const* dstd, float x_coef, float y_coef,
+                                                                     float* const* df, int64_t df_pitch, float* const* dw, float* const* db,
+                                                                     float* const* dlog_std, void* workspace, int64_t* ws_bytes, void* s) {
+    MMS_DEV(device)
+    const int64_t need = check_marl_heads_shapes("", groups, M, H, A).empty() ? mms::marl_heads_grad_ws_bytes(groups, M, H, A) : 0;
+    if (refused(check_marl_heads_grad_group(groups, M, H, f, f_pitch, w, A, dout, log_std, dstd, x_coef, df, df_pitch, dw, db, dlog_std, workspace, ws_bytes,
+                                            need)))
+        return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }                // the size query
+    mms::MarlHeadsGradArgs a = {};
+    for (int g = 0; g < groups; g++) {
+        a.f[g] = f[g]; a.w[g] = w[g]; a.dout[g] = dout[g]; a.A[g] = A[g];
+        a.df[g] = df ? df[g] : nullptr; a.dw[g] = dw ? dw[g] : nullptr; a.db[g] = db ? db[g] : nullptr;
+        a.dlog_std[g] = dlog_std ? dlog_std[g] : nullptr;
+        a.log_std[g] = a.dlog_std[g] ? log_std[g] : nullptr; a.dstd[g] = a.dlog_std[g] ? dstd[g] : nullptr;
+    }
+    a.part = static_cast<double*>(workspace);
+    a.f_pitch = f_pitch; a.df_pitch = df_pitch; a.x_coef = x_coef; a.y_coef = y_coef; a.M = (int)M; a.H = H;
+    MMS_FREE(mms::launch_marl_heads_grad_group(a, groups, (hipStream_t)s));
     return 0;
 }
 

@@ -937,6 +937,98 @@ static inline std::string check_elu_ln_grad_group(int32_t groups, int64_t M, int
     return {};
 }
 
+// the shapes of mms_marl_heads_fwd_group and mms_marl_heads_grad_group (A: HOST array)
+static inline std::string check_marl_heads_shapes(const char* who, int32_t groups, int64_t M, int32_t H, const int32_t* A) {
+    std::string bad = check_groups(who, groups);
+    if (!bad.empty()) return bad;
+    if (M < 0 || M > 0x7fffffff || H < 4 || (H % 4) != 0 || H > 1024)
+        return std::string(who) + ": bad shapes (0 <= M <= 2147483647, H a positive multiple of 4, H <= 1024)";
+    if (!A) return std::string(who) + ": null pointer (A is required)";
+    for (int g = 0; g < groups; g++)
+        if (A[g] < 1 || A[g] > 16) return std::string(who) + ": A[g] must be 1..16, got " + std::to_string(A[g]);
+    return {};
+}
+
+// mms_marl_heads_fwd_group: shapes, the pitch, then per group the pointers, their alignment and every destination against every source
+// and every other destination over all groups
+static inline std::string check_marl_heads_fwd_group(int32_t groups, int64_t M, int32_t H, const float* const* f, int64_t f_pitch, const float* const* w,
+                                                     const float* const* b, const int32_t* A, const float* const* log_std, float x_coef,
+                                                     float* const* out, float* const* std_out) {
+    const char* who = "mms_marl_heads_fwd_group";
+    std::string bad = check_marl_heads_shapes(who, groups, M, H, A);
+    if (!bad.empty()) return bad;
+    if (!f || !w || !b || !out) return std::string(who) + ": null pointer (f, w, b and out are required)";
+    if (f_pitch < H || (f_pitch % 4) != 0) return std::string(who) + ": bad pitch (f_pitch >= H, a multiple of 4)";
+    if (log_std && (!std_out || !(x_coef != 0.f))) return std::string(who) + ": log_std needs std and a non-zero x_coef";
+    for (int g = 0; g < groups; g++) {
+        if (!f[g] || !w[g] || !b[g] || !out[g] || (log_std && log_std[g] && !std_out[g])) return std::string(who) + ": null pointer in a group";
+        if (((addr(f[g]) | addr(w[g])) & 15) != 0 || ((addr(b[g]) | addr(out[g]) | (log_std ? addr(log_std[g]) | addr(std_out[g]) : 0)) & 3) != 0)
+            return std::string(who) + ": misaligned pointer in a group (f, w 16-byte aligned, b, log_std, out, std 4)";
+    }
+    for (int g = 0; g < groups; g++) {
+        const float* dst[2] = {out[g], log_std && log_std[g] ? std_out[g] : nullptr};
+        if (dst[0] == dst[1]) return std::string(who) + ": two destinations share an address";
+        for (int k = 0; k < 2; k++) {
+            if (!dst[k]) continue;
+            for (int q = 0; q < groups; q++) {
+                const float* src[4] = {f[q], w[q], b[q], log_std ? log_std[q] : nullptr};
+                for (int l = 0; l < 4; l++)
+                    if (dst[k] == src[l]) return std::string(who) + ": a destination (out, std) must not be a source (f, w, b, log_std)";
+                if (q == g) continue;
+                if (dst[k] == out[q] || (log_std && log_std[q] && dst[k] == std_out[q])) return std::string(who) + ": two groups share a destination";
+            }
+        }
+    }
+    return {};
+}
+
+// mms_marl_heads_grad_group: ws_bytes and the shapes first (workspace NULL is the size query: nothing but A is read), then as above.
+// `need`: the build's workspace size (the CPU build: 0).
+static inline std::string check_marl_heads_grad_group(int32_t groups, int64_t M, int32_t H, const float* const* f, int64_t f_pitch, const float* const* w,
+                                                      const int32_t* A, const float* const* dout, const float* const* log_std, const float* const* dstd,
+                                                      float x_coef, float* const* df, int64_t df_pitch, float* const* dw, float* const* db,
+                                                      float* const* dlog_std, const void* workspace, const int64_t* ws_bytes, int64_t need) {
+    const char* who = "mms_marl_heads_grad_group";
+    std::string bad = check_marl_heads_shapes(who, groups, M, H, A);
+    if (!bad.empty()) return bad;
+    if (!ws_bytes) return std::string(who) + ": ws_bytes required";
+    if (!workspace) return {};
+    if (!f || !w || !dout) return std::string(who) + ": null pointer (f, w and dout are required)";
+    if ((dw == nullptr) != (db == nullptr)) return std::string(who) + ": dw and db are given together or not at all";
+    if (f_pitch < H || (f_pitch % 4) != 0 || (df && (df_pitch < H || (df_pitch % 4) != 0)))
+        return std::string(who) + ": bad pitches (f_pitch, df_pitch >= H, each a multiple of 4)";
+    if (dlog_std && (!log_std || !dstd || !(x_coef != 0.f))) return std::string(who) + ": dlog_std needs log_std, dstd and a non-zero x_coef";
+    if (*ws_bytes < need) return std::string(who) + ": workspace too small (" + std::to_string(*ws_bytes) + " bytes, needs " + std::to_string(need) + ")";
+    if (addr(workspace) & 255) return std::string(who) + ": workspace must be 256-byte aligned";
+    const auto at = [](float* const* t, int g) -> float* { return t ? t[g] : nullptr; };
+    for (int g = 0; g < groups; g++) {
+        if (!f[g] || !w[g] || !dout[g]) return std::string(who) + ": null pointer in a group";
+        if ((at(dw, g) == nullptr) != (at(db, g) == nullptr)) return std::string(who) + ": dw_g and db_g are given together or not at all";
+        if (at(dlog_std, g) && (!log_std[g] || !dstd[g])) return std::string(who) + ": dlog_std_g needs log_std_g and dstd_g";
+        if (((addr(f[g]) | addr(w[g]) | addr(at(df, g))) & 15) != 0 ||
+            ((addr(dout[g]) | addr(at(dw, g)) | addr(at(db, g)) | addr(at(dlog_std, g)) | (log_std ? addr(log_std[g]) : 0) | (dstd ? addr(dstd[g]) : 0)) & 3) != 0)
+            return std::string(who) + ": misaligned pointer in a group (f, w, df 16-byte aligned, the others 4)";
+    }
+    for (int g = 0; g < groups; g++) {
+        const float* dst[4] = {at(df, g), at(dw, g), at(db, g), at(dlog_std, g)};
+        for (int k = 0; k < 4; k++) {
+            if (!dst[k]) continue;
+            for (int l = k + 1; l < 4; l++)
+                if (dst[k] == dst[l]) return std::string(who) + ": two destinations share an address";
+            for (int q = 0; q < groups; q++) {
+                const float* src[5] = {f[q], w[q], dout[q], log_std ? log_std[q] : nullptr, dstd ? dstd[q] : nullptr};
+                for (int l = 0; l < 5; l++)
+                    if (dst[k] == src[l]) return std::string(who) + ": a destination (df, dw, db, dlog_std) must not be a source (f, w, dout, log_std, dstd)";
+                if (q == g) continue;
+                const float* other[4] = {at(df, q), at(dw, q), at(db, q), at(dlog_std, q)};
+                for (int l = 0; l < 4; l++)
+                    if (dst[k] == other[l]) return std::string(who) + ": two groups share a destination";
+            }
+        }
+    }
+    return {};
+}
+
 // mms_mlp_grad and mms_mlp_grad_rop: the shapes, then (workspace NULL is the size query: nothing else is read) the operands.  The
 // workspace's size and alignment are the HIP build's own; the CPU build needs none.
 static inline std::string check_mlp_shapes(const char* entry, int32_t layers, int64_t M, const int32_t* dims, const int64_t* ws_bytes) {

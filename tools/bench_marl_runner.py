@@ -21,7 +21,12 @@ factor, timed the same way (us per launch, and the GB/s of the [rows, 512] fp32 
 `--series grouped`: instead of the above, MAPPO's `Runner.train()` with `grouped_update` off (the agent loop) and on (MAPPO.train_group: the
 agents in lockstep, one mms_marl_ppo_loss_group call per step) at the same shapes, both with fused_block_update, FusedAdam optimizers
 and fused_factor, from the same rollout, alternating in this process: `train_sequential_ms`, `train_grouped_ms`, the same windows and
-verdict rule (profiles/marl_grouped_update_bench.jsonl).
+verdict rule (profiles/marl_grouped_update_bench.jsonl), and a third route in the same rounds: `grouped_update` with `fused_head_update`
+(heads.update_heads: the 2 x agents output heads of a step in one mms_marl_heads_fwd_group call, their backward in one
+mms_marl_heads_grad_group call), `train_grouped_heads_ms`, with its windows against the agent loop's and against the grouped route's
+(profiles/marl_head_update_bench.jsonl).  `--trace ROUTE --trains N` (with `--series grouped`): only that route (sequential, grouped,
+grouped_heads) at the first size of --envs, the rollout and N `train()` calls and nothing else -- the run to put under
+`rocprofv3 --kernel-trace --stats`; launches per `train()` are the difference between a run with N = 2 and one with N = 1.
 
 One JSON line per measurement on stdout, appended to --out when given.
 
@@ -52,6 +57,8 @@ def main():
     ap.add_argument("--kernel-rows", type=int, default=32768)
     ap.add_argument("--out", default="")
     ap.add_argument("--series", default="factor", choices=("factor", "grouped"))
+    ap.add_argument("--trace", default="", choices=("", "sequential", "grouped", "grouped_heads"), help="--series grouped: only this route, --trains train() calls")
+    ap.add_argument("--trains", type=int, default=1)
     args = ap.parse_args()
     import torch
     import marl_runner_check as rc
@@ -138,16 +145,30 @@ def main():
             env = rc.make_env("cuda", n)
             torch.manual_seed(1)
             over = dict(run_dir=tempfile.mkdtemp(), n_rollout_threads=n, hidden_size=512, ppo_epoch=5, num_env_steps=8 * n, fused_block_update=True)
-            pair = {"sequential": Runner(env, rc.config("mappo", grouped_update=False, **over)), "grouped": Runner(env, rc.config("mappo", grouped_update=True, **over))}
+            routes = {"sequential": dict(grouped_update=False), "grouped": dict(grouped_update=True), "grouped_heads": dict(grouped_update=True, fused_head_update=True)}
+            if args.trace:
+                r = Runner(env, rc.config("mappo", **routes[args.trace], **over))
+                for pol in r.policy:
+                    pol.actor_optimizer, pol.critic_optimizer = FusedAdam.from_torch(pol.actor_optimizer), FusedAdam.from_torch(pol.critic_optimizer)
+                rollout_into(r, [])
+                for _ in range(args.trains):
+                    r.train()
+                torch.cuda.synchronize()
+                return
+            pair = {k: Runner(env, rc.config("mappo", **kw, **over)) for k, kw in routes.items()}
             for r in pair.values():
                 for pol in r.policy:
                     pol.actor_optimizer, pol.critic_optimizer = FusedAdam.from_torch(pol.actor_optimizer), FusedAdam.from_torch(pol.critic_optimizer)
-            rollout_into(pair["sequential"], [pair["grouped"]])
+            rollout_into(pair["sequential"], [pair["grouped"], pair["grouped_heads"]])
             trn = timed({k: r.train for k, r in pair.items()}, args.calls, args.warmup)
             emit({"bench": "marl_grouped_update", "algo": "mappo", "envs": n, "rows": 8 * n, "agents": pair["grouped"].num_agents, "hidden": 512, "ppo_epoch": 5,
                   "num_mini_batch": 1, "fused_block_update": True, "optimizer": "FusedAdam", "rounds": args.rounds, "calls": args.calls,
                   "train_sequential_ms": win(trn["sequential"]), "train_grouped_ms": win(trn["grouped"]),
-                  "train_speedup_median": round(trn["sequential"][0] / trn["grouped"][0], 3), "train_verdict": verdict(trn["sequential"], trn["grouped"])})
+                  "train_speedup_median": round(trn["sequential"][0] / trn["grouped"][0], 3), "train_verdict": verdict(trn["sequential"], trn["grouped"]),
+                  "train_grouped_heads_ms": win(trn["grouped_heads"]), "heads_speedup_median_over_sequential": round(trn["sequential"][0] / trn["grouped_heads"][0], 3),
+                  "heads_verdict_over_sequential": verdict(trn["sequential"], trn["grouped_heads"]),
+                  "heads_speedup_median_over_grouped": round(trn["grouped"][0] / trn["grouped_heads"][0], 3),
+                  "heads_verdict_over_grouped": verdict(trn["grouped"], trn["grouped_heads"])})
             del pair, env
             torch.cuda.empty_cache()
         return
