@@ -433,6 +433,45 @@ int mms_q_heads_backup(int device, int64_t M, int32_t H,
                        const float* reward, const uint8_t* done, const float* logp, float gamma, float alpha,
                        float* backup, void* hip_stream);
 
+/* The critics' loss heads WITH a gradient, forward and backward in one streaming pass: the last layer of one or two critics, the
+ * loss and everything loss.backward() leaves behind that tail.  Replaces, in the reference's SAC update, compute_loss_q (sac.py:367-389:
+ * both critics' Linear(H, 1), two squared-error means and autograd's mirror image) with mode 0, and the critic half of
+ * compute_loss_pi (sac.py:392-403: both critics' Linear(H, 1), torch.min, the mean and their backward) with mode 1; one network and
+ * mode 0 is TD3's / DDPG's critic loss.  d loss / d q is known the moment q is known, so each [M,H] block is read from memory once.
+ *   q_g[i] = mms_q_heads_backup's value for that row, bit for bit (the order of the sum is a function of H alone)
+ *   mode 0 (MSE; target [M] required):  e = (double)q_g[i] - (double)target[i]
+ *       loss = fp32( sum_g (1/M) sum_i e^2 )                dq_g[i] = scale 2 e / M
+ *   mode 1 (policy; target NULL, logp [M] or NULL):  m_i = min_g q_g[i]
+ *       loss = fp32( (1/M) sum_i (alpha logp[i] - m_i) )    (logp NULL: no alpha term)
+ *       dq_g[i] = -scale/M where q_g is the strict minimum, half of that on a tie (torch.min(a, b)'s rule), 0 otherwise; one network:
+ *       dq = -scale/M
+ *   dh_g[i,k] = fp32(dq_g[i]) w_g[k] in fp32 (mode 0: one rounding for dq, one for the product);  fp32( dq_g[i] (double)w_g[k] ) (mode 1)
+ *   dw_g[k] = fp32( sum_i dq_g[i] (double)h_g[i,k] )        db_g = fp32( sum_i dq_g[i] )
+ * dq is a double and stays one in the sums: dw and db carry their own final rounding and the order of the double sum, nothing else
+ * (rounded to fp32 first, every term of mode 0 would carry a rounding of its own, and in mode 1 the representation error of 1/M
+ * would enter dh, dw and db with one sign).
+ * Sums over rows are accumulated in double: per-workgroup partials in the workspace over a partition that is a function of (M, H),
+ * added in one finish pass in a fixed order and rounded once.  No atomics, no memset, at most two launches on hip_stream, no host
+ * synchronisation: bit-identical run to run, and graph-capturable.  A row's q, dq and dh depend on that row, the parameters and the
+ * scalars (M through the stated 1/M), not on where the row sits in the call.
+ * Outputs: loss [1] (required); q0_out, q1_out [M]; dh0, dh1 [M,H]; dw_g [H] and db_g [1] as a pair.  Each of q*_out, dh* and the pair
+ * may be NULL: not computed (frozen critics in the policy step pass dw = db = NULL), and the others keep their bits.
+ * h1 = w1 = b1 = NULL (with q1_out, dh1, dw1, db1 NULL) runs one network.  H a positive multiple of 64 up to MMS_Q_LOSS_MAX_H (a row then
+ * fits a quarter wave's registers), h_g, w_g and dh_g 16-byte aligned, 1 <= M <= 0x7fffffff (M == 0 is a bad argument: a mean of
+ * nothing has no value).  Rows past M are neither read nor written.  Inputs are taken to be finite.
+ * workspace / ws_bytes: mms_sac_heads_grad's convention (NULL stores the bytes needed and returns 0 -- of the arguments only M, H and
+ * whether h1 is given are looked at, nothing is dereferenced; 256-byte aligned; a smaller one is an error; the CPU build needs 0 and
+ * runs on any aligned non-NULL workspace).  The workspace needs no initialisation.
+ * Bad arguments return non-zero with mms_last_error(NULL) and write nothing. */
+#define MMS_Q_LOSS_MAX_H 1024
+int mms_q_heads_loss(int device, int64_t M, int32_t H,
+                     const float* h0, const float* w0, const float* b0,
+                     const float* h1, const float* w1, const float* b1,     /* all NULL: one network */
+                     int32_t mode, const float* target, const float* logp, float alpha, float scale,
+                     float* loss, float* q0_out, float* q1_out,
+                     float* dh0, float* dh1, float* dw0, float* db0, float* dw1, float* db1,
+                     void* workspace, int64_t* ws_bytes, void* hip_stream);
+
 /* One hidden layer of the PPO policy for BOTH networks in one launch (module.py:27-52: nn.Linear + activation, actor and
  * critic of the same shape): y_g = act(x_g @ w_g^T + b_g), g = 0, 1, on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact
  * fp32 products and sums) with bias and activation in the epilogue.  x [M,K], w [N,K] and b [N] in torch's Linear layout,

@@ -43,6 +43,7 @@ import torch.nn as nn
 
 from .... import _lib
 from ..ddpg.module import LAYERS, _Split16Owner, fused_mlp_forward, fused_q_backup, fused_q_forward, mlp, split16_hidden
+from .loss import q_heads_loss
 from ..ppo.loss import _p, _workspace       # (the device's cached, 256-byte aligned workspace: one per process, calls run in stream order)
 
 LOG_STD_MAX = 2
@@ -225,7 +226,9 @@ class SquashedGaussianMLPActor(_Split16Owner, nn.Module):
             logp = (-0.5 * z * z - log_std - _HALF_LOG_2PI - torch.log(1 - torch.tanh(u).pow(2) + epsilon)).sum(dim=-1, keepdim=True)
         return self.act_limit * torch.tanh(u), logp
 
-    def forward(self, obs, deterministic=False, with_logprob=True, epsilon=1e-6):
+    def forward(self, obs, deterministic=False, with_logprob=True, epsilon=1e-6, eps=None):
+        if eps is not None:                # given standard normals (a recorded rsample): torch_forward's statements on them
+            return self.torch_forward(obs, deterministic, with_logprob, epsilon, eps)
         if self._fusable(obs):
             out = self._fused(obs, deterministic, with_logprob, epsilon)
             if out is not None:
@@ -269,6 +272,23 @@ class MLPActorCritic(nn.Module):
         """r + gamma * (1 - d) * (min(q1(o2, a2), q2(o2, a2)) - alpha * logp), no gradient: called on the target copy it is
         sac.py:379-382 in one line -- both critics per launch, the min and the backup inside the last one (ddpg.module.fused_q_backup)."""
         return fused_q_backup([self.q1, self.q2], o2, a2, r, d, gamma, alpha, logp)
+
+    def q_loss(self, o, a, backup):
+        """compute_loss_q's loss for a given Bellman backup (sac.py:370-371, 385-387): mean((q1 - backup)^2) + mean((q2 - backup)^2).
+        The critics' hidden layers run in torch on cat(o, a) (autograd keeps them, their products stay with the library); both last
+        layers, the loss and their backward are one mms_q_heads_loss call (loss.q_heads_loss)."""
+        x = torch.cat([o, a], dim=-1)
+        x = x.reshape(-1, x.shape[-1])
+        return q_heads_loss([q.q[:-2](x) for q in (self.q1, self.q2)], [self.q1.q[-2], self.q2.q[-2]], target=backup, mode="mse")
+
+    def pi_loss(self, o, alpha):
+        """compute_loss_pi (sac.py:392-403): mean(alpha logp_pi - min(q1(o, pi), q2(o, pi))) with pi, logp_pi = self.pi(o).  The actor
+        and the critics' hidden layers as in q_loss; the critics' last layers, the min, the mean and their backward are one
+        mms_q_heads_loss call.  Critics whose parameters do not require a gradient get none computed."""
+        pi, logp = self.pi(o)
+        x = torch.cat([o, pi], dim=-1)
+        x = x.reshape(-1, x.shape[-1])
+        return q_heads_loss([q.q[:-2](x) for q in (self.q1, self.q2)], [self.q1.q[-2], self.q2.q[-2]], logp=logp.reshape(-1), alpha=alpha, mode="pi")
 
     def act(self, obs, deterministic=False):
         with torch.no_grad():

@@ -22,6 +22,7 @@
 #include "../ppo_loss_lane.h"
 #include "../marl_loss_lane.h"
 #include "../q_lane.h"
+#include "../q_loss_lane.h"
 #include "../maddpg_lane.h"
 #include "../sac_lane.h"
 #include "../sac_grad_lane.h"
@@ -341,6 +342,81 @@ MMS_API int mms_q_heads_backup(int device, int64_t M, int32_t H, const float* h0
             backup[row] = mms::q_backup(reward[row], done[row], qm, logp != nullptr, logp ? logp[row] : 0.f, gamma, alpha);
         }
     }
+    return 0;
+}
+// The loss heads with a gradient (include/mms.h: mms_q_heads_loss) over ../q_loss_lane.h: the HIP kernel's partition and its order of
+// every double sum (q_loss_partition, q_loss_slot_sum, the finish pass's segments), OpenMP over the workgroups, so dw, db and the loss
+// are the HIP build's bits wherever q is; q is this build's mms_q_heads_backup chain.  No workspace.
+template <int G>
+static void q_heads_loss_cpu(int64_t M, int H, const float* const* hs, const float* const* ws, const float* const* bs, int mode, const float* target,
+                             const float* logp, float alpha, float scale, float* loss, float* const* qs, float* const* dhs, float* const* dws,
+                             float* const* dbs) {
+    const mms::QLossPartition p = mms::q_loss_partition(M, H);
+    const int NC = mms::q_loss_columns(G, H);
+    std::vector<double> part((size_t)p.blocks * NC, 0.0);
+#pragma omp parallel for schedule(static)
+    for (int64_t blk = 0; blk < p.blocks; blk++) {
+        std::vector<double> slot((size_t)NC * mms::kQLossRows, 0.0);          // [column][row slot]
+        for (int64_t it = 0; it < p.iters; it++)
+            for (int r = 0; r < mms::kQLossRows; r++) {
+                const int64_t row = (blk * p.iters + it) * mms::kQLossRows + r;
+                if (row >= M) continue;
+                float q[2] = {0.f, 0.f};
+                double dq[2] = {0.0, 0.0};
+                for (int g = 0; g < G; g++) {
+                    float s = 0.f;
+                    for (int k = 0; k < H; k++) s = fmaf(hs[g][row * (int64_t)H + k], ws[g][k], s);
+                    q[g] = mms::q_value(s, bs[g][0]);
+                    if (qs[g]) qs[g][row] = q[g];
+                }
+                const double term = mms::q_loss_row<G>(mode, q, mode == 0 ? target[row] : 0.f, logp != nullptr, logp ? logp[row] : 0.f, alpha, scale,
+                                                       (double)M, dq);
+                slot[(size_t)(NC - 1) * mms::kQLossRows + r] += term;
+                for (int g = 0; g < G; g++) {
+                    const float* x = hs[g] + row * (int64_t)H;
+                    if (dhs[g])
+                        for (int k = 0; k < H; k++) dhs[g][row * (int64_t)H + k] = mms::q_loss_dh(mode, dq[g], ws[g][k]);
+                    if (dws[g]) {
+                        double* c = slot.data() + (size_t)g * (H + 1) * mms::kQLossRows;
+                        const double d = dq[g];
+                        for (int k = 0; k < H; k++) c[(size_t)k * mms::kQLossRows + r] += d * (double)x[k];
+                        c[(size_t)H * mms::kQLossRows + r] += d;
+                    }
+                }
+            }
+        for (int c = 0; c < NC; c++) part[(size_t)blk * NC + c] = mms::q_loss_slot_sum(slot.data() + (size_t)c * mms::kQLossRows);
+    }
+    for (int c = 0; c < NC; c++) {
+        float* dst = nullptr;
+        if (c == NC - 1) dst = loss;
+        else if (dws[c / (H + 1)]) dst = c % (H + 1) < H ? dws[c / (H + 1)] + c % (H + 1) : dbs[c / (H + 1)];
+        if (!dst) continue;
+        double t = 0.0;
+        for (int seg = 0; seg < mms::kQLossSegments; seg++) {
+            const int64_t first = seg * p.per_segment, last = first + p.per_segment < p.blocks ? first + p.per_segment : p.blocks;
+            t += first < last ? mms::q_loss_segment_sum(part.data() + c, NC, first, last) : 0.0;
+        }
+        *dst = c == NC - 1 ? (float)(t / (double)M) : (float)t;
+    }
+}
+MMS_API int mms_q_heads_loss(int device, int64_t M, int32_t H, const float* h0, const float* w0, const float* b0, const float* h1, const float* w1,
+                             const float* b1, int32_t mode, const float* target, const float* logp, float alpha, float scale, float* loss,
+                             float* q0_out, float* q1_out, float* dh0, float* dh1, float* dw0, float* db0, float* dw1, float* db1, void* workspace,
+                             int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_q_heads_loss(M, H, h0, w0, b0, h1, w1, b1, mode, target, loss, q1_out, dh0, dh1, dw0, db0, dw1, db1, workspace, ws_bytes, 0))) return 1;
+    if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query
+    const float* hs[2] = {h0, h1};
+    const float* ws[2] = {w0, w1};
+    const float* bs[2] = {b0, b1};
+    float* qs[2] = {q0_out, q1_out};
+    float* dhs[2] = {dh0, dh1};
+    float* dws[2] = {dw0, dw1};
+    float* dbs[2] = {db0, db1};
+    if (mode == 1) target = nullptr;
+    else logp = nullptr;
+    if (h1) q_heads_loss_cpu<2>(M, H, hs, ws, bs, mode, target, logp, alpha, scale, loss, qs, dhs, dws, dbs);
+    else q_heads_loss_cpu<1>(M, H, hs, ws, bs, mode, target, logp, alpha, scale, loss, qs, dhs, dws, dbs);
     return 0;
 }
 MMS_API int mms_det_heads_act_group(int device, int32_t groups, int64_t M, int32_t H, int32_t A, int32_t agent0, const float* const* h,

@@ -46,6 +46,9 @@ hipError_t launch_param_step(const ParamArgs&, hipStream_t);
 int64_t sac_grad_ws_bytes(int64_t, int);
 hipError_t launch_sac_heads_grad(int64_t, int, float, float, const float*, const float*, const float*, const float*, const float*, float*, float*, void*,
                                  hipStream_t);
+int64_t q_loss_ws_bytes(int64_t, int, int);
+hipError_t launch_q_heads_loss(int, int64_t, int, const float* const*, const float* const*, const float* const*, int, const float*, const float*, float,
+                               float, float*, float* const*, float* const*, float* const*, float* const*, void*, hipStream_t);
 struct MlpPlan;
 }  // namespace mms
 
@@ -375,6 +378,29 @@ __attribute__((visibility("default"))) int mms_q_heads_backup(int device, int64_
     const float* b[2] = {b0, b1};
     float* q[2] = {q0_out, q1_out};
     MMS_FREE(mms::launch_q_heads_backup(h1 ? 2 : 1, M, H, h, w, b, q, reward, done, backup ? logp : nullptr, gamma, alpha, backup, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_q_heads_loss(int device, int64_t M, int32_t H, const float* h0, const float* w0, const float* b0,
+                                                            const float* h1, const float* w1, const float* b1, int32_t mode, const float* target,
+                                                            const float* logp, float alpha, float scale, float* loss, float* q0_out,
+                                                            float* q1_out, float* dh0, float* dh1, float* dw0, float* db0, float* dw1, float* db1,
+                                                            void* workspace, int64_t* ws_bytes, void* s) {
+    MMS_DEV(device)
+    const int G = h1 ? 2 : 1;
+    const bool shapes = M >= 1 && M <= 0x7fffffff && H > 0 && H % 64 == 0 && H <= MMS_Q_LOSS_MAX_H;
+    const int64_t need = shapes ? mms::q_loss_ws_bytes(M, H, G) : 0;
+    if (refused(check_q_heads_loss(M, H, h0, w0, b0, h1, w1, b1, mode, target, loss, q1_out, dh0, dh1, dw0, db0, dw1, db1, workspace, ws_bytes, need)))
+        return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }                // the size query
+    const float* h[2] = {h0, h1};
+    const float* w[2] = {w0, w1};
+    const float* b[2] = {b0, b1};
+    float* q[2] = {q0_out, q1_out};
+    float* dh[2] = {dh0, dh1};
+    float* dw[2] = {dw0, dw1};
+    float* db[2] = {db0, db1};
+    MMS_FREE(mms::launch_q_heads_loss(G, M, H, h, w, b, mode, target, logp, alpha, scale, loss, q, dh, dw, db, workspace, (hipStream_t)s));
     return 0;
 }
 

@@ -385,6 +385,30 @@ static inline std::string check_q_heads_backup(int64_t M, int32_t H, const float
     return {};
 }
 
+// mms_q_heads_loss: everything before any work (workspace NULL is the size query: nothing else is read)
+static inline std::string check_q_heads_loss(int64_t M, int32_t H, const float* h0, const float* w0, const float* b0, const float* h1, const float* w1,
+                                             const float* b1, int32_t mode, const float* target, const float* loss, const float* q1_out,
+                                             const float* dh0, const float* dh1, const float* dw0, const float* db0, const float* dw1, const float* db1,
+                                             const void* workspace, const int64_t* ws_bytes, int64_t need) {
+    if (!ws_bytes) return "mms_q_heads_loss: ws_bytes required";
+    if (M < 1 || M > 0x7fffffff) return "mms_q_heads_loss: M must be in 1..2147483647 (a mean of no rows has no value)";
+    if (H <= 0 || (H % 64) != 0 || H > MMS_Q_LOSS_MAX_H)
+        return "mms_q_heads_loss: H must be a positive multiple of 64 up to " + std::to_string(MMS_Q_LOSS_MAX_H);
+    if (mode != 0 && mode != 1) return "mms_q_heads_loss: mode must be 0 (MSE) or 1 (policy)";
+    if (!workspace) return {};
+    if (!h0 || !w0 || !b0 || !loss) return "mms_q_heads_loss: null pointer (h0, w0, b0 and loss are required)";
+    if ((h1 || w1 || b1) && !(h1 && w1 && b1)) return "mms_q_heads_loss: the second network needs h1, w1 and b1 (or all NULL: one network)";
+    if (!h1 && (q1_out || dh1 || dw1 || db1)) return "mms_q_heads_loss: an output of the second network without h1, w1 and b1";
+    if (mode == 0 && !target) return "mms_q_heads_loss: mode 0 needs target";
+    if (mode == 1 && target) return "mms_q_heads_loss: mode 1 takes no target";
+    if ((!dw0) != (!db0) || (!dw1) != (!db1)) return "mms_q_heads_loss: dw_g and db_g are given together or both NULL";
+    if ((addr(h0) | addr(w0) | addr(h1) | addr(w1) | addr(dh0) | addr(dh1)) & 15)
+        return "mms_q_heads_loss: hidden activations, weights and dh must be 16-byte aligned";
+    if (*ws_bytes < need) return "mms_q_heads_loss: workspace too small (" + std::to_string(*ws_bytes) + " bytes, needs " + std::to_string(need) + ")";
+    if (addr(workspace) & 255) return "mms_q_heads_loss: workspace must be 256-byte aligned";
+    return {};
+}
+
 static inline std::string check_det_heads_act_group(int32_t groups, int64_t M, int32_t H, int32_t A, int32_t agent0, const float* const* h,
                                                     const float* const* w, const float* const* b, const float* act_limit, float sigma,
                                                     const int64_t* counters, float* const* act_out, int64_t act_pitch, const float* joint_out,

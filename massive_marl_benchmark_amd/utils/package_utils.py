@@ -2,8 +2,9 @@
 train_customize.py:8-13) -- and `train(argv)`, the wiring of train.py:20-96, both without isaacgym: flags (get_args), YAML
 (load_cfg), seeds, then parse_task builds the task on this engine and wraps it in VecTaskPython / MultiVecTaskPython.
 
-The learners themselves are the reference's (callers of the hot path: out of scope); `train` imports them
+The learners `train` starts are the reference's (callers of the hot path: out of scope); `train` imports them
 from the caller's checkout of the reference (the `agents` package on PYTHONPATH) and hands them the env exactly as train.py does.
+(SAC also lives here -- `algorithms.rl.sac.SAC` -- and binds to `process_sarl`'s SAC branch by one import: INTEGRATION.md.)
 tests/golden/run_reference_learners.py runs `PPO.run` and `Runner.run` that way in the build container."""
 from .config import MARL_ALGOS, get_args, load_cfg, parse_sim_params, set_np_formatting, set_seed
 from .parse_task import parse_task
