@@ -5,7 +5,15 @@ the gates.
 Gates.  Deterministic actions against float64: e <= 2 e_ref + 1e-6 with e = max |a - a64| / (act_limit (1 + s)), s the row scale
 sum_k |h_k w_jk| + |b_j| (q_check.f64_q's) and e_ref the same measure for torch's fp32 `act_limit * tanh(linear)` on the same device.
 The drawn normal is recovered as z' = (a_noisy - a_det) / sigma in float64: a_noisy is a + sigma z rounded once (fused) or twice, so
-|z' - z| <= 2^-23 (|a| + sigma |z|) / sigma <= 2^-23 (act_limit / sigma + |z|); the gate is twice that."""
+|z' - z| <= 2^-23 (|a| + sigma |z|) / sigma <= 2^-23 (act_limit / sigma + |z|); the gate is twice that.
+
+The launcher's rule, restated (csrc/maddpg_kernels.hip: launch_det_heads_act): `expected_kernel`.  REACHABLE is every
+det_heads_act_kernel<NCT, WAVES> with NCT = ceil(A / 16) in 1..8 (A in 1..128, mms_host.h: check_det_heads_act_group) and WAVES in
+{1, 2, 4, 8} (H any positive multiple of 64: the check sets no maximum), 32 kernels: the launcher's `switch` instantiates exactly
+these and no A demotes WAVES.  HEAD_CASES + NEW_HEAD_CASES reaches all of them (test_maddpg.py: test_head_table_reaches_every_kernel).
+Q_REACHABLE is the grouped Q kernel with each part of its k-loop (q_check.expected_path); Q_CASES + NEW_Q_CASES reaches it.
+
+Operands live inside NaN-filled allocations and destinations between guard floats (q_check.poisoned, q_check.Guarded)."""
 import ctypes
 
 import numpy as np
@@ -18,6 +26,57 @@ SENTINEL = 7.0
 HEAD_CASES = [(1, 64, 1, 1, 0), (7, 64, 3, 2, 0), (16, 128, 8, 3, 0), (17, 512, 8, 10, 0), (333, 512, 16, 3, 2), (333, 256, 17, 2, 0),
               (100, 1024, 24, 32, 0), (1000, 512, 8, 10, 5)]                  # (M, H, A, groups, agent0)
 Q_CASES = [(1, 64, 1), (7, 256, 3), (17, 512, 10), (1000, 256, 32), (37, 4096, 2)]    # (M, H, groups)
+MAX_A = 128                  # mms_host.h: check_det_heads_act_group (A in 1..128; H a positive multiple of 64, no maximum)
+REACHABLE = {(nct, waves) for nct in range(1, MAX_A // 16 + 1) for waves in (1, 2, 4, 8)}
+Q_REACHABLE = {("grouped", path) for path in qc.PATHS}
+
+
+def expected_kernel(H, A):
+    """launch_det_heads_act's choice (nct, waves) of det_heads_act_kernel<NCT, WAVES>: one 16-column tile per 16 actions, the most waves
+    that leave every wave a multiple of 64 k.  The launcher then halves waves while the partial sums (waves x 16 rows x 16 nct floats)
+    exceed 64 KB of LDS: for nct <= 8 they never do -- the largest, (8, 8), is 8 x 16 x 128 x 4 = 65536 bytes, exactly 64 KB, and the
+    comparison is `>` -- so that loop is unreachable through the entry and no (H, A) is demoted."""
+    assert 1 <= A <= MAX_A and H > 0 and H % 64 == 0
+    nct = (A + 15) // 16
+    waves = 8 if H % 512 == 0 else 4 if H % 256 == 0 else 2 if H % 128 == 0 else 1
+    assert waves * 16 * nct * 16 * 4 <= 64 * 1024
+    return nct, waves
+
+
+def _new_head_cases():
+    """One case per kernel at M in {17, 33} (two or three 16-row blocks, the last one partial).  Per NCT = t the four WAVES alternate
+    between A = 16 t (a full last column tile) and A = 16 (t - 1) + 1 (one live column in it); groups go round 1, 3, 10 and agent0
+    alternates between 0 and 2 (the joint row's column offset).  Then H = 192, 384, 768 (multiples of 64 that are no power of two: 1, 2,
+    4 waves) and a single row."""
+    cases, n = [], 0
+    for t in range(1, 9):
+        for wi, H in enumerate((64, 128, 256, 512)):
+            A = 16 * t if (t + wi) % 2 == 0 else 16 * (t - 1) + 1
+            cases.append((17 if n % 2 == 0 else 33, H, A, (1, 3, 10)[n % 3], (0, 2)[(n // 2) % 2]))
+            n += 1
+    return cases + [(33, 192, 40, 3, 2), (17, 384, 97, 1, 0), (33, 768, 113, 3, 0), (1, 512, 128, 3, 2)]
+
+
+NEW_HEAD_CASES = _new_head_cases()
+# nj = 1, 3 (remainder), 4 (unrolled), 5, 7, 9 (both), each with one group and with three, and a single row
+NEW_Q_CASES = [(17 if (i + G) % 2 else 33, H, G) for i, H in enumerate((64, 192, 256, 320, 448, 576)) for G in (1, 3)] + [(1, 448, 3)]
+
+
+def head_coverage(cases=None):
+    return {expected_kernel(H, A) for _, H, A, _, _ in (HEAD_CASES + NEW_HEAD_CASES if cases is None else cases)}
+
+
+def q_coverage(cases=None):
+    return {("grouped", qc.expected_path(H)) for _, H, _ in (Q_CASES + NEW_Q_CASES if cases is None else cases)}
+
+
+def noise_case(case):
+    """`case` with agent0, then groups, cut down until the joint row has at most 128 columns (mms_ppo_act, the source of the expected
+    normals, draws for columns 0..127): the kernel is the same, it follows from H and A."""
+    M, H, A, G, agent0 = case
+    agent0 = min(agent0, max(0, 128 // A - 1))
+    return M, H, A, min(G, 128 // A - agent0), agent0
+
 
 vp = ctypes.c_void_p
 
@@ -42,7 +101,7 @@ def head_problem(M, H, A, groups, seed=0, device="cpu"):
     hs = [torch.nn.functional.elu(torch.randn(max(M, 1), H, generator=g))[:M].contiguous() for _ in range(groups)]
     ws = [torch.randn(A, H, generator=g) * H ** -0.5 for _ in range(groups)]
     bs = [torch.randn(A, generator=g) * 0.1 for _ in range(groups)]
-    to = lambda t: t.to(device)
+    to = lambda t: qc.poisoned(t.to(device))
     return dict(h=[to(t) for t in hs], w=[to(t) for t in ws], b=[to(t) for t in bs], limit=[1.0 + 0.25 * i for i in range(groups)])
 
 
@@ -57,32 +116,41 @@ def head_raw(L, device, stream, groups, M, H, A, agent0, h, w, b, limit, sigma, 
 def head_run(L, device, stream, pr, *, agent0=0, sigma=0.0, seed=0, counters=None, row_offset=0, with_act=True, with_joint=True, act_pad=0,
              joint_pad=0, rows=None, tail=3):
     """One call on the first `rows` rows of `pr` into SENTINEL-filled destinations of M + tail rows with padded pitches.  Returns
-    (act buffers [M + tail, A + act_pad] or None, joint buffer [M + tail, (agent0 + groups) A + joint_pad] or None)."""
+    (act buffers [M + tail, A + act_pad] or None, joint buffer [M + tail, (agent0 + groups) A + joint_pad] or None).  Every destination
+    sits between guard floats, which the call must leave alone."""
     G = len(pr["h"])
     M, H = pr["h"][0].shape
     A = pr["w"][0].shape[0]
     M = M if rows is None else rows
     dev = pr["h"][0].device
     ap, jp = A + act_pad, (agent0 + G) * A + joint_pad
-    acts = [torch.full((M + tail, ap), SENTINEL, device=dev) for _ in range(G)] if with_act else None
-    joint = torch.full((M + tail, jp), SENTINEL, device=dev) if with_joint else None
+    guards = ([qc.Guarded((M + tail, ap), dev) for _ in range(G)] if with_act else []) + ([qc.Guarded((M + tail, jp), dev)] if with_joint else [])
+    acts = [x.view for x in guards[:G]] if with_act else None
+    joint = guards[-1].view if with_joint else None
     rc = head_raw(L, device, stream, G, M, H, A, agent0, pr["h"], pr["w"], pr["b"], pr["limit"], sigma, seed, counters, row_offset, acts, ap, joint, jp)
     _lib.check(rc, None, "mms_det_heads_act_group", L)
     sync(pr["h"][0])
+    assert all(x.intact() for x in guards), "a float outside a destination was written"
     return acts, joint
 
 
-def head_f64(pr, g):
-    """a_g in float64 and the row scale s of the pre-activation."""
+def head_f64(pr, g, mutation=None):
+    """a_g in float64 and the row scale s of the pre-activation.  `mutation` corrupts a_g (not s): "tile" leaves the weight rows of the
+    last 16-column tile out, "last" the last live column's alone -- what a kernel that loses that tile, or that column, would store."""
     h, w, b = (t.detach().double() for t in (pr["h"][g], pr["w"][g], pr["b"][g]))
-    pre = h @ w.T + b
     s = h.abs() @ w.abs().T + b.abs()
+    if mutation is not None:
+        w = w.clone()
+        w[{"tile": 16 * ((w.shape[0] - 1) // 16), "last": w.shape[0] - 1}[mutation]:] = 0.0
+    pre = h @ w.T + b
     return (pr["limit"][g] * torch.tanh(pre)).cpu().numpy(), s.cpu().numpy()
 
 
-def check_head_case(L, device, stream, case, dev):
+def check_head_case(L, device, stream, case, dev, mutation=None):
     """Deterministic actions against float64 (module docstring), every destination layout: padded pitches and each destination NULL in
-    turn give the same bits; nothing is written past M, past A or between pitched rows."""
+    turn give the same bits; nothing is written past M, past A or between pitched rows.  With `mutation` the float64 actions are
+    corrupted (head_f64; torch's fp32 is still measured against the true ones), the gate is not asserted and the worst
+    e / (2 e_ref + 1e-6) is returned."""
     M, H, A, G, agent0 = case
     pr = head_problem(M, H, A, G, seed=1, device=dev)
     acts, joint = head_run(L, device, stream, pr, agent0=agent0, act_pad=3, joint_pad=5)
@@ -90,14 +158,19 @@ def check_head_case(L, device, stream, case, dev):
     for g in range(G):
         a64, s = head_f64(pr, g)
         got = acts[g][:M, :A]
-        e = float((np.abs(got.double().cpu().numpy() - a64) / (pr["limit"][g] * (1 + s))).max())
+        e = float((np.abs(got.double().cpu().numpy() - head_f64(pr, g, mutation)[0]) / (pr["limit"][g] * (1 + s))).max())
         ref = pr["limit"][g] * torch.tanh(torch.nn.functional.linear(pr["h"][g], pr["w"][g], pr["b"][g]))
         et = float((np.abs(ref.double().cpu().numpy() - a64) / (pr["limit"][g] * (1 + s))).max())
         worst = max(worst, e / (2 * et + 1e-6))
+        if mutation is not None:
+            continue
         assert e <= 2 * et + 1e-6, (case, g, e, et)
         assert torch.equal(joint[:M, (agent0 + g) * A:(agent0 + g + 1) * A], got), (case, g)
         assert (acts[g][:M, A:] == SENTINEL).all() and (acts[g][M:] == SENTINEL).all(), (case, g)
-    print("head case %s: worst e / (2 e_ref + 1e-6) = %.3g" % (case, worst))
+    print("head case %s, kernel <%d, %d>: worst e / (2 e_ref + 1e-6) = %.3g" % ((case,) + expected_kernel(H, A) + (worst,)))
+    if mutation is not None:
+        return worst
+    qc.note("cpu" if device < 0 else "gpu", "det_heads_act", "old" if case in HEAD_CASES else "new", worst)
     assert (joint[:, :agent0 * A] == SENTINEL).all() and (joint[:, (agent0 + G) * A:] == SENTINEL).all() and (joint[M:] == SENTINEL).all(), case
     only_act, none = head_run(L, device, stream, pr, agent0=agent0, with_joint=False)
     assert none is None and all(torch.equal(only_act[g][:M], acts[g][:M, :A]) for g in range(G)), case
@@ -242,8 +315,8 @@ def check_head_error_paths(L, device, stream, other_device):
 def q_problem(M, H, G, seed=0, device="cpu"):
     """q_check.problem with G networks and a reward / done pair per group."""
     pr = qc.problem(M, H, G, seed=seed, device=device)
-    pr["r"] = [pr["r"] * (1 + g) for g in range(G)]
-    pr["d"] = [torch.roll(pr["d"], g) for g in range(G)]
+    pr["r"] = [qc.poisoned(pr["r"] * (1 + g)) for g in range(G)]
+    pr["d"] = [qc.poisoned(torch.roll(pr["d"], g)) for g in range(G)]
     return pr
 
 
@@ -258,10 +331,12 @@ def check_q_case(L, device, stream, case, dev, gamma=0.99):
     M, H, G = case
     pr = q_problem(M, H, G, seed=3, device=dev)
     tail = 5
-    q = [torch.full((M + tail,), SENTINEL, device=dev) for _ in range(G)]
-    bk = [torch.full((M + tail,), SENTINEL, device=dev) for _ in range(G)]
+    guards = [qc.Guarded((M + tail,), dev) for _ in range(2 * G)]
+    q = [x.view for x in guards[:G]]
+    bk = [x.view for x in guards[G:]]
     _lib.check(q_raw(L, device, stream, G, M, H, pr["h"], pr["w"], pr["b"], q, pr["r"], pr["d"], gamma, bk), None, "mms_q_heads_backup_group", L)
     sync(q[0])
+    assert all(x.intact() for x in guards), (case, "a float outside a destination was written")
     for g in range(G):
         q1, b1 = torch.full((M,), SENTINEL, device=dev), torch.full((M,), SENTINEL, device=dev)
         _lib.check(qc.call(L, device, stream, M, H, [pr["h"][g]], [pr["w"][g]], [pr["b"][g]], [q1], pr["r"][g], pr["d"][g], None, gamma, 0.0, b1), None,

@@ -6,15 +6,87 @@ test_sac_actor.py::test_cpu_build_against_float64 for the same kind of chain), e
 e = max |q - q64| / s and e_torch the same for torch.nn.functional.linear in fp32 (test_sac_actor_gpu.py::test_kernel_against_float64).
 The backup is compared with the float64 evaluation of the formula FROM THE CALL'S OWN q_out, so that the dot product's error is
 out of it: |backup - backup64| <= 1e-6 (|r| + gamma (|qmin| + alpha |logp|)) -- five roundings of at most 2^-24 each on terms
-bounded by that scale give 3e-7.  gamma and alpha cross the ABI as fp32: the float64 statement uses the fp32-rounded values."""
+bounded by that scale give 3e-7.  gamma and alpha cross the ABI as fp32: the float64 statement uses the fp32-rounded values.
+
+The launcher's rule, restated (csrc/q_kernels.hip: launch_q_heads_backup; csrc/maddpg_kernels.hip: launch_q_heads_backup_group).
+The kernel follows from G alone (q_heads_backup_kernel<1>, <2>; the grouped entry has one), and inside it H alone decides which of
+the k-loop's two parts a row runs: nj = H / 64 chunks, UNROLL = 4 per trip of the unrolled loop, the rest in the remainder loop.
+REACHABLE is {"G1", "G2"} x {"unrolled", "remainder", "both"} over the entry's accepted H (a positive multiple of 64 up to
+MMS_Q_MAX_H = 4096, mms_host.h: check_q_heads_backup): every kernel can run every part, and a dropped chunk or a stale register shows
+only where a call runs both.  CASES reaches all of it (test_q_target.py: test_case_table_reaches_every_path); maddpg_check.py holds
+the grouped kernel's.
+
+Operands live inside NaN-filled allocations (`poisoned`; done: 255-filled) and destinations between guard floats (`Guarded`): a
+read past an operand shows as NaN in a result (a terminal row for done), a write outside a destination as a broken guard."""
 import ctypes
 
 import numpy as np
 import torch
 
+import parity
 from massive_marl_benchmark_amd import _lib
 
 SENTINEL = 7.0
+POISON = 64                  # elements on either side of an operand or a destination (64 floats: the operand stays 16-byte aligned)
+Q_MAX_H = 4096               # mms_host.h: check_q_heads_backup, check_q_heads_backup_group (MMS_Q_MAX_H)
+UNROLL = 4                   # q_kernels.hip: kQUnroll; maddpg_kernels.hip: kQgUnroll
+PATHS = ("unrolled", "remainder", "both")
+REACHABLE = {("G%d" % G, path) for G in (1, 2) for path in PATHS}
+# (M, H, G): nj = 1, 3 (remainder), 4 (unrolled), 5, 7 (one trip and a rest), 9 (two trips and a rest); two or three 16-row passes, the
+# last one partial, and one single row
+CASES = [(17 if (i + G) % 2 else 33, H, G) for i, H in enumerate((64, 192, 256, 320, 448, 576)) for G in (1, 2)] + [(1, 320, 2)]
+# the shapes test_q_target.py and test_q_target_gpu.py ran before CASES: every one runs ONE part of the loop
+OLD_H = (64, 128, 192, 256, 1024, 4096)
+# the launchers of the off-policy tails read nothing from the environment; these select kernels elsewhere in the library, and a run
+# with one of them set is no run of the shipped dispatch (the GPU test files refuse it, as test_linear_act_gpu.py does)
+DISPATCH_ENV = ("MMS_HEAD_RT", "MMS_SPLIT_MT", "MMS_LINEAR_SMALL_MAX", "MMS_LINEAR_TALL_TILES", "MMS_LINEAR_GENERIC")
+WORST = {}
+
+
+def expected_path(H):
+    """Which parts of the k-loop a live row runs at this H (every kernel of the family has the same loop): `for (; j + 4 <= nj; j += 4)`
+    then `for (; j < nj; j++)`."""
+    assert H > 0 and H % 64 == 0 and H <= Q_MAX_H
+    trips, rest = divmod(H // 64, UNROLL)
+    return "remainder" if trips == 0 else "unrolled" if rest == 0 else "both"
+
+
+def coverage(cases=None):
+    return {("G%d" % G, expected_path(H)) for _, H, G in (CASES if cases is None else cases)}
+
+
+def note(where, family, kind, ratio):
+    """Record (parity.record) the worst error / gate of a family over its `kind` ("old" or "new") cases so far."""
+    key = "%s/%s_error_over_gate" % (where, family)
+    d = WORST.setdefault(key, {"old_cases": 0.0, "new_cases": 0.0})
+    d[kind + "_cases"] = max(d[kind + "_cases"], float(ratio))
+    parity.record(key, **d)
+
+
+def poisoned(t, pad=POISON):
+    """`t` in the middle of a NaN-filled (integers: 255-filled) allocation on its device, `pad` elements on either side."""
+    fill = float("nan") if t.is_floating_point() else 255
+    full = torch.full((t.numel() + 2 * pad,), fill, dtype=t.dtype, device=t.device)
+    view = full[pad:pad + t.numel()].view(t.shape)
+    view.copy_(t)
+    return view
+
+
+class Guarded:
+    """A destination of `shape` filled with `fill` between `pad` guard floats on either side."""
+    GUARD = -3.0
+
+    def __init__(self, shape, dev, fill=SENTINEL, pad=POISON):
+        n = 1
+        for v in shape:
+            n *= int(v)
+        self.pad = pad
+        self.full = torch.full((n + 2 * pad,), self.GUARD, device=dev)
+        self.view = self.full[pad:pad + n].view(*shape)
+        self.view.fill_(fill)
+
+    def intact(self):
+        return bool((self.full[:self.pad] == self.GUARD).all()) and bool((self.full[self.full.numel() - self.pad:] == self.GUARD).all())
 
 
 def problem(M, H, G, seed=0, device="cpu"):
@@ -29,7 +101,7 @@ def problem(M, H, G, seed=0, device="cpu"):
     if M >= 2:
         d[0], d[1] = 1, 0
     logp = torch.randn(M, generator=g) * 2 - 3
-    to = lambda t: t.to(device)
+    to = lambda t: poisoned(t.to(device))
     return dict(h=[to(t) for t in hs], w=[to(t) for t in ws], b=[to(t) for t in bs], r=to(r), d=to(d), logp=to(logp))
 
 
@@ -51,19 +123,26 @@ def run(L, device, stream, pr, *, G=None, with_q=True, with_backup=True, with_lo
     M, H = pr["h"][0].shape
     M = M if rows is None else rows
     dev = pr["h"][0].device
-    q = [torch.full((M,), SENTINEL, device=dev) if with_q else None for _ in range(G)]
-    backup = torch.full((M,), SENTINEL, device=dev) if with_backup else None
+    guards = [Guarded((M,), dev) for _ in range(G + 1)]
+    q = [guards[g].view if with_q else None for g in range(G)]
+    backup = guards[G].view if with_backup else None
     use = with_backup
     rc = call(L, device, stream, M, H, pr["h"][:G], pr["w"][:G], pr["b"][:G], q, pr["r"] if use else None, pr["d"] if use else None,
               pr["logp"] if use and with_logp else None, gamma, alpha, backup)
     _lib.check(rc, None, "mms_q_heads_backup", L)
+    assert all(x.intact() for x in guards), "a float outside a destination was written"
     return q, backup
 
 
-def f64_q(pr, g):
-    """q_g in float64 and the row scale s."""
+def f64_q(pr, g, mutation=None):
+    """q_g in float64 and the row scale s.  `mutation` corrupts q (not s): "chunk" leaves the last 64 k out of the product, "last" the
+    last k alone -- what a kernel that drops its last chunk, or its last element, would compute."""
     h, w, b = (t.detach().double() for t in (pr["h"][g], pr["w"][g], pr["b"][g]))           # (on the tensors' own device: [65536, 1024] rows)
-    return (h @ w[0] + b[0]).cpu().numpy(), (h.abs() @ w[0].abs() + b[0].abs()).cpu().numpy()
+    s = (h.abs() @ w[0].abs() + b[0].abs()).cpu().numpy()
+    if mutation is not None:
+        w = w.clone()
+        w[0, {"chunk": w.shape[1] - 64, "last": w.shape[1] - 1}[mutation]:] = 0.0
+    return (h @ w[0] + b[0]).cpu().numpy(), s
 
 
 def f64_backup(q, pr, with_logp, gamma, alpha, rows=None):
@@ -88,6 +167,34 @@ def check_backup(q, backup, pr, with_logp, gamma, alpha, what="", extra=0.0):
     assert (err <= gate + extra).all(), (what, float((err / (gate + extra + 1e-30)).max()))
     done = np.asarray(pr["d"].cpu())[:backup.numel()] != 0
     assert torch.equal(backup.cpu()[done], pr["r"].cpu()[:backup.numel()][done]), what       # r + gamma * 0 * x
+
+
+def check_case(L, device, stream, dev, M, H, G, mutation=None, kind="new"):
+    """One shape on either build: q against float64 by the build's own gate (module docstring: 1e-6 s on the CPU build, the device's
+    2 e_torch + 1e-6), then check_backup, with and without logp.  Returns the worst e / gate.  With `mutation` the float64 q is
+    corrupted (f64_q; torch's fp32 is still measured against the true one) and nothing is asserted: the caller judges the ratio."""
+    pr = problem(M, H, G, seed=1, device=dev)
+    where = "cpu" if device < 0 else "gpu"
+    worst = 0.0
+    for with_logp in (True, False):
+        q, backup = run(L, device, stream, pr, with_logp=with_logp)
+        if device >= 0:
+            torch.cuda.synchronize()
+        for g in range(G):
+            q64, s = f64_q(pr, g)
+            gate = 1e-6
+            if device >= 0:
+                t = torch.nn.functional.linear(pr["h"][g], pr["w"][g], pr["b"][g])[:, 0].double().cpu().numpy()
+                gate = 2 * float((np.abs(t - q64) / s).max()) + 1e-6
+            e = float((np.abs(q[g].double().cpu().numpy() - f64_q(pr, g, mutation)[0]) / s).max())
+            print("%s M %d H %d G %d g %d (%s): e = %.3g, gate = %.3g" % (where, M, H, G, g, expected_path(H), e, gate))
+            worst = max(worst, e / gate)
+            assert mutation is not None or e <= gate, (M, H, G, g, e, gate)
+        if mutation is None:
+            check_backup(q, backup, pr, with_logp, 0.99, 0.2, "%s M %d H %d G %d logp %d" % (where, M, H, G, with_logp))
+    if mutation is None:
+        note(where, "q_heads_backup", kind, worst)
+    return worst
 
 
 def exact_properties(L, device, stream, pr1000):

@@ -18,18 +18,48 @@ CALL'S OWN q_out, so the dot product's error is out of it:
 The HIP build and the CPU build share the partition and the order of every double sum (q_loss_lane.h), so on inputs whose dot
 product is exact in fp32 (small dyadic rationals: `exact_problem`) q is equal on both builds and dq, dh, dw, db and the loss agree
 BIT FOR BIT; on general inputs q itself differs between the builds (one fmaf chain against sixteen and a butterfly, as for
-mms_q_heads_backup), so that comparison is made on the exact problem."""
+mms_q_heads_backup), so that comparison is made on the exact problem.
+
+The launcher's rule, restated (csrc/q_loss_kernels.hip: launch_main): `expected_kernel`.  REACHABLE is every q_heads_loss_kernel<G, NJ>,
+G in {1, 2} and NJ in {1, 2, 4, 8, 16} the power of two that holds nj = H / 64 chunks (H a positive multiple of 64 up to
+MMS_Q_LOSS_MAX_H = 1024, mms_host.h: check_q_heads_loss), each with every chunk live (nj = NJ) and, where some H gives it (NJ >= 4),
+with chunks guarded out by `j < nj`: ten kernels, sixteen entries.  NEW_SHAPES reaches all of them (test_q_loss.py:
+test_shape_table_reaches_every_kernel).  Operands live inside NaN-filled allocations (q_check.poisoned)."""
 import ctypes
 import itertools
 
 import numpy as np
 import torch
 
+import q_check as qc
 from massive_marl_benchmark_amd import _lib
 
 SENTINEL = 7.0
 PAD = 8                      # canary floats on each side of a destination (32 bytes: dh stays 16-byte aligned)
 SHAPES = [(1, 64, 1), (15, 64, 2), (17, 192, 2), (389, 1024, 2), (2100, 128, 2)]
+Q_LOSS_MAX_H = 1024          # mms_host.h: check_q_heads_loss (MMS_Q_LOSS_MAX_H)
+
+
+def expected_kernel(G, H):
+    """launch_main<G>'s choice (G, NJ, nj) of q_heads_loss_kernel<G, NJ>: NJ the least of 1, 2, 4, 8, 16 that is >= nj = H / 64."""
+    assert G in (1, 2) and H > 0 and H % 64 == 0 and H <= Q_LOSS_MAX_H
+    nj = H // 64
+    return G, next(n for n in (1, 2, 4, 8, 16) if nj <= n), nj
+
+
+def _entry(G, H):
+    G, NJ, nj = expected_kernel(G, H)
+    return G, NJ, "full" if nj == NJ else "guarded"
+
+
+REACHABLE = {_entry(G, H) for G in (1, 2) for H in range(64, Q_LOSS_MAX_H + 1, 64)}
+# (M, H, G): nj = 1 <1>, 2 <2>, 3 and 4 <4>, 5 and 8 <8>, 9 and 16 <16> for either G at M in {17, 33} (two or three 16-row slots, the
+# last one partial), and a single row
+NEW_SHAPES = [(17 if (i + G) % 2 else 33, H, G) for i, H in enumerate((64, 128, 192, 256, 320, 512, 576, 1024)) for G in (1, 2)] + [(1, 320, 2)]
+
+
+def coverage(shapes=None):
+    return {_entry(G, H) for _, H, G in (NEW_SHAPES if shapes is None else shapes)}
 MULTI = (16 * 512 * 2 + 5, 64, 2)       # more than 512 row groups: a workgroup walks several, the finish pass adds hundreds of partials
 
 
@@ -48,7 +78,7 @@ def problem(M, H, G, seed=0, device="cpu", tie=False):
         hs[1], ws[1], bs[1] = hs[0].clone(), ws[0].clone(), bs[0].clone()
     target = torch.randn(M, generator=g)
     logp = torch.randn(M, generator=g) * 2 - 3
-    to = lambda t: t.to(device).contiguous()
+    to = lambda t: qc.poisoned(t.to(device).contiguous())
     return dict(h=[to(t) for t in hs], w=[to(t) for t in ws], b=[to(t) for t in bs], target=to(target), logp=to(logp))
 
 
@@ -173,7 +203,12 @@ def f64_statement(out, pr, mode, with_logp, alpha, scale):
     return dq, loss_terms
 
 
-def check_against_float64(out, pr, mode, with_logp=True, alpha=0.2, scale=1.0, what=""):
+def check_against_float64(out, pr, mode, with_logp=True, alpha=0.2, scale=1.0, what="", mutation=None):
+    """Every output but q against the float64 statement (module docstring); returns each one's worst error / gate.  `mutation` corrupts
+    the statement's h and w -- "chunk": the last 64 k are zero, "last": the last k alone, what a kernel that drops its last chunk or
+    element would leave in dh and dw -- and nothing is asserted: the caller judges the ratios."""
+    if mutation is not None:
+        return _ratios_against_mutated(out, pr, mode, with_logp, alpha, scale, mutation)
     G, M, H = out.G, out.M, out.H
     dq64, loss_terms = f64_statement(out, pr, mode, with_logp, alpha, scale)
     u = 2.0 ** -24
@@ -215,6 +250,26 @@ def check_against_float64(out, pr, mode, with_logp=True, alpha=0.2, scale=1.0, w
     return worst
 
 
+def _ratios_against_mutated(out, pr, mode, with_logp, alpha, scale, mutation):
+    """check_against_float64's dh and dw gates, unasserted, against h and w without their last chunk or element."""
+    G, M, H = out.G, out.M, out.H
+    dq64, _ = f64_statement(out, pr, mode, with_logp, alpha, scale)
+    cut = {"chunk": H - 64, "last": H - 1}[mutation]
+    u = 2.0 ** -24
+    worst = {}
+    for g in range(G):
+        w = pr["w"][g].cpu().double().numpy()[0].copy()
+        h = pr["h"][g].cpu().double().numpy()[:M].copy()
+        w[cut:], h[:, cut:] = 0.0, 0.0
+        ref = dq64[g][:, None] * w[None, :]
+        worst["dh%d" % g] = float((np.abs(out.get("dh%d" % g).double().numpy() - ref) / ((2 * u + 2.0 ** -40) * np.abs(ref) + 1e-300)).max())
+        terms = dq64[g][:, None] * h
+        ref = terms.sum(0)
+        gate = u * np.abs(ref) + M * 2.0 ** -50 * np.abs(terms).sum(0)
+        worst["dw%d" % g] = float((np.abs(out.get("dw%d" % g).double().numpy() - ref) / (gate + 1e-300)).max())
+    return worst
+
+
 def same_bits(a, b, keys=Out.NAMES):
     for k in keys:
         x, y = a.get(k), b.get(k)
@@ -225,17 +280,22 @@ def same_bits(a, b, keys=Out.NAMES):
     return None
 
 
-def check_shape(L, device, stream, dev, M, H, G, what=""):
-    """Both modes at one shape: q against mms_q_heads_backup, everything else against float64, a second run bit for bit."""
+def check_shape(L, device, stream, dev, M, H, G, what="", mutation=None):
+    """Both modes at one shape: q against mms_q_heads_backup, everything else against float64, a second run bit for bit.  With
+    `mutation` (check_against_float64) only mode 0's ratios against the corrupted statement are returned."""
     pr = problem(M, H, G, seed=3, device=dev)
+    if mutation is not None:
+        return check_against_float64(run(L, device, stream, pr, 0, scale=0.75), pr, 0, True, 0.2, 0.75, what, mutation=mutation)
     qb = backup_q(L, device, stream, pr, G)
+    worst = 0.0
     for mode, with_logp in ((0, True), (1, True), (1, False)):
         out = run(L, device, stream, pr, mode, with_logp=with_logp, scale=0.75)
         for g in range(G):
             assert torch.equal(out.get("q%d" % g), qb[g]), (what, "q differs from mms_q_heads_backup", g)
-        check_against_float64(out, pr, mode, with_logp, 0.2, 0.75, what)
+        worst = max(worst, max(check_against_float64(out, pr, mode, with_logp, 0.2, 0.75, what).values()))
         again = run(L, device, stream, pr, mode, with_logp=with_logp, scale=0.75)
         assert same_bits(out, again) is None, (what, "second run differs", same_bits(out, again))
+    qc.note("cpu" if device < 0 else "gpu", "q_heads_loss", "new" if (M, H, G) in NEW_SHAPES else "old", worst)
 
 
 def check_ties_and_strict(L, device, stream, dev):
@@ -271,16 +331,17 @@ def check_row_independence(L, device, stream, dev):
             assert torch.equal(part.get(k), full.get(k)[52:52 + 64]), (mode, k)
 
 
-def check_null_outputs(L, device, stream, dev, M=17, H=192):
+def check_null_outputs(L, device, stream, dev, M=17, H=192, G=2):
     """Every combination of NULL outputs leaves the others' bits unchanged."""
-    pr = problem(M, H, 2, seed=7, device=dev)
+    pr = problem(M, H, G, seed=7, device=dev)
     groups = [("q0",), ("q1",), ("dh0",), ("dh1",), ("dw0", "db0"), ("dw1", "db1")]
+    groups = [grp for grp in groups if G == 2 or not grp[0].endswith("1")]
     for mode in (0, 1):
         full = run(L, device, stream, pr, mode)
         for mask in itertools.product((0, 1), repeat=len(groups)):
             want = set(k for on, grp in zip(mask, groups) if on for k in grp)
             out = run(L, device, stream, pr, mode, want=want)
-            assert all((out.get(k) is None) == (k not in want and k != "loss") for k in Out.NAMES)
+            assert all((out.get(k) is None) == (k not in want and k != "loss") for k in Out.NAMES if G == 2 or not k.endswith("1"))
             assert same_bits(out, full) is None, (mode, sorted(want), same_bits(out, full))
 
 

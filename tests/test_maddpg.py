@@ -43,6 +43,43 @@ def test_q_group_error_paths():
     mc.check_q_error_paths(*_cpu(), other_device=0)
 
 
+# ---- every det_heads_act_kernel<NCT, WAVES> and every part of the grouped Q kernel's k-loop (maddpg_check's docstring) ----
+
+def test_head_table_reaches_every_kernel():
+    """The launcher's `switch` (NCT 1..8) times its four WAVES: an instantiation added there without a case fails here."""
+    assert len(mc.REACHABLE) == 32 and mc.head_coverage() == mc.REACHABLE
+    assert mc.head_coverage(mc.NEW_HEAD_CASES) == mc.REACHABLE and len(mc.head_coverage(mc.HEAD_CASES)) == 5
+    assert mc.expected_kernel(512, 128) == (8, 8) and mc.expected_kernel(192, 1) == (1, 1) and mc.expected_kernel(384, 17) == (2, 2)
+    assert mc.expected_kernel(768, 113) == (8, 4)
+    for t in range(1, 9):            # each NCT with a full last column tile and with one live column in it
+        assert {A for _, _, A, _, _ in mc.NEW_HEAD_CASES if (A + 15) // 16 == t} >= {16 * t, 16 * (t - 1) + 1}
+    assert all(mc.noise_case(c)[1:3] == c[1:3] and sum(mc.noise_case(c)[3:]) * c[2] <= 128 for c in mc.NEW_HEAD_CASES)
+
+
+def test_q_group_table_reaches_every_path():
+    assert mc.q_coverage() == mc.Q_REACHABLE and mc.q_coverage(mc.NEW_Q_CASES) == mc.Q_REACHABLE
+    assert mc.q_coverage(mc.Q_CASES) == {("grouped", "remainder"), ("grouped", "unrolled")}
+
+
+@pytest.mark.parametrize("case", mc.NEW_HEAD_CASES, ids=lambda c: "M%d-H%d-A%d-G%d-a%d" % c)
+def test_head_kernel_table(case):
+    mc.check_head_case(*_cpu(), case, "cpu")
+    mc.check_head_noise(*_cpu(), mc.noise_case(case), "cpu")
+
+
+@pytest.mark.parametrize("mutation", ["tile", "last"])
+def test_head_gate_sees_a_dropped_tile_or_column(mutation):
+    """The float64 side without the last column tile's weights, or without the last column's, at NCT = 8 with one live column in the
+    last tile: the gate is missed at least ten times over."""
+    assert mc.check_head_case(*_cpu(), (33, 768, 113, 3, 0), "cpu", mutation=mutation) >= 10
+    assert mc.check_head_case(*_cpu(), (1, 512, 128, 3, 2), "cpu", mutation=mutation) >= 10
+
+
+@pytest.mark.parametrize("case", mc.NEW_Q_CASES, ids=lambda c: "M%d-H%d-G%d" % c)
+def test_q_group_path_table(case):
+    mc.check_q_case(*_cpu(), case, "cpu")
+
+
 # ---- the modules against the reference's recorded update ----
 
 def test_storage_against_reference_ring():

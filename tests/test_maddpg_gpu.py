@@ -59,6 +59,36 @@ def test_q_group_error_paths(torch_cuda):
     mc.check_q_error_paths(*_gpu(), other_device=-1)
 
 
+# ---- every det_heads_act_kernel<NCT, WAVES> and every part of the grouped Q kernel's k-loop (maddpg_check's docstring) ----
+
+@pytest.fixture
+def no_dispatch_override():
+    import os
+    found = [v for v in mc.qc.DISPATCH_ENV if v in os.environ]
+    if found:
+        pytest.fail("%s set in the environment: not the shipped dispatch; unset to run these tests" % ", ".join(found))
+
+
+@pytest.mark.parametrize("case", mc.NEW_HEAD_CASES, ids=lambda c: "M%d-H%d-A%d-G%d-a%d" % c)
+def test_head_kernel_table(torch_cuda, no_dispatch_override, case):
+    """One case per det_heads_act_kernel<NCT, WAVES> (mc.expected_kernel): sigma = 0 against float64 in every destination layout, then
+    sigma > 0 against mms_ppo_act's stream."""
+    mc.check_head_case(*_gpu(), case, "cuda")
+    mc.check_head_noise(*_gpu(), mc.noise_case(case), "cuda")
+
+
+@pytest.mark.parametrize("mutation", ["tile", "last"])
+def test_head_gate_sees_a_dropped_tile_or_column(torch_cuda, no_dispatch_override, mutation):
+    """test_maddpg.py's, with the device's e_ref in the gate."""
+    assert mc.check_head_case(*_gpu(), (33, 768, 113, 3, 0), "cuda", mutation=mutation) >= 10
+    assert mc.check_head_case(*_gpu(), (1, 512, 128, 3, 2), "cuda", mutation=mutation) >= 10
+
+
+@pytest.mark.parametrize("case", mc.NEW_Q_CASES, ids=lambda c: "M%d-H%d-G%d" % c)
+def test_q_group_path_table(torch_cuda, no_dispatch_override, case):
+    mc.check_q_case(*_gpu(), case, "cuda")
+
+
 # ---- the modules through the fused paths on the device ----
 
 def test_losses_at_initial_parameters(torch_cuda, monkeypatch):

@@ -37,6 +37,32 @@ def test_cpu_build_against_float64(cpu, M, H, G):
     lc.check_shape(L, device, stream, dev, M, H, G, "cpu")
 
 
+def test_shape_table_reaches_every_kernel():
+    """launch_main's five NJ for either G, each with all chunks live and (NJ >= 4) with chunks guarded out."""
+    assert lc.coverage() == lc.REACHABLE and len(lc.REACHABLE) == 16 and len({k[:2] for k in lc.REACHABLE}) == 10
+    assert lc.coverage(lc.SHAPES) == {(1, 1, "full"), (2, 1, "full"), (2, 4, "guarded"), (2, 16, "full"), (2, 2, "full")}
+    assert [lc.expected_kernel(1, H)[1:] for H in (64, 128, 192, 256, 320, 512, 576, 1024)] == [(1, 1), (2, 2), (4, 3), (4, 4), (8, 5), (8, 8), (16, 9), (16, 16)]
+
+
+@pytest.mark.parametrize("M,H,G", lc.NEW_SHAPES)
+def test_kernel_table(cpu, M, H, G):
+    L, device, stream, dev = cpu
+    lc.check_shape(L, device, stream, dev, M, H, G, "cpu")
+
+
+@pytest.mark.parametrize("mutation", ["chunk", "last"])
+def test_gates_see_a_dropped_chunk_or_element(cpu, mutation):
+    """The float64 statement without the last 64 k of h and w, or without the last k, at nj = 16: the gates of dh and dw are missed at
+    least ten times over, for either network."""
+    L, device, stream, dev = cpu
+    worst = lc.check_shape(L, device, stream, dev, 33, 1024, 2, "cpu", mutation=mutation)
+    assert sorted(worst) == ["dh0", "dh1", "dw0", "dw1"] and min(worst.values()) >= 10, worst
+
+
+def test_null_outputs_one_network(cpu):
+    lc.check_null_outputs(*cpu, M=17, H=320, G=1)
+
+
 def test_ties_and_strict_rows(cpu):
     lc.check_ties_and_strict(*cpu)
 

@@ -24,6 +24,33 @@ def test_kernel_against_float64(gpu, M, H, G):
     lc.check_shape(L, device, stream, dev, M, H, G, "gpu")
 
 
+@pytest.fixture
+def no_dispatch_override():
+    import os
+    found = [v for v in lc.qc.DISPATCH_ENV if v in os.environ]
+    if found:
+        pytest.fail("%s set in the environment: not the shipped dispatch; unset to run these tests" % ", ".join(found))
+
+
+@pytest.mark.parametrize("M,H,G", lc.NEW_SHAPES)
+def test_kernel_table(gpu, no_dispatch_override, M, H, G):
+    """One shape per q_heads_loss_kernel<G, NJ> with every chunk live, and one with chunks guarded out (lc.expected_kernel)."""
+    L, device, stream, dev = gpu
+    lc.check_shape(L, device, stream, dev, M, H, G, "gpu")
+
+
+@pytest.mark.parametrize("mutation", ["chunk", "last"])
+def test_gates_see_a_dropped_chunk_or_element(gpu, no_dispatch_override, mutation):
+    """test_q_loss.py's on the device."""
+    L, device, stream, dev = gpu
+    worst = lc.check_shape(L, device, stream, dev, 33, 1024, 2, "gpu", mutation=mutation)
+    assert sorted(worst) == ["dh0", "dh1", "dw0", "dw1"] and min(worst.values()) >= 10, worst
+
+
+def test_null_outputs_one_network(gpu, no_dispatch_override):
+    lc.check_null_outputs(*gpu, M=17, H=320, G=1)
+
+
 def test_ties_and_strict_rows(gpu):
     lc.check_ties_and_strict(*gpu)
 

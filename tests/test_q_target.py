@@ -78,7 +78,27 @@ def test_cpu_build_against_float64(M, H, G, with_logp):
         err = np.abs(q[g].double().numpy() - q64) / s
         print("M %d H %d g %d: max |q - q64| / s = %.3g" % (M, H, g, err.max()))
         assert (err <= 1e-6).all()
+        qc.note("cpu", "q_heads_backup", "old", err.max() / 1e-6)
     qc.check_backup(q, backup, pr, with_logp, 0.99, 0.2, "cpu M %d H %d G %d" % (M, H, G))
+
+
+def test_case_table_reaches_every_path():
+    """Both kernels with each part of the k-loop; the shapes that ran before the table never ran both parts in one call."""
+    assert qc.coverage() == qc.REACHABLE and len(qc.REACHABLE) == 6
+    assert {qc.expected_path(H) for H in qc.OLD_H} == {"remainder", "unrolled"}
+    assert [qc.expected_path(H) for H in (64, 192, 256, 320, 448, 576, 4096)] == ["remainder", "remainder", "unrolled", "both", "both", "both", "unrolled"]
+
+
+@pytest.mark.parametrize("M,H,G", qc.CASES)
+def test_path_table(M, H, G):
+    qc.check_case(_lib.lib_cpu(), -1, None, "cpu", M, H, G)
+
+
+@pytest.mark.parametrize("G", [1, 2])
+@pytest.mark.parametrize("mutation", ["chunk", "last"])
+def test_gate_sees_a_dropped_chunk_or_element(mutation, G):
+    """The float64 side without the last 64 k, or without the last k, at nj = 9: the gate is missed at least ten times over."""
+    assert qc.check_case(_lib.lib_cpu(), -1, None, "cpu", 33, 576, G, mutation=mutation) >= 10
 
 
 def test_exact_properties_cpu_build():

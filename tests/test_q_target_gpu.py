@@ -57,7 +57,32 @@ def test_kernel_against_float64(torch_cuda, M, H, G):
             et = (np.abs(t - q64) / s).max()
             print("M %d H %d G %d g %d: e = %.3g, e_torch = %.3g" % (M, H, G, g, e, et))
             assert e <= 2 * et + 1e-6, (e, et)
+            qc.note("gpu", "q_heads_backup", "old", e / (2 * et + 1e-6))
         qc.check_backup(q, backup, pr, with_logp, 0.99, 0.2, "gpu M %d H %d G %d logp %d" % (M, H, G, with_logp))
+
+
+@pytest.fixture
+def no_dispatch_override():
+    import os
+    found = [v for v in qc.DISPATCH_ENV if v in os.environ]
+    if found:
+        pytest.fail("%s set in the environment: not the shipped dispatch; unset to run these tests" % ", ".join(found))
+
+
+@pytest.mark.parametrize("M,H,G", qc.CASES)
+def test_path_table(torch_cuda, no_dispatch_override, M, H, G):
+    """q_heads_backup_kernel<G> with each part of its k-loop (qc.expected_path): the unrolled loop, the remainder loop, and both in one
+    call."""
+    L, dev, stream = _gpu()
+    qc.check_case(L, dev, stream, "cuda", M, H, G)
+
+
+@pytest.mark.parametrize("G", [1, 2])
+@pytest.mark.parametrize("mutation", ["chunk", "last"])
+def test_gate_sees_a_dropped_chunk_or_element(torch_cuda, no_dispatch_override, mutation, G):
+    """test_q_target.py's, with the device's gate."""
+    L, dev, stream = _gpu()
+    assert qc.check_case(L, dev, stream, "cuda", 33, 576, G, mutation=mutation) >= 10
 
 
 def test_exact_properties(torch_cuda):

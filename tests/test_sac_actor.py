@@ -67,6 +67,31 @@ def test_cpu_build_against_float64(N, H, A, limit, det):
         assert torch.equal(out["u"], out["mu"])
 
 
+def test_case_table_reaches_every_kernel():
+    """The launcher's `switch` (NCT 2..16) times the WAVES its LDS clamp leaves, and both ways to 4 waves at NCT >= 10: an instantiation
+    or a clamp changed there without a case fails here."""
+    assert sc.coverage() == sc.REACHABLE and len(sc.REACHABLE) == 32 and len({k[:2] for k in sc.REACHABLE}) == 28
+    assert sc.coverage(sc.OLD_SHAPES) == {(10, 4, True), (4, 8, False), (2, 4, False), (2, 1, False), (4, 2, False), (16, 1, False)}
+    assert sc.expected_kernel(512, 128) == (16, 4, True) and sc.expected_kernel(256, 128) == (16, 4, False)
+    assert sc.expected_kernel(512, 64) == (8, 8, False) and sc.expected_kernel(768, 113) == (16, 4, False)
+    for t in range(1, 9):            # each NCT with a full last column tile per head and with one live column in it
+        assert {A for _, _, A in sc.CASES if (A + 15) // 16 == t} >= {16 * t, 16 * (t - 1) + 1}
+
+
+@pytest.mark.parametrize("N,H,A", sc.CASES)
+def test_kernel_table(N, H, A):
+    sc.check_case(_lib.lib_cpu(), -1, None, "cpu", N, H, A)
+
+
+@pytest.mark.parametrize("mutation", ["tile", "last"])
+def test_gate_sees_a_dropped_tile_or_column(mutation):
+    """The float64 side without each head's last column tile, or without its last column, at NCT = 16: the gate of the products is
+    missed at least ten times over."""
+    L = _lib.lib_cpu()
+    assert sc.check_kernel(L, -1, None, "cpu", 33, 768, 113, mutation=mutation) >= 10
+    assert sc.check_kernel(L, -1, None, "cpu", 17, 256, 128, mutation=mutation) >= 10
+
+
 def test_counters_and_draws():
     L = _lib.lib_cpu()
     N, H, A = 1000, 64, 9

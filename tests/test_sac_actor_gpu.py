@@ -36,32 +36,32 @@ SHAPES = [(4096, 1024, 80), (8192, 1024, 24), (1000, 256, 8), (7, 64, 3), (333, 
 
 @pytest.mark.parametrize("N,H,A", SHAPES)
 def test_kernel_against_float64(torch_cuda, N, H, A):
-    torch = torch_cuda
-    L, dev, stream = _gpu(torch)
-    h, mw, mb, lw, lb = (t.cuda() for t in sc.problem(N, H, A, seed=N + H + A))
-    counters = (torch.arange(N, dtype=torch.int64, device="cuda") * 3) % 7
-    z = sc.draws(L, dev, stream, 11, counters, 5, N, A)
-    out = sc.run(L, dev, stream, h, mw, mb, lw, lb, act_limit=1.0, seed=11, counters=counters, row_offset=5)
-    det = sc.run(L, dev, stream, h, mw, mb, lw, lb, deterministic=True, seed=11)
-    torch.cuda.synchronize()
-    mu64, ls64, s_mu, s_ls = sc.f64_head(h, mw, mb, lw, lb)
-    # the GEMMs: error against float64 (over the row scale) <= 2 x torch fp32 nn.Linear's on the same data + 1e-6
-    t_mu = torch.nn.functional.linear(h, mw, mb).double().cpu().numpy()
-    t_ls = torch.nn.functional.linear(h, lw, lb).double().cpu().numpy()
-    for name, got, ref, tref, s in (("mu", out["mu"], mu64, t_mu, s_mu), ("mu det", det["mu"], mu64, t_mu, s_mu)):
-        e = (np.abs(got.double().cpu().numpy() - ref) / s).max()
-        et = (np.abs(tref - ref) / s).max()
-        assert e <= 2 * et + 1e-6, (name, e, et)
-    ls = out["log_std"].double().cpu().numpy()
-    inside = (ls64 > -19.99) & (ls64 < 1.99)
-    e = (np.abs(ls - ls64) / s_ls)[inside].max()
-    et = (np.abs(t_ls - ls64) / s_ls)[inside].max()
-    assert e <= 2 * et + 1e-6, ("log_std", e, et)
-    assert (ls[ls64 < -20.001] == -20.0).all() and (ls[ls64 > 2.001] == 2.0).all()
-    assert torch.equal(counters, (torch.arange(N, dtype=torch.int64, device="cuda") * 3) % 7 + 1)
-    sc.check_epilogue(out, z, 1.0, 1e-6, False, "gpu sample")
-    sc.check_epilogue(det, torch.zeros_like(z), 1.0, 1e-6, True, "gpu deterministic")
-    assert torch.equal(det["u"], det["mu"])
+    L, dev, stream = _gpu(torch_cuda)
+    sc.check_kernel(L, dev, stream, "cuda", N, H, A, kind="old")
+
+
+@pytest.fixture
+def no_dispatch_override():
+    import os
+    found = [v for v in sc.qc.DISPATCH_ENV if v in os.environ]
+    if found:
+        pytest.fail("%s set in the environment: not the shipped dispatch; unset to run these tests" % ", ".join(found))
+
+
+@pytest.mark.parametrize("N,H,A", sc.CASES)
+def test_kernel_table(torch_cuda, no_dispatch_override, N, H, A):
+    """One case per sac_head_act_kernel<NCT, WAVES> and per way to reach it (sc.expected_kernel): sampled and deterministic, with and
+    without logp_slot."""
+    L, dev, stream = _gpu(torch_cuda)
+    sc.check_case(L, dev, stream, "cuda", N, H, A)
+
+
+@pytest.mark.parametrize("mutation", ["tile", "last"])
+def test_gate_sees_a_dropped_tile_or_column(torch_cuda, no_dispatch_override, mutation):
+    """test_sac_actor.py's, with the device's e_torch in the gate."""
+    L, dev, stream = _gpu(torch_cuda)
+    assert sc.check_kernel(L, dev, stream, "cuda", 33, 768, 113, mutation=mutation) >= 10
+    assert sc.check_kernel(L, dev, stream, "cuda", 17, 256, 128, mutation=mutation) >= 10
 
 
 @pytest.mark.parametrize("N,H,A", [(1000, 256, 8), (333, 128, 17), (512, 1024, 80)])
