@@ -892,7 +892,8 @@ int mms_linear_group_act_split16(int device, int32_t groups, int64_t M, int32_t 
  *   bias_g[n] (NULL: without that term), rb[g][n] = |W~ row|_2 sqrt(K) + |c[n]|: the row's bound of W~ xhat + c over normalised inputs.
  * mms_fold_scales16_group: scale_g = 2^(14 - e) with 1.001 max_{i < n[g]} rb[g][i] <= 2^e -> scale1[g][0] (f32 [1], optional) and
  *   ysc[g][0..M) = scale_g, yinv[g][0..M) = 1 / scale_g (f32 [M] each, optional): the y_scale / next x_inv rows of
- *   mms_linear_group_act_split16 for a layer whose output bound does not depend on the data. */
+ *   mms_linear_group_act_split16 for a layer whose output bound does not depend on the data.  A zero network (largest rb[g][i] zero or
+ *   at most 1e-30, or n[g] = 0) gets scale_g = 2^100 and 1 / scale_g = 2^-100, not 1: the bound is floored at 1e-30 and the shift clamped. */
 int mms_fold_planes16_group(int device, int32_t groups, const int64_t* N, const int32_t* K, const float* const* w, const float* const* gamma,
                             const float* const* beta, const float* const* bias, void* const* planes, float* const* inv, float* const* s,
                             float* const* c, float* const* rb, float* const* wt, void* hip_stream);

@@ -130,9 +130,11 @@ hipError_t launch_fold_planes16(const FoldPlanesArgs& a, int groups, hipStream_t
     return hipGetLastError();
 }
 
-// scale_g = 2^(14 - e) with 1.001 max_n rb_g[n] <= 2^e (an all-zero network keeps 1): stored once (scale1[g], f32 [1], optional) and per
-// row of the batch (ysc[g], yinv[g]: f32 [M] each -- what the layer kernel reads).  Every block re-reduces its network's row bounds
-// (a few hundred floats) instead of waiting for a separate reduction launch.
+// scale_g = 2^(14 - e) with 1.001 max_n rb_g[n] <= 2^e: stored once (scale1[g], f32 [1], optional) and per row of the batch (ysc[g],
+// yinv[g]: f32 [M] each -- what the layer kernel reads).  A network whose largest row bound is zero, at most 1e-30, or that has no rows
+// (n[g] = 0) does NOT keep 1: fold_net_bound floors the bound at 1e-30 and pow2_scale clamps the shift, so it gets scale 2^100 and
+// inverse 2^-100 -- harmless, its activations are zero under any scale (tests/refresh_kernels_check.py pins it).  Every block
+// re-reduces its network's row bounds (a few hundred floats) instead of waiting for a separate reduction launch.
 __global__ void __launch_bounds__(256) fold_scales16_kernel(FoldScalesArgs a) {
     __shared__ float s_m[4];
     const int g = blockIdx.y;

@@ -1,5 +1,6 @@
-"""ActorCritic.refresh() and the device-side refresh entry points (mms_weight_planes16_group, mms_layer_bounds16, mms_chain_scales16) --
-one check list for both builds: tests/test_cpu_backend.py runs it on libmms_cpu.so, tests/test_gpu_parity.py on libmms.so.
+"""ActorCritic.refresh() and the device-side refresh entry points (mms_weight_planes16_group, mms_chain_refresh16,
+mms_fold_planes16_group, mms_fold_scales16_group) -- one check list for both builds: tests/test_cpu_backend.py runs it on
+libmms_cpu.so, tests/test_gpu_parity.py on libmms.so.  (Per output, per instantiation and at the loops' edges: refresh_kernels_check.py.)
 
 What the reference does at this point: nothing -- its nn.Linear layers read their parameters in every forward
 (/root/reference/agents/algorithms/rl/ppo/module.py:73-87), so a parameter update of any kind is followed by the next `act`.  The fused
