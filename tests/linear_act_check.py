@@ -335,15 +335,16 @@ def check_tanh(L, di, stream, tdev):
     """The epilogue's tanh (act = 3) alone: x = (v, 0, ..), w = (1, 0, ..), b = 0, so that the pre-activation IS v, through one generic
     and one fast kernel, against float64 tanh(v).  Gate: absolute error <= 8 * 2^-23 = 9.6e-7 for every v of tanh_sweep().
 
-    Where it comes from (u = 2^-24; csrc/layer_common.h evaluates 1 - 2 / (E + 1), E = __expf(2 v); the CPU build calls tanhf):
-    q = 2 / (E + 1) lies in [0, 2] and a relative error r of E moves it by q E / (E + 1) r = sech^2(v) r / 2.  E carries at most
-    2 ulp = 4u from the exponential itself and |2 v| u from the rounding of its scaled argument: sech^2(v) (4u + 2 |v| u) / 2 <= 2.5u
-    (|v| sech^2(v) <= 0.45).  The sum E + 1 rounds once (q u <= 2u), the division is good to 2.5 ulp = 5u if the build relaxes it
-    (5u q <= 10u), and the final 1 - q rounds a value of magnitude <= 1 (u).  In all <= 15.5u to first order at the very worst (q -> 2,
-    v << 0; half of that for v >= 0, where q <= 1) -- inside 32u = 8 * 2^-23 with room for the second-order terms, while a wrong
-    constant or a dropped term shows as 1e-3 and more.  Near v = 0 the form cancels: the result keeps an absolute, not a relative,
-    accuracy, which is what csrc/layer_common.h promises.
-    Saturation: v = +-50 gives exactly +-1 (E overflows to inf, or underflows to 0).  Returns the worst absolute error."""
+    Where it comes from (u = 2^-24; csrc/layer_common.h evaluates sign(v) (1 - t) / (1 + t), t = __expf(-2 |v|) in (0, 1]; the CPU build
+    calls tanhf): a relative error r of t moves the quotient by 2 t / (1 + t)^2 r = sech^2(v) r / 2.  t carries at most 2 ulp = 4u from
+    the exponential itself and |2 v| u from the rounding of its scaled argument: sech^2(v) (4u + 2 |v| u) / 2 <= 2.5u (|v| sech^2(v) <=
+    0.45).  1 - t is exact for t >= 1/2 and rounds once below, 1 + t rounds once (u of the quotient each, which is <= 1), and the
+    division is good to 2.5 ulp = 5u of the quotient if the build relaxes it.  In all <= 9.5u to first order at the very worst, and
+    <= 2.5u near v = 0, where every term but the exponential's scales with the result -- inside 32u = 8 * 2^-23 with room for the
+    second-order terms, while a wrong constant or a dropped term shows as 1e-3 and more.  (Until tests/test_split16_paths_gpu.py the
+    form was 1 - 2 / (E + 1), E = __expf(2 v): rounded twice at magnitude 1 whatever |v|, 1.7 x 2^-23 measured -- inside this gate,
+    outside the layers' per-element bound in rows of tiny activations.)
+    Saturation: v = +-50 gives exactly +-1 (t underflows to 0).  Returns the worst absolute error."""
     v = tanh_sweep()
     truth = torch.tanh(v.double())
     worst = {}
