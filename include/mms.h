@@ -76,6 +76,11 @@
  *   MADDPG: every agent's deterministic actor head, exploration noise    mms_det_heads_act_group
  *     and the joint action row (algorithms/marl/maddpg/module.py:36-46,
  *     :165-175); every agent's Q target tail (:218-219)                  mms_q_heads_backup_group
+ *   DDPG / TD3: MLPActor's last Linear + tanh + act_limit, the target     mms_det_heads_act
+ *     policy smoothing (rl/td3/td3.py:361-367, rl/ddpg/ddpg.py:357-365)
+ *     and the exploration noise of act (rl/ddpg/module.py:52-58)
+ *   autograd's backward of that head's epilogue in compute_loss_pi      mms_det_heads_grad
+ *     (td3.py:383-388, ddpg.py:377-381)
  *   clip_grad_norm_ + Adam.step() + the polyak loop of every learner     mms_param_step
  *     (rl/sac/sac.py:325-349, rl/ppo/ppo.py, marl/mappo_trainer.py,
  *     marl/maddpg/module.py:280-292)
@@ -530,6 +535,45 @@ int mms_det_heads_act_group(int device, int32_t groups, int64_t M, int32_t H, in
                             const float* const* h, const float* const* w, const float* const* b, const float* act_limit,
                             float sigma, uint64_t seed, int64_t* counters, int64_t row_offset,
                             float* const* act_out, int64_t act_pitch, float* joint_out, int64_t joint_pitch, void* hip_stream);
+
+/* The last layer of ONE deterministic actor (algorithms/rl/{ddpg,td3}/module.py MLPActor, from its last hidden activation on), with
+ * what DDPG's and TD3's updates put behind it, in one launch plus at most one counter launch:
+ *   t[i,k] = tanh(dot(h[i,:], w[k,:]) + b[k])                    h [M,H], w [A,H], b [A]: torch's parameters, read in place
+ *   a[i,k] = act_limit * t[i,k]
+ *   sigma > 0:  e = sigma * z,  z ~ N(0,1): counter-based (seed, global row = row_offset + i, counters[i], k), mms_ppo_act's stream
+ *               noise_clip finite and >= 0:  e = min(max(e, -noise_clip), noise_clip)        (td3.py:362-364 target policy smoothing)
+ *               a = min(max(a + e, -act_limit), act_limit);  counters[i] += 1 once per call (behind the draws, on the same stream)
+ *   sigma == 0: nothing is drawn, no clamp, counters untouched (may be NULL)
+ * noise_clip negative or +inf: no noise clip (MLPActorCritic.act's exploration noise).  Destinations, each optional, at least one:
+ * act_out [M,A] at act_pitch floats per row (a pitch of W + A writes the action into the action columns of a [o | a] block), and
+ * tanh_out [M,A] dense: t as computed BEFORE any noise -- what mms_det_heads_grad reads.
+ * This is mms_det_heads_act_group's kernel with one group: with sigma == 0, or sigma > 0 without a noise clip, act_out holds bit for
+ * bit what that entry gives with groups = 1, agent0 = 0; the order of the sum over k is a function of H and A alone, no atomics, and
+ * a row's result depends on that row and the parameters only.  H a positive multiple of 64, 1 <= A <= 128, h and w 16-byte aligned,
+ * act_pitch >= A (when act_out is given), M >= 0 (M == 0 succeeds and touches nothing).  Rows past M and columns past A are never
+ * written.  Bad arguments return non-zero with mms_last_error(NULL) and write nothing. */
+int mms_det_heads_act(int device, int64_t M, int32_t H, int32_t A, const float* h, const float* w, const float* b, float act_limit,
+                      float sigma, float noise_clip, uint64_t seed, int64_t* counters, int64_t row_offset,
+                      float* act_out, int64_t act_pitch, float* tanh_out, void* hip_stream);
+
+/* The backward of that head's epilogue (csrc/det_head_kernels.hip), on mms_sac_heads_grad's pattern: the gradient with respect to the
+ * OUTPUT of the actor's last Linear, and its bias gradient, from the forward's tanh_out.
+ *   dy[i,k]  = (act_limit * g[i,k]) * (1 - t[i,k]^2)       g = d loss / d action, [N,A] at grad_pitch floats per row (>= A)
+ *   dbias[k] = sum_i dy[i,k]                               dbias NULL: not computed
+ * t [N,A] and dy [N,A] are dense.  grad_pitch lets g be the action columns of the critic's input gradient [N, W + A], read where they
+ * lie.  The two products behind it (grad_hidden = dy @ W, grad_W = dy^T @ hidden) are left to the caller's GEMM library.
+ * Every product and difference is rounded on its own (no contraction): dy has the same bits in the HIP and the CPU build.  A row of
+ * dy depends on that row and act_limit alone.  dbias: per-workgroup partials in double in the workspace, then one pass that adds them
+ * in a fixed order and rounds once -- no atomics, no memset, bit-identical run to run.  At most two launches on hip_stream, no host
+ * synchronisation, graph-capturable.  16-byte accesses of t and dy where both are 16-byte aligned (any A), of g where in addition g is
+ * 16-byte aligned and A and grad_pitch are multiples of 4; element by element otherwise, with the same results.
+ * workspace / ws_bytes: mms_sac_heads_grad's convention (NULL stores the bytes needed and returns 0 -- nothing else is read; 256-byte
+ * aligned; a smaller one is an error; the CPU build needs 0 and runs on any aligned non-NULL workspace).  No initialisation needed.
+ * 0 <= N <= 0x7fffffff (N == 0 succeeds and writes nothing), 1 <= A <= 128.  Inputs are taken to be finite.  Bad arguments -- t, g
+ * or dy NULL, grad_pitch below A, A or N out of range, a small or misaligned workspace -- return non-zero with mms_last_error(NULL)
+ * and write nothing. */
+int mms_det_heads_grad(int device, int64_t N, int32_t A, float act_limit, const float* t, const float* g, int64_t grad_pitch,
+                       float* dy, float* dbias, void* workspace, int64_t* ws_bytes, void* hip_stream);
 
 /* mms_q_heads_backup with ONE critic per group for up to MMS_MAX_GROUPS groups in one launch (cal_value_loss, module.py:218-219):
  *   q_g[i]      = dot(h_g[i,:], w_g) + b_g[0]

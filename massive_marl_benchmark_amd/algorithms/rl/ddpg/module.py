@@ -25,6 +25,25 @@ rebuilt from the parameters on EVERY call (two launches), so an optimizer step o
 replays of a captured graph -- is followed with no validity rule at all.  Shapes the kernel does not take (batch or a hidden width
 not a multiple of 128) run the "fp32" chain and give its bits.  The actor's Linear(H, act_dim) + tanh stays one `mms_linear2_act`
 launch, the critics' Linear(H, 1) stays inside `mms_q_heads_backup`.
+
+`fused_grad=True` (constructor keyword of MLPActor and MLPActorCritic, which hands it down; the default False is everything above, launch
+for launch) gives the actor's last layer -- Linear(H, act_dim) + tanh + act_limit -- to the two entries `mms_det_heads_act` /
+`mms_det_heads_grad`, on "cuda" and, through the CPU build, on "cpu":
+  * where a gradient is wanted (compute_loss_pi, td3.py:383-388) the hidden layers stay in torch and the head is `_DetHead`: one
+    `mms_det_heads_act` launch forward (the action, and tanh(pre) kept for the backward), one `mms_det_heads_grad` call plus the two
+    library products backward.  Once differentiable: `create_graph=True` raises.
+  * where none is wanted the head is one `mms_det_heads_act` launch behind the hidden-layer paths above.
+  * `MLPActor.smoothed(obs, sigma, noise_clip)` is the no-gradient target action of td3.py:361-367 (ddpg.py:357-365 smooths too) with
+    the noise and both clamps inside that launch; `MLPActorCritic.act(deterministic=False)` on the HIP device takes its exploration
+    noise there as well (`sigma = act_noise`, no noise clip).
+  * `MLPActorCritic.q_loss` / `pi_loss` are compute_loss_q / compute_loss_pi on sac.loss.q_heads_loss; `pi_loss` has the head write the
+    action into the action columns of the critic's `[o | a]` input block, so no `torch.cat` runs, and the backward reads the action
+    columns of that block's gradient where they lie.
+A head the entries do not take (dtype, H not a multiple of 64, act_dim > 128, alignment, another device) runs the torch expression; that
+is decided before anything is launched.  The noise of the fused head is this build's counter stream keyed (seed, row_offset + row, the
+row's draw counter, column), not torch's generator: another stream of normals, the same distribution.  Seed, counters and row_offset are
+owned as sac.module's actor owns them (`_NoiseOwner`): plain attributes, not buffers -- the state_dict keys stay the reference's -- with
+the counters pinned once a graph capture has used them (`pi.reserve_counters(rows, device)` before capturing).
 """
 import copy
 import ctypes
@@ -37,6 +56,56 @@ from ....engine import current_stream_ptr
 
 _ACT_CODES = {nn.Identity: 0, nn.ELU: 1, nn.ReLU: 2, nn.Tanh: 3}
 _Q_MAX_H = 4096          # include/mms.h: MMS_Q_MAX_H
+
+
+def _p(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _draw_seed():
+    """A noise-stream key from torch's default generator, so that torch.manual_seed makes runs reproducible."""
+    return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+class _NoiseOwner:
+    """What an actor with a fused sampling head keeps besides its layers: `seed`, `row_offset` (global index of row 0: data-parallel
+    shards draw disjoint rows) and the per-row draw counters -- a plain device tensor, not a buffer, grown to the largest row count
+    seen.  A captured graph holds only the counters' device address, so once a graph capture has used them they are pinned: a call
+    that would need more rows (or another device) raises instead of moving them."""
+
+    def _init_noise(self, seed, row_offset):
+        self.seed = int(seed)
+        self.row_offset = int(row_offset)
+        self._counters = None
+        self._counters_pinned = False      # a graph capture has used the counters: their address must not change
+
+    def reserve_counters(self, n, device):
+        """Size the per-row draw counters for n rows on `device` now (before a graph capture); returns them."""
+        return self.counters(n, device)
+
+    def counters(self, n, device):
+        """The per-row draw counters on `device`, at least n of them (grown on demand; what was drawn so far is kept).  Once pinned
+        by a graph capture they are never reallocated: a request they cannot serve raises."""
+        c = self._counters
+        if c is None or c.device != torch.device(device) or c.numel() < n:
+            capturing = torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing()
+            if self._counters_pinned or capturing:     # (allocated inside a capture, the zero fill would replay with the graph)
+                raise RuntimeError("%s: %d rows on %s need new draw counters, but a graph capture holds or is recording the current "
+                                   "ones (%s); call pi.reserve_counters(<largest row count>, device) before capturing"
+                                   % (type(self).__name__, n, torch.device(device), "none" if c is None else "%d on %s" % (c.numel(), c.device)))
+            old = None if c is None else c.to(device)
+            c = torch.zeros(max(n, 0 if old is None else old.numel()), dtype=torch.int64, device=device)
+            if old is not None:
+                c[:old.numel()].copy_(old)
+            self._counters = c
+        return c
+
+    def _draw_counters(self, n, device):
+        """The counters for a call that draws, pinned if a capture is recording it."""
+        c = self.counters(n, device)
+        if torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing():
+            self._counters_pinned = True
+        return c
 
 
 def _kernel_layout(t):
@@ -327,14 +396,91 @@ def fused_q_backup(qs, obs, act, r, d, gamma, alpha=None, logp=None):
     return backup
 
 
-class MLPActor(_Split16Owner, nn.Module):
-    def __init__(self, obs_dim, act_dim, hidden_sizes, activation, act_limit, layers="fp32"):
+def det_head_act(hidden, weight, bias, act_limit, sigma=0.0, noise_clip=-1.0, seed=0, counters=None, row_offset=0, out=None, tanh_out=None):
+    """One mms_det_heads_act call on hidden [M, H] (16-byte aligned, dense): the action into `out` ([M, A] with unit column stride and
+    any row pitch; allocated when None and tanh_out is None) and tanh(pre) into `tanh_out` ([M, A] dense).  Returns `out`."""
+    M, H = hidden.shape
+    A = weight.shape[0]
+    if out is None and tanh_out is None:
+        out = torch.empty(M, A, device=hidden.device)
+    L, idx, stream = _lib.for_device(hidden.device)
+    _lib.check(L.mms_det_heads_act(idx, M, H, A, _p(hidden), _p(weight), _p(bias), float(act_limit), float(sigma), float(noise_clip), seed, _p(counters),
+                                   row_offset, _p(out), 0 if out is None else out.stride(0), _p(tanh_out), stream), None, "mms_det_heads_act", L)
+    return out
+
+
+class _DetHead(torch.autograd.Function):
+    """The actor's head behind its hidden layers with a gradient (`fused_grad=True`): mms_det_heads_act forward with tanh(pre) kept,
+    mms_det_heads_grad + two library products backward.  With `obs` [N, W] the result is the critic's input block [o | a] ([N, W + A]:
+    the head writes the action columns at pitch W + A, the observation is copied in front) and the backward reads the action columns
+    of the block's gradient where they lie; with obs None the result is the action [N, A]."""
+
+    @staticmethod
+    def forward(ctx, hidden, weight, bias, act_limit, obs):
+        N, A = hidden.shape[0], weight.shape[0]
+        W = 0 if obs is None else obs.shape[1]
+        block = torch.empty(N, W + A, device=hidden.device)
+        t = torch.empty(N, A, device=hidden.device)
+        if W:
+            block[:, :W].copy_(obs)
+        det_head_act(hidden, weight, bias, act_limit, out=block[:, W:], tanh_out=t)
+        ctx.save_for_backward(hidden, weight, t)
+        ctx.act_limit, ctx.W = act_limit, W
+        return block
+
+    @staticmethod
+    def backward(ctx, g):
+        # once_differentiable alone raises only where the incoming gradient itself requires one; under create_graph=True with a constant
+        # incoming gradient it would hand back a silently constant head: refuse that as well (sac.module._SacHead)
+        if torch.is_grad_enabled():
+            raise RuntimeError("MLPActor(fused_grad=True): the fused head is once differentiable (no create_graph=True)")
+        return _DetHead._backward(ctx, g)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _backward(ctx, g):
+        from ..ppo.loss import _workspace      # (the device's cached, 256-byte aligned workspace: calls run in stream order)
+        hidden, weight, t = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        N, A = t.shape
+        W, dev = ctx.W, t.device
+        if g.dtype != torch.float32 or g.stride(1) != 1 or g.stride(0) < W + A:      # (a .sum() upstream delivers a stride-0 expanded tensor)
+            g = g.to(torch.float32).contiguous()
+        g_obs = g[:, :W] if (W and need[4]) else None
+        if not any(need[:3]):
+            return None, None, None, None, g_obs
+        g_act = g[:, W:]
+        L, idx, stream = _lib.for_device(dev)
+        dy = torch.empty(N, A, device=dev)
+        dbias = torch.empty(A, device=dev) if need[2] else None
+        nbytes = ctypes.c_int64(-1)
+        head = (idx, N, A, ctx.act_limit, _p(t), _p(g_act), g.stride(0), _p(dy), _p(dbias))
+        _lib.check(L.mms_det_heads_grad(*head, None, ctypes.byref(nbytes), stream), None, "mms_det_heads_grad size query", L)
+        ws = _workspace(nbytes.value, dev)
+        _lib.check(L.mms_det_heads_grad(*head, ctypes.c_void_p(ws), ctypes.byref(nbytes), stream), None, "mms_det_heads_grad", L)
+        return dy @ weight if need[0] else None, dy.t() @ hidden if need[1] else None, dbias, None, g_obs
+
+
+class MLPActor(_NoiseOwner, _Split16Owner, nn.Module):
+    def __init__(self, obs_dim, act_dim, hidden_sizes, activation, act_limit, seed=None, row_offset=0, fused_grad=False, layers="fp32"):
         super().__init__()
         self.pi = mlp([obs_dim, *hidden_sizes, act_dim], activation, nn.Tanh)
         self.act_limit = act_limit
         self._init_layers(layers)          # "f16x2": the hidden pairs through split16_hidden (module docstring)
+        self.fused_grad = bool(fused_grad)  # True: the last layer through mms_det_heads_act / mms_det_heads_grad (module docstring)
+        # drawn after the layers (their initialisation is the reference's) and only where a fused head can use it: the default
+        # constructor leaves torch's generator where the reference's does
+        self._init_noise(_draw_seed() if (seed is None and self.fused_grad) else (seed or 0), row_offset)
 
     def forward(self, obs):
+        if self._head_fusable(obs):
+            if torch.is_grad_enabled() and (obs.requires_grad or any(p.requires_grad for p in self.parameters())):
+                return self._block(obs, None)
+            return self._fused_head(obs)
+        return self.torch_forward(obs)
+
+    def torch_forward(self, obs):
+        """`fused_grad=False`, and every head the entries do not take: the hidden-layer paths of the module docstring, torch otherwise."""
         out = None
         if self.layers == "f16x2" and obs.is_cuda and obs.dim() == 2 and len(self.pi) > 2:
             hs = split16_hidden([list(self.pi)[:-2]], obs, self._split16_scratch)
@@ -345,6 +491,66 @@ class MLPActor(_Split16Owner, nn.Module):
         if out is None:
             out = self.pi(obs)
         return out if self.act_limit == 1.0 else self.act_limit * out       # x 1.0 is exact: one launch less for the ant / helicopter tasks
+
+    def _head_fusable(self, obs):
+        """`fused_grad=True` and the two entries take this actor's last layer for `obs`: Linear(H, A) with a bias + Tanh behind at least
+        one hidden pair, fp32, dense, 16-byte aligned parameters on "cuda" or "cpu", H % 64 == 0, 1 <= A <= 128, a non-empty fp32
+        input on the parameters' device.  Nothing has been launched when this returns."""
+        if not self.fused_grad or len(self.pi) < 4 or not torch.is_tensor(obs) or obs.dtype != torch.float32 or obs.dim() < 1 or obs.numel() == 0:
+            return False
+        last, fn = self.pi[-2], self.pi[-1]
+        if not isinstance(last, nn.Linear) or last.bias is None or type(fn) is not nn.Tanh:
+            return False
+        dev = last.weight.device
+        H, A = last.in_features, last.out_features
+        return (dev.type in ("cuda", "cpu") and obs.device == dev and H % 64 == 0 and 1 <= A <= 128 and obs.shape[-1] == self.pi[0].in_features
+                and all(p.dtype == torch.float32 and p.device == dev and _kernel_layout(p) for p in (last.weight, last.bias)))
+
+    def _hidden(self, x):
+        """The last hidden activations [M, H] of x [M, W], dense and 16-byte aligned: without a gradient through the fused hidden-layer
+        paths where they apply, in torch otherwise (autograd keeps them)."""
+        body = self.pi[:-2]
+        h = None
+        if not torch.is_grad_enabled() or not (x.requires_grad or any(p.requires_grad for p in body.parameters())):
+            if self.layers == "f16x2":
+                hs = split16_hidden([list(body)], x, self._split16_scratch)
+                h = None if hs is None else hs[0]
+            if h is None:
+                h = fused_mlp_forward(body, x)
+        if h is None:
+            h = body(x).contiguous()
+        return h.clone() if h.data_ptr() % 16 else h
+
+    def _fused_head(self, obs, sigma=0.0, noise_clip=-1.0):
+        """No gradient: the hidden layers, then one mms_det_heads_act launch (sigma > 0: noise, clamps and counters inside it)."""
+        with torch.no_grad():
+            x = obs.reshape(-1, obs.shape[-1])
+            h = self._hidden(x)
+            counters = self._draw_counters(h.shape[0], h.device) if sigma > 0 else None
+            a = det_head_act(h, self.pi[-2].weight.detach(), self.pi[-2].bias.detach(), self.act_limit, sigma, noise_clip, self.seed, counters, self.row_offset)
+        return a.view(*obs.shape[:-1], a.shape[1])
+
+    def _block(self, obs, cat_obs):
+        """With a gradient: the hidden layers in torch, the head through _DetHead.  cat_obs None: the action in obs's leading shape;
+        else the critic's input block [cat_obs | action] as [M, W + A] (MLPActorCritic.pi_loss)."""
+        x = obs.reshape(-1, obs.shape[-1])
+        last = self.pi[-2]
+        out = _DetHead.apply(self._hidden(x), last.weight, last.bias, float(self.act_limit), cat_obs)
+        return out.view(*obs.shape[:-1], out.shape[1]) if (cat_obs is None and obs.dim() != 2) else out
+
+    def smoothed(self, obs, sigma, noise_clip, eps=None):
+        """The target action of td3.py:361-367 / ddpg.py:357-365, no gradient: clamp(pi(obs) + clamp(sigma z, -noise_clip, noise_clip),
+        -act_limit, act_limit).  On the fused path (`fused_grad=True`, a head the entry takes, no `eps`) the draw and both clamps sit
+        inside the head launch and z is the counter stream; otherwise the reference's five statements, on `eps` (given standard
+        normals: a recorded run) or torch.randn_like."""
+        with torch.no_grad():
+            if eps is None and sigma > 0 and noise_clip >= 0 and self._head_fusable(obs):
+                return self._fused_head(obs, float(sigma), float(noise_clip))
+            pi_targ = self(obs)
+            epsilon = (torch.randn_like(pi_targ) if eps is None else eps) * sigma
+            epsilon = torch.clamp(epsilon, -noise_clip, noise_clip)
+            a2 = pi_targ + epsilon
+            return torch.clamp(a2, -self.act_limit, self.act_limit)
 
 
 class MLPQFunction(_Split16Owner, nn.Module):
@@ -362,9 +568,11 @@ class MLPQFunction(_Split16Owner, nn.Module):
 
 
 class MLPActorCritic(nn.Module):
-    def __init__(self, observation_space, action_space, act_noise, device, hidden_sizes=(256, 256), activation=nn.ReLU, layers="fp32", fused_q=True):
+    def __init__(self, observation_space, action_space, act_noise, device, hidden_sizes=(256, 256), activation=nn.ReLU, layers="fp32",
+                 fused_grad=False, seed=None, row_offset=0, fused_q=True):
         super().__init__()
         self.fused_q = bool(fused_q)
+        self.fused_grad = bool(fused_grad)  # handed down to the actor (module docstring)
         if layers not in LAYERS:
             raise ValueError("layers must be one of %s, not %r" % (LAYERS, layers))
         self.layers = layers               # handed down to the actor and the critics ("f16x2": module docstring)
@@ -372,8 +580,10 @@ class MLPActorCritic(nn.Module):
         self.act_limit = action_space.high[0]
         self.act_noise = act_noise
         self.device = device
-        self.pi = MLPActor(obs_dim, act_dim, hidden_sizes, activation, self.act_limit, self.layers)
+        self.pi = MLPActor(obs_dim, act_dim, hidden_sizes, activation, self.act_limit, seed=0, row_offset=row_offset, fused_grad=self.fused_grad, layers=self.layers)
         self._build_q(obs_dim, act_dim, hidden_sizes, activation)
+        if self.fused_grad:                # after every layer: initialisation identical to the reference's
+            self.pi.seed = _draw_seed() if seed is None else int(seed)
 
     def _build_q(self, obs_dim, act_dim, hidden_sizes, activation):
         self.q = MLPQFunction(obs_dim, act_dim, hidden_sizes, activation, self.fused_q, self.layers)
@@ -386,8 +596,34 @@ class MLPActorCritic(nn.Module):
         copy it is ddpg.py:368-369 / td3.py:370-373 in one line (see fused_q_backup)."""
         return fused_q_backup(self._critics(), o2, a2, r, d, gamma, alpha, logp)
 
+    def q_loss(self, o, a, backup):
+        """compute_loss_q's loss for a given Bellman backup (ddpg.py:353, 372; td3.py:356-357, 376-378): sum over this network's critics
+        of mean((q(o, a) - backup)^2).  The critics' hidden layers run in torch on cat(o, a) (autograd keeps them); the last layers, the
+        loss and their backward are one mms_q_heads_loss call (sac.loss.q_heads_loss)."""
+        from ..sac.loss import q_heads_loss
+        qs = self._critics()
+        x = torch.cat([o, a], dim=-1)
+        x = x.reshape(-1, x.shape[-1])
+        return q_heads_loss([q.q[:-2](x) for q in qs], [q.q[-2] for q in qs], target=backup, mode="mse")
+
+    def pi_loss(self, o):
+        """compute_loss_pi (ddpg.py:377-382; td3.py:383-388): -mean(q(o, pi(o))) over the FIRST critic only (`q`; TD3: `q1`).  With
+        `fused_grad` the actor's head writes the action into the [o | a] block (no torch.cat); the critic's hidden layers run in torch,
+        its last layer, the mean and their backward are one mms_q_heads_loss call.  A critic whose parameters do not require a gradient
+        gets none computed."""
+        from ..sac.loss import q_heads_loss
+        q = self._critics()[0]
+        if self.pi._head_fusable(o) and torch.is_grad_enabled():
+            x = self.pi._block(o, o.reshape(-1, o.shape[-1]))
+        else:
+            x = torch.cat([o, self.pi(o)], dim=-1)
+            x = x.reshape(-1, x.shape[-1])
+        return q_heads_loss([q.q[:-2](x)], [q.q[-2]], mode="pi")
+
     def act(self, obs, deterministic=True):
         with torch.no_grad():
+            if not deterministic and obs.is_cuda and self.act_noise > 0 and self.pi._head_fusable(obs):
+                return self.pi._fused_head(obs, float(self.act_noise))      # mean + act_noise * N(0, 1) and the clamp inside the head launch
             a = self.pi(obs)
             if not deterministic:
                 if a.is_cuda:      # mean + std * N(0, 1) in one launch, clamp in place (the collection loop is launch bound)

@@ -42,7 +42,7 @@ import torch
 import torch.nn as nn
 
 from .... import _lib
-from ..ddpg.module import LAYERS, _Split16Owner, fused_mlp_forward, fused_q_backup, fused_q_forward, mlp, split16_hidden
+from ..ddpg.module import LAYERS, _NoiseOwner, _Split16Owner, _draw_seed, fused_mlp_forward, fused_q_backup, fused_q_forward, mlp, split16_hidden
 from .loss import q_heads_loss
 from ..ppo.loss import _p, _workspace       # (the device's cached, 256-byte aligned workspace: one per process, calls run in stream order)
 
@@ -105,12 +105,7 @@ class _SacHead(torch.autograd.Function):
                 dbias[A:] if need[4] else None) + (None,) * 7
 
 
-def _draw_seed():
-    """A noise-stream key from torch's default generator, so that torch.manual_seed makes runs reproducible."""
-    return int(torch.randint(0, 2 ** 62, (1,)).item())
-
-
-class SquashedGaussianMLPActor(_Split16Owner, nn.Module):
+class SquashedGaussianMLPActor(_NoiseOwner, _Split16Owner, nn.Module):
     def __init__(self, obs_dim, act_dim, hidden_sizes, activation, act_limit, seed=None, row_offset=0, fused_grad=False, layers="fp32"):
         super().__init__()
         self._init_layers(layers)          # "f16x2": `net` through split16_hidden (module docstring)
@@ -119,31 +114,8 @@ class SquashedGaussianMLPActor(_Split16Owner, nn.Module):
         self.mu_layer = nn.Linear(hidden_sizes[-1], act_dim)
         self.log_std_layer = nn.Linear(hidden_sizes[-1], act_dim)
         self.act_limit = act_limit
-        self.seed = _draw_seed() if seed is None else int(seed)    # drawn after the layers: their initialisation is the reference's
-        self.row_offset = int(row_offset)                           # global index of row 0 (data-parallel shards draw disjoint rows)
-        self._counters = None
-        self._counters_pinned = False      # a graph capture has used the counters: their address must not change
-
-    def reserve_counters(self, n, device):
-        """Size the per-row draw counters for n rows on `device` now (before a graph capture); returns them."""
-        return self.counters(n, device)
-
-    def counters(self, n, device):
-        """The per-row draw counters on `device`, at least n of them (grown on demand; what was drawn so far is kept).  Once pinned
-        by a graph capture they are never reallocated: a request they cannot serve raises."""
-        c = self._counters
-        if c is None or c.device != torch.device(device) or c.numel() < n:
-            capturing = torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing()
-            if self._counters_pinned or capturing:     # (allocated inside a capture, the zero fill would replay with the graph)
-                raise RuntimeError("SquashedGaussianMLPActor: %d rows on %s need new draw counters, but a graph capture holds or is recording the current "
-                                   "ones (%s); call pi.reserve_counters(<largest row count>, device) before capturing"
-                                   % (n, torch.device(device), "none" if c is None else "%d on %s" % (c.numel(), c.device)))
-            old = None if c is None else c.to(device)
-            c = torch.zeros(max(n, 0 if old is None else old.numel()), dtype=torch.int64, device=device)
-            if old is not None:
-                c[:old.numel()].copy_(old)
-            self._counters = c
-        return c
+        # (ddpg.module._NoiseOwner: seed, row_offset, the per-row draw counters) drawn after the layers: their initialisation is the reference's
+        self._init_noise(_draw_seed() if seed is None else seed, row_offset)
 
     def _fusable(self, obs):
         if not obs.is_cuda or obs.dtype != torch.float32 or obs.dim() < 1:

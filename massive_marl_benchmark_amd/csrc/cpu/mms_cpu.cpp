@@ -26,6 +26,7 @@
 #include "../maddpg_lane.h"
 #include "../sac_lane.h"
 #include "../sac_grad_lane.h"
+#include "../det_head_lane.h"
 #include "../gru_lane.h"
 #include "../gru_grad_lane.h"
 #include "../elu_ln_lane.h"
@@ -444,6 +445,66 @@ MMS_API int mms_det_heads_act_group(int device, int32_t groups, int64_t M, int32
         }
         if (noisy) counters[row] = c + 1;
     }
+    return 0;
+}
+// One deterministic actor head (include/mms.h: mms_det_heads_act): the grouped loop above for one network -- the same fmaf chain, so the
+// same bits as mms_det_heads_act_group(groups = 1, agent0 = 0) of this build -- with tanh(pre) kept and the clipped smoothing noise.
+MMS_API int mms_det_heads_act(int device, int64_t M, int32_t H, int32_t A, const float* h, const float* w, const float* b, float act_limit, float sigma,
+                              float noise_clip, uint64_t seed, int64_t* counters, int64_t row_offset, float* act_out, int64_t act_pitch, float* tanh_out,
+                              void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_det_heads_act(M, H, A, h, w, b, act_limit, sigma, noise_clip, counters, act_out, act_pitch, tanh_out))) return 1;
+    const bool noisy = sigma > 0.f;
+    const float clip = det_noise_clip(noise_clip);
+#pragma omp parallel for schedule(static)
+    for (int64_t row = 0; row < M; row++) {
+        const int64_t c = noisy ? counters[row] : 0;
+        const float* x = h + row * (int64_t)H;
+        for (int k = 0; k < A; k++) {
+            float s = 0.f;
+            for (int j = 0; j < H; j++) s = fmaf(x[j], w[(int64_t)k * H + j], s);
+            const float pre = s + b[k];
+            float act = mms::det_action(pre, act_limit);
+            if (tanh_out) tanh_out[row * A + k] = tanhf(pre);
+            if (noisy)
+                act = clip >= 0.f ? mms::det_smooth(act, sigma, clip, seed, (uint64_t)(row_offset + row), (uint64_t)c, (uint32_t)k, act_limit)
+                                  : mms::det_explore(act, sigma, seed, (uint64_t)(row_offset + row), (uint64_t)c, (uint32_t)k, act_limit);
+            if (act_out) act_out[row * act_pitch + k] = act;
+        }
+        if (noisy) counters[row] = c + 1;
+    }
+    return 0;
+}
+// The backward of that head's epilogue (include/mms.h: mms_det_heads_grad) over ../det_head_lane.h, on mms_sac_heads_grad's plan below:
+// rows in at most 1024 chunks of at least 256 (OpenMP over chunks), a chunk's column sums in double over ascending rows, the chunks
+// added in ascending order and rounded once -- the result does not depend on the number of threads.  No workspace.
+MMS_API int mms_det_heads_grad(int device, int64_t N, int32_t A, float act_limit, const float* t, const float* g, int64_t grad_pitch, float* dy,
+                               float* dbias, void* workspace, int64_t* ws_bytes, void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_det_heads_grad(N, A, t, g, grad_pitch, dy, workspace, ws_bytes, 0))) return 1;
+    if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query
+    if (N == 0) return 0;
+    int64_t chunk = (N + 1023) / 1024;
+    chunk = chunk < 256 ? 256 : chunk;
+    const int64_t nchunks = (N + chunk - 1) / chunk;
+    std::vector<double> part(dbias ? (size_t)nchunks * A : 0, 0.0);
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < nchunks; c++) {
+        double* p = dbias ? part.data() + c * A : nullptr;
+        const int64_t end = (c + 1) * chunk < N ? (c + 1) * chunk : N;
+        for (int64_t row = c * chunk; row < end; row++)
+            for (int j = 0; j < A; j++) {
+                const float d = mms::det_head_grad_one(t[row * A + j], g[row * grad_pitch + j], act_limit);
+                dy[row * A + j] = d;
+                if (p) p[j] += (double)d;
+            }
+    }
+    if (dbias)
+        for (int q = 0; q < A; q++) {
+            double s = 0.0;
+            for (int64_t c = 0; c < nchunks; c++) s += part[c * A + q];
+            dbias[q] = (float)s;
+        }
     return 0;
 }
 MMS_API int mms_q_heads_backup_group(int device, int32_t groups, int64_t M, int32_t H, const float* const* h, const float* const* w,

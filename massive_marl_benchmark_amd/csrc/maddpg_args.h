@@ -21,6 +21,9 @@ struct DetHeadsArgs {
     int64_t M, row_offset, act_pitch, joint_pitch;
     int H, A, agent0;
     float sigma;
+    // mms_det_heads_act (one network: groups = 1, agent0 = 0) only; the grouped entry leaves both at "none"
+    float* tanh_out;                        // NULL: no store; [M,A] dense, tanh(pre) before any noise
+    float noise_clip;                       // < 0: none (det_explore); >= 0: det_head_lane.h's det_smooth
 };
 
 // The last layer of `groups` critics and the Bellman backup per group (q_kernels.hip's QArgs with one network per group)

@@ -4,7 +4,10 @@
 //                                activation, agents/algorithms/marl/maddpg/module.py:36-46), the exploration noise of
 //                                MADDPG_policy.act (:165-175) and the stores: each agent's action to its own destination (a replay
 //                                ring row) AND to its columns of the joint action row -- torch's Linear, tanh, scale, randn, add,
-//                                clamp per agent, the cat of N tensors and N copies into N buffers in one launch
+//                                clamp per agent, the cat of N tensors and N copies into N buffers in one launch.  With one group it
+//                                is also mms_det_heads_act, the head of DDPG's / TD3's actor (rl/ddpg/module.py MLPActor): the same
+//                                block body, so the same bits, plus two things only that entry asks for -- tanh(pre) stored for the
+//                                backward (det_head_kernels.hip) and TD3's clipped smoothing noise (td3.py:361-367; det_head_lane.h)
 //   q_heads_backup_group_kernel  q_kernels.hip's q_heads_backup_kernel<1> with one critic per group (cal_value_loss, :218-219)
 //
 // The head's matrix phase is sac_kernels.hip's as separate code: the group on blockIdx.y, a block owns 16 rows, its WAVES waves split
@@ -21,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "det_head_lane.h"
 #include "maddpg_args.h"
 #include "maddpg_lane.h"
 #include "mms_lane.h"
@@ -104,9 +108,14 @@ __global__ void __launch_bounds__(64 * WAVES) det_heads_act_kernel(DetHeadsArgs 
         float sum = s_part[e];
 #pragma unroll
         for (int w = 1; w < WAVES; w++) sum += s_part[w * 16 * RW + e];
-        float act = det_action(sum + bg[k], limit);
-        if (a.sigma > 0.f)
-            act = det_explore(act, a.sigma, a.seed, (uint64_t)(a.row_offset + row), (uint64_t)a.counters[row], (uint32_t)(jcol0 + k), limit);
+        const float pre = sum + bg[k];
+        float act = det_action(pre, limit);
+        if (a.tanh_out) a.tanh_out[row * A + k] = tanhf(pre);      // (one network: mms_det_heads_act) the backward's t, before any noise
+        if (a.sigma > 0.f) {
+            const uint64_t rg = (uint64_t)(a.row_offset + row), cnt = (uint64_t)a.counters[row];
+            act = a.noise_clip >= 0.f ? det_smooth(act, a.sigma, a.noise_clip, a.seed, rg, cnt, (uint32_t)(jcol0 + k), limit)
+                                      : det_explore(act, a.sigma, a.seed, rg, cnt, (uint32_t)(jcol0 + k), limit);
+        }
         if (out) out[row * a.act_pitch + k] = act;
         if (a.joint_out) a.joint_out[row * a.joint_pitch + jcol0 + k] = act;
     }

@@ -46,6 +46,8 @@ hipError_t launch_param_step(const ParamArgs&, hipStream_t);
 int64_t sac_grad_ws_bytes(int64_t, int);
 hipError_t launch_sac_heads_grad(int64_t, int, float, float, const float*, const float*, const float*, const float*, const float*, float*, float*, void*,
                                  hipStream_t);
+int64_t det_grad_ws_bytes(int64_t, int);
+hipError_t launch_det_heads_grad(int64_t, int, float, const float*, const float*, int64_t, float*, float*, void*, hipStream_t);
 int64_t q_loss_ws_bytes(int64_t, int, int);
 hipError_t launch_q_heads_loss(int, int64_t, int, const float* const*, const float* const*, const float* const*, int, const float*, const float*, float,
                                float, float*, float* const*, float* const*, float* const*, float* const*, void*, hipStream_t);
@@ -416,8 +418,35 @@ __attribute__((visibility("default"))) int mms_det_heads_act_group(int device, i
         a.h[g] = h[g]; a.w[g] = w[g]; a.b[g] = b[g]; a.act_out[g] = act_out ? act_out[g] : nullptr; a.act_limit[g] = act_limit[g];
     }
     a.joint_out = joint_out; a.counters = counters; a.seed = seed; a.M = M; a.row_offset = row_offset; a.act_pitch = act_pitch;
-    a.joint_pitch = joint_pitch; a.H = H; a.A = A; a.agent0 = agent0; a.sigma = sigma;
+    a.joint_pitch = joint_pitch; a.H = H; a.A = A; a.agent0 = agent0; a.sigma = sigma; a.noise_clip = -1.f;
     MMS_FREE(mms::launch_det_heads_act(a, groups, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_det_heads_act(int device, int64_t M, int32_t H, int32_t A, const float* h, const float* w,
+                                                             const float* b, float act_limit, float sigma, float noise_clip, uint64_t seed,
+                                                             int64_t* counters, int64_t row_offset, float* act_out, int64_t act_pitch,
+                                                             float* tanh_out, void* s) {
+    MMS_DEV(device)
+    if (refused(check_det_heads_act(M, H, A, h, w, b, act_limit, sigma, noise_clip, counters, act_out, act_pitch, tanh_out))) return 1;
+    mms::DetHeadsArgs a = {};              // the grouped kernel with one group: the same block body, the same bits
+    a.h[0] = h; a.w[0] = w; a.b[0] = b; a.act_out[0] = act_out; a.act_limit[0] = act_limit;
+    a.counters = counters; a.seed = seed; a.M = M; a.row_offset = row_offset; a.act_pitch = act_pitch; a.H = H; a.A = A; a.sigma = sigma;
+    a.tanh_out = tanh_out; a.noise_clip = det_noise_clip(noise_clip);
+    MMS_FREE(mms::launch_det_heads_act(a, 1, (hipStream_t)s));
+    return 0;
+}
+
+__attribute__((visibility("default"))) int mms_det_heads_grad(int device, int64_t N, int32_t A, float act_limit, const float* t, const float* g,
+                                                              int64_t grad_pitch, float* dy, float* dbias, void* workspace, int64_t* ws_bytes,
+                                                              void* s) {
+    MMS_DEV(device)
+    const bool shapes = N >= 0 && N <= 0x7fffffff && A >= 1 && A <= 128;
+    const int64_t need = shapes ? mms::det_grad_ws_bytes(N, A) : 0;
+    if (refused(check_det_heads_grad(N, A, t, g, grad_pitch, dy, workspace, ws_bytes, need))) return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }                // the size query
+    if (N == 0) return 0;
+    MMS_FREE(mms::launch_det_heads_grad(N, A, act_limit, t, g, grad_pitch, dy, dbias, workspace, (hipStream_t)s));
     return 0;
 }
 

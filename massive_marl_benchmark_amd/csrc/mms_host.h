@@ -431,6 +431,37 @@ static inline std::string check_det_heads_act_group(int32_t groups, int64_t M, i
     return {};
 }
 
+// mms_det_heads_act: the grouped entry's limits for one network, two optional destinations
+static inline std::string check_det_heads_act(int64_t M, int32_t H, int32_t A, const float* h, const float* w, const float* b, float act_limit,
+                                              float sigma, float noise_clip, const int64_t* counters, const float* act_out, int64_t act_pitch,
+                                              const float* tanh_out) {
+    if (!h || !w || !b || M < 0 || A <= 0 || A > 128 || H <= 0 || (H % 64) != 0 || !(sigma >= 0.f) || noise_clip != noise_clip || act_limit != act_limit)
+        return "mms_det_heads_act: bad arguments (h, w, b required, A must be in 1..128, H a positive multiple of 64, M >= 0, sigma >= 0, no NaN)";
+    if (sigma > 0.f && !counters) return "mms_det_heads_act: sigma > 0 needs counters";
+    if ((addr(h) | addr(w)) & 15) return "mms_det_heads_act: hidden activations and weights must be 16-byte aligned";
+    if (!act_out && !tanh_out) return "mms_det_heads_act: no destination (act_out and tanh_out both NULL)";
+    if (act_out && act_pitch < A) return "mms_det_heads_act: act_pitch below A";
+    return {};
+}
+
+// the noise clip as the kernels take it: the value where it is finite and >= 0, -1 ("none") for a negative one and +inf
+static inline float det_noise_clip(float noise_clip) { return (noise_clip >= 0.f && noise_clip <= 3.4028234e38f) ? noise_clip : -1.f; }
+
+// mms_det_heads_grad: mms_sac_heads_grad's order -- the shapes, then (workspace NULL is the size query: nothing else is read; N == 0:
+// nothing to do, nothing else is read) the operands and the workspace against `need`, the bytes this build's plan asks for (CPU build: 0)
+static inline std::string check_det_heads_grad(int64_t N, int32_t A, const float* t, const float* g, int64_t grad_pitch, const float* dy,
+                                               const void* workspace, const int64_t* ws_bytes, int64_t need) {
+    if (!ws_bytes) return "mms_det_heads_grad: ws_bytes required";
+    if (N < 0 || N > 0x7fffffff) return "mms_det_heads_grad: N must be in 0..2147483647";
+    if (A < 1 || A > 128) return "mms_det_heads_grad: A must be in 1..128";
+    if (!workspace || N == 0) return {};
+    if (!t || !g || !dy) return "mms_det_heads_grad: null pointer (t, g and dy are required)";
+    if (grad_pitch < A) return "mms_det_heads_grad: grad_pitch below A";
+    if (*ws_bytes < need) return "mms_det_heads_grad: workspace too small (" + std::to_string(*ws_bytes) + " bytes, needs " + std::to_string(need) + ")";
+    if (addr(workspace) & 255) return "mms_det_heads_grad: workspace must be 256-byte aligned";
+    return {};
+}
+
 static inline std::string check_q_heads_backup_group(int32_t groups, int64_t M, int32_t H, const float* const* h, const float* const* w,
                                                      const float* const* b, float* const* q_out, const float* const* reward,
                                                      const uint8_t* const* done, float* const* backup) {
