@@ -64,6 +64,10 @@
  *     (algorithms/rl/trpo/trpo.py:290) and the create_graph=True
  *     gradient of the KL (:427)
  *   TRPO double backward of the KL's Hessian-vector product (:431)      mms_mlp_grad_rop
+ *   TRPO.update's policy-step head behind ActorCritic.evaluate:         mms_trpo_heads
+ *     surrogate, KL, their gradients with respect to mu, the KL's
+ *     Gauss-Newton column scaling and the line search's scalar
+ *     (algorithms/rl/trpo/trpo.py:287-298, 417-435, 464-478)
  *   HATRPO.fisher_vector_product / trpo_update's actor gradient         mms_ln_mlp_grad, mms_ln_mlp_jvp
  *     (algorithms/marl/hatrpo_trainer.py:170-179, :236)
  *   PPO.update's loss head: KL, clipped surrogate, value loss, entropy  mms_ppo_loss
@@ -1062,6 +1066,49 @@ int mms_ppo_loss(int device, int64_t M, int32_t A, const float* mu, const float*
                  const float* actions, const float* old_logp, const float* adv, const float* returns, const float* target_values,
                  const float* old_mu, const float* old_sigma, float clip, float value_coef, float entropy_coef, int32_t clipped_value,
                  float* out, float* dmu, float* dlog_std, float* dvalue, void* workspace, int64_t* ws_bytes, void* hip_stream);
+
+/* ---- The head of TRPO's policy step in one call (csrc/trpo_loss_kernels.hip) --------------------------------------------------------
+ * What agents/algorithms/rl/trpo/trpo.py evaluates behind ActorCritic.evaluate per minibatch -- the surrogate and the KL (:287-298), the
+ * output side of the KL's Hessian-vector product (:417-435) and the line search's evaluation (:464-478) -- as a dozen element-wise
+ * launches forward and again backward each time.  trpo.py takes its step with respect to actor.parameters() only: log_std gets no
+ * gradient anywhere in TRPO.update, so every derivative here is with respect to mu.
+ * Dense inputs: mu [M, A], log_std [A] (l below), rmu [M, A] (optional).  Stored inputs, read in place as row indices[i] of their base
+ * (row i when indices == NULL): actions [*, A], adv [*], old_mu [*, A], old_sigma [*, A] (what the reference stores as "sigma": log_std
+ * rows).  old_logp: stored [*] and read through indices, or, with old_logp_dense != 0, a dense [M] vector read at row i (the reference's
+ * line search measures every trial against the PREVIOUS evaluation's log-probabilities, trpo.py:409).  All f32 and contiguous, indices
+ * int64.
+ *   z_ij    = (a_ij - mu_ij) exp(-2 l_j)
+ *   logp_i  = sum_j (-0.5 z_ij^2 - 2 l_j - 0.5 log 2pi)        mms_ppo_loss's, ActorCritic.evaluate's
+ *   r_i     = exp(logp_i - old_logp_i)
+ *   a_loss  = mean_i (-adv_i r_i)                               trpo.py:287-288, 475-476
+ *   kl      = mean_i sum_j (l_j - os_ij + (exp(os_ij)^2 + (om_ij - mu_ij)^2) / (2 exp(l_j)^2) - 0.5)        trpo.py:294-298
+ *   gsur_ij = (-adv_i r_i / M) z_ij exp(-2 l_j)                 = d a_loss / d mu
+ *   gkl_ij  = (mu_ij - om_ij) / (exp(l_j)^2 M)                  = d kl / d mu
+ *   gn_ij   = rmu_ij / (exp(l_j)^2 M)                           = (d2 kl / d mu2) rmu: the KL's Hessian in mu is diagonal and constant
+ * With J = d mu / d theta the exact Hessian-vector product of the KL over the actor's parameters is
+ *   H v = J^T ((J v) / (exp(l)^2 M)) + sum_rows gkl . (d2 mu / d theta2) v:
+ * mms_mlp_grad_rop along v with g = gkl gives J v (its rmu) and the second term; this entry turns J v into gn; mms_mlp_grad(gn) is the
+ * first term.
+ * Outputs, each optional, at least one: out [2] = {a_loss, kl}, logp [M], gsur [M, A], gkl [M, A], gn [M, A].  What a call must be
+ * given follows from what it asks for, and nothing else is read: log_std always; mu for out, logp, gsur, gkl; actions for out, logp,
+ * gsur; old_logp and adv for out, gsur; old_mu for out, gkl; old_sigma for out; rmu for gn.  out + logp is the line search's
+ * evaluation; gn alone reads log_std and rmu and nothing stored.
+ * Each output has the same bits whichever others are asked for.  A row's outputs depend on that row, M and log_std alone.  The two sums
+ * are per-block partials in double, added in a fixed order, divided by M and rounded once: no atomics, no memset, bit-identical run to
+ * run.  At most two launches on hip_stream (one without out), no host synchronisation, graph-capturable.  16-byte accesses where A is a
+ * multiple of 4 and every [*, A] base given is 16-byte aligned; element by element otherwise, with the same bits.  gkl and gn have the
+ * same bits in the HIP and the CPU build (csrc/trpo_loss_lane.h says why the others agree to rounding only); on one build a_loss, kl
+ * and gsur have the bits of mms_ppo_loss's surrogate (with a clip range that holds every ratio), kl and dmu.
+ * The entry cannot see the values of indices: every one must be a valid row of the stored inputs in use.
+ * workspace / ws_bytes: mms_mlp_grad's convention (NULL stores the bytes needed and returns 0 -- nothing else is read; 256-byte aligned;
+ * a smaller one is an error; the CPU build needs 0 and runs on any aligned non-NULL workspace).  The workspace needs no initialisation.
+ * 1 <= M <= 0x7fffffff, 1 <= A <= MMS_PPO_LOSS_MAX_A.  Inputs are taken to be finite.  Bad arguments -- a pointer the requested outputs
+ * need is NULL (gn without rmu among them), no output at all, A or M out of range, a small or misaligned workspace -- return non-zero
+ * with mms_last_error(NULL) and write nothing. */
+int mms_trpo_heads(int device, int64_t M, int32_t A, const float* mu, const float* log_std, const float* rmu, const int64_t* indices,
+                   const float* actions, const float* adv, const float* old_mu, const float* old_sigma, const float* old_logp,
+                   int32_t old_logp_dense, float* out, float* logp, float* gsur, float* gkl, float* gn, void* workspace, int64_t* ws_bytes,
+                   void* hip_stream);
 
 /* ---- The MAPPO / HAPPO update's loss head and its gradients in one call (csrc/marl_loss_kernels.hip) --------------------------------
  * What agents/algorithms/marl/mappo_trainer.py:63-179 and happo_trainer.py:48-170 evaluate per minibatch behind

@@ -17,7 +17,7 @@ _lib_cpu = None
 
 # every symbol include/mms.h declares (tests check that the library exports all of them)
 SYMBOLS = ["mms_create", "mms_destroy", "mms_get_tensor", "mms_step", "mms_post_step", "mms_reset_all", "mms_set_state",
-           "mms_bind_obs_out", "mms_bind_obs_planes16", "mms_bind_actions", "mms_bind_policy_head", "mms_set_dr", "mms_set_obs_outputs", "mms_bind_rollout_out", "mms_ppo_act", "mms_ppo_heads_act", "mms_sac_heads_act", "mms_sac_heads_grad", "mms_q_heads_backup", "mms_q_heads_loss", "mms_det_heads_act_group", "mms_det_heads_act", "mms_det_heads_grad", "mms_q_heads_backup_group", "mms_linear2_act", "mms_linear_group_act", "mms_split_planes", "mms_split_planes_group", "mms_linear_group_act_split", "mms_split_planes16_group", "mms_split_planes16_cat", "mms_weight_planes16_group", "mms_chain_refresh16", "mms_fold_planes16_group", "mms_fold_scales16_group", "mms_linear_group_act_split16", "mms_row_stats_chan_group", "mms_marl_heads_finish", "mms_row_stats_group", "mms_row_moments_group", "mms_layernorm_group", "mms_marl_heads_act", "mms_marl_heads_eval", "mms_gru_group", "mms_gru_gates_group", "mms_gru_gates_grad_group", "mms_elu_ln_group", "mms_elu_ln_planes16_group", "mms_elu_ln_grad_group", "mms_marl_heads_fwd_group", "mms_marl_heads_grad_group", "mms_marl_views", "mms_gae_ppo", "mms_adv_normalize", "mms_gae_ppo_normalized", "mms_layer_clock_probe", "mms_gae_marl", "mms_gae_marl_agents", "mms_mlp_grad", "mms_mlp_grad_rop", "mms_ln_mlp_grad", "mms_ln_mlp_jvp", "mms_ppo_loss", "mms_marl_ppo_loss", "mms_marl_ppo_loss_group", "mms_param_step", "mms_param_step_partials",
+           "mms_bind_obs_out", "mms_bind_obs_planes16", "mms_bind_actions", "mms_bind_policy_head", "mms_set_dr", "mms_set_obs_outputs", "mms_bind_rollout_out", "mms_ppo_act", "mms_ppo_heads_act", "mms_sac_heads_act", "mms_sac_heads_grad", "mms_q_heads_backup", "mms_q_heads_loss", "mms_det_heads_act_group", "mms_det_heads_act", "mms_det_heads_grad", "mms_q_heads_backup_group", "mms_linear2_act", "mms_linear_group_act", "mms_split_planes", "mms_split_planes_group", "mms_linear_group_act_split", "mms_split_planes16_group", "mms_split_planes16_cat", "mms_weight_planes16_group", "mms_chain_refresh16", "mms_fold_planes16_group", "mms_fold_scales16_group", "mms_linear_group_act_split16", "mms_row_stats_chan_group", "mms_marl_heads_finish", "mms_row_stats_group", "mms_row_moments_group", "mms_layernorm_group", "mms_marl_heads_act", "mms_marl_heads_eval", "mms_gru_group", "mms_gru_gates_group", "mms_gru_gates_grad_group", "mms_elu_ln_group", "mms_elu_ln_planes16_group", "mms_elu_ln_grad_group", "mms_marl_heads_fwd_group", "mms_marl_heads_grad_group", "mms_marl_views", "mms_gae_ppo", "mms_adv_normalize", "mms_gae_ppo_normalized", "mms_layer_clock_probe", "mms_gae_marl", "mms_gae_marl_agents", "mms_mlp_grad", "mms_mlp_grad_rop", "mms_ln_mlp_grad", "mms_ln_mlp_jvp", "mms_ppo_loss", "mms_trpo_heads", "mms_marl_ppo_loss", "mms_marl_ppo_loss_group", "mms_param_step", "mms_param_step_partials",
            "mms_last_error", "mms_abi_version"]
 
 
@@ -113,6 +113,7 @@ def _bind(path):
     L.mms_ln_mlp_jvp.argtypes = [ci, ctypes.c_int32, c64, vp, cf] + [vp] * 11 + [vp, ctypes.POINTER(c64), vp]
     L.mms_ppo_loss.argtypes = [ci, c64, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, ctypes.c_int32, vp, vp, vp, vp, vp,
                                ctypes.POINTER(c64), vp]
+    L.mms_trpo_heads.argtypes = [ci, c64, ctypes.c_int32] + [vp] * 9 + [ctypes.c_int32] + [vp] * 5 + [vp, ctypes.POINTER(c64), vp]
     L.mms_marl_ppo_loss.argtypes = [ci, c64, ctypes.c_int32, vp, vp, vp, vp, vp, cf, cf, cf, cf] + [ctypes.c_int32] * 5 + [vp] * 8 + [ctypes.POINTER(c64), vp]
     L.mms_marl_ppo_loss_group.argtypes = [ci, ctypes.c_int32, c64, ctypes.c_int32, vp, cf, cf, cf, cf] + [ctypes.c_int32] * 5 + [vp, ctypes.POINTER(c64), vp]
     cd = ctypes.c_double

@@ -68,6 +68,40 @@ def _grad(net, g, save):
     return out, d, e
 
 
+def _rop(net, g, d, e, V, C):
+    """mms_mlp_grad_rop: the R-op of J^T g along the parameters' direction (V weights, C biases), with the d_l / e_l of _grad(net, g, save=True).
+    Returns (rmu = J v, [rdW_1, rdb_1, ...] = sum_rows g . (d2 mu) v)."""
+    L, idx, stream = _lib.for_device(g.device)
+    W = net.params[0::2]
+    rmu = torch.empty_like(g)
+    rdw = [torch.empty_like(w) for w in W]
+    rdb = [torch.empty_like(b) for b in net.params[1::2]]
+    dims, ws, nbytes = net.workspace("rop", L, idx, stream)
+    _lib.check(L.mms_mlp_grad_rop(idx, net.L, g.shape[0], dims, _p(net.x), _ptrs(net.hs), _ptrs(W), _ptrs(V), _ptrs(C), _p(g), _ptrs(d),
+                                  _ptrs(e), _p(rmu), _ptrs(rdw), _ptrs(rdb), _p(ws), ctypes.byref(nbytes), stream), None,
+               "mms_mlp_grad_rop", L)
+    out = []
+    for a, b in zip(rdw, rdb):
+        out += [a, b]
+    return rmu, out
+
+
+def _forward(x, params):
+    """(mu, the saved state): hidden layers Linear + ELU and an identity output layer through mms_linear2_act, one launch per layer."""
+    L, idx, stream = _lib.for_device(x.device)
+    W, B = params[0::2], params[1::2]
+    M, h, hs = x.shape[0], x, []
+    for l, (w, b) in enumerate(zip(W, B)):
+        y = torch.empty(M, w.shape[0], device=x.device)
+        last = l == len(W) - 1
+        _lib.check(L.mms_linear2_act(idx, M, w.shape[0], w.shape[1], _p(h), _p(w), _p(b), _p(y), None, None, None, None, 0 if last else 1,
+                                     stream), None, "mms_linear2_act", L)
+        if not last:
+            hs.append(y)
+        h = y
+    return h, _Net(x, hs, list(params), [x.shape[1]] + [w.shape[0] for w in W])
+
+
 class _ActorMLPGrad(torch.autograd.Function):
     """forward: J^T g (mms_mlp_grad).  backward: its R-op along the parameters' direction (mms_mlp_grad_rop)."""
 
@@ -83,20 +117,7 @@ class _ActorMLPGrad(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, *vs):
         net, (g,) = ctx.net, ctx.saved_tensors
-        L, idx, stream = _lib.for_device(g.device)
-        W = net.params[0::2]
-        V = [v.contiguous() for v in vs[0::2]]
-        C = [c.contiguous() for c in vs[1::2]]
-        rmu = torch.empty_like(g)
-        rdw = [torch.empty_like(w) for w in W]
-        rdb = [torch.empty_like(b) for b in net.params[1::2]]
-        dims, ws, nbytes = net.workspace("rop", L, idx, stream)
-        _lib.check(L.mms_mlp_grad_rop(idx, net.L, g.shape[0], dims, _p(net.x), _ptrs(net.hs), _ptrs(W), _ptrs(V), _ptrs(C), _p(g), _ptrs(ctx.d),
-                                      _ptrs(ctx.e), _p(rmu), _ptrs(rdw), _ptrs(rdb), _p(ws), ctypes.byref(nbytes), stream), None,
-                   "mms_mlp_grad_rop", L)
-        out = []
-        for a, b in zip(rdw, rdb):
-            out += [a, b]
+        rmu, out = _rop(net, g, ctx.d, ctx.e, [v.contiguous() for v in vs[0::2]], [c.contiguous() for c in vs[1::2]])
         return (None, rmu, *out)
 
 
@@ -106,18 +127,7 @@ class _ActorMLP(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, *params):
-        L, idx, stream = _lib.for_device(x.device)
-        W, B = params[0::2], params[1::2]
-        M, h, hs = x.shape[0], x, []
-        for l, (w, b) in enumerate(zip(W, B)):
-            y = torch.empty(M, w.shape[0], device=x.device)
-            last = l == len(W) - 1
-            _lib.check(L.mms_linear2_act(idx, M, w.shape[0], w.shape[1], _p(h), _p(w), _p(b), _p(y), None, None, None, None, 0 if last else 1,
-                                         stream), None, "mms_linear2_act", L)
-            if not last:
-                hs.append(y)
-            h = y
-        ctx.net = _Net(x, hs, list(params), [x.shape[1]] + [w.shape[0] for w in W])
+        h, ctx.net = _forward(x, params)
         return h
 
     @staticmethod
@@ -157,14 +167,65 @@ class ActorCritic(_PPOActorCritic):
                 return False
         return obs.device.type in ("cuda", "cpu") and obs.shape[1] == mods[0].in_features and obs.shape[0] > 0
 
+    def _actor_params(self):
+        return [p for m in self.actor if isinstance(m, nn.Linear) for p in (m.weight, m.bias)]
+
+    def mean(self, observations):
+        """The actor's mean as `evaluate` takes it: through _ActorMLP when the actor qualifies, the torch module otherwise."""
+        if not self._grad_path_qualifies(observations):
+            return self.actor(observations)
+        return _ActorMLP.apply(observations, *self._actor_params())
+
+    def mean_saved(self, observations):
+        """Not in the reference: (mu, net) without an autograd graph -- _ActorMLP's forward with its saved state in hand, for a caller that
+        takes the actor's derivatives itself (trpo.py: J^T g by `grad_flat`, the curvature product by `rop_flat`).  The actor must qualify."""
+        if not self._grad_path_qualifies(observations):
+            raise ValueError("ActorCritic.mean_saved: the actor does not qualify for the kernels' backward passes (fused_grad=True, fp32 "
+                             "Linear / ELU layers with biases, input widths multiples of 4, contiguous fp32 observations on its device)")
+        with torch.no_grad():
+            return _forward(observations, [p.detach() for p in self._actor_params()])
+
+    def mean_nograd(self, observations):
+        """Not in the reference: the actor's mean without a graph, through the no-gradient layer route (`_hidden_one`: mms_linear2_act with
+        bias and ELU in the epilogue, persistent activations) plus the last Linear where the actor is an fp32 ELU network; the torch
+        module otherwise."""
+        with torch.no_grad():
+            if (observations.dtype == torch.float32 and observations.dim() == 2 and self._fp32_net_qualifies(self.actor)
+                    and observations.device == self.actor[-1].weight.device):
+                return self.actor[-1](self._hidden_one(self.actor, observations.contiguous()))
+            return self.actor(observations)
+
     def evaluate(self, observations, states, actions):
         if not self._grad_path_qualifies(observations):
             return super().evaluate(observations, states, actions)
-        params = [p for m in self.actor if isinstance(m, nn.Linear) for p in (m.weight, m.bias)]
-        mean = _ActorMLP.apply(observations, *params)
+        mean = self.mean(observations)
         scale_log = 2.0 * self.log_std                               # as ppo/module.py's evaluate from here on
         z = (actions - mean) * torch.exp(-scale_log)
         log_prob = (-0.5 * z * z - scale_log - 0.5 * math.log(2.0 * math.pi)).sum(-1)
         entropy = (0.5 + 0.5 * math.log(2.0 * math.pi) + scale_log).sum(-1).expand(mean.shape[0])
         value = self.critic(states if self.asymmetric else observations)
         return log_prob, entropy, value, mean, self.log_std.repeat(mean.shape[0], 1)
+
+
+def grad_flat(net, g):
+    """J^T g over the actor's parameters in the flat layout of actor.parameters() (mms_mlp_grad)."""
+    out, _, _ = _grad(net, g.contiguous(), save=False)
+    return torch.cat([t.reshape(-1) for t in out])
+
+
+def grad_saved(net, g):
+    """The d_l / e_l of mms_mlp_grad(g, save): what rop_flat needs of the gradient g it differentiates."""
+    _, d, e = _grad(net, g.contiguous(), save=True)
+    return d, e
+
+
+def rop_flat(net, g, d, e, v):
+    """(J v, sum_rows g . (d2 mu / d theta2) v as a flat vector) along the flat direction v (mms_mlp_grad_rop)."""
+    V, C, at = [], [], 0
+    for w, b in zip(net.params[0::2], net.params[1::2]):
+        V.append(v[at:at + w.numel()].view(w.shape).contiguous())
+        at += w.numel()
+        C.append(v[at:at + b.numel()].contiguous())
+        at += b.numel()
+    rmu, out = _rop(net, g, d, e, V, C)
+    return rmu, torch.cat([t.reshape(-1) for t in out])

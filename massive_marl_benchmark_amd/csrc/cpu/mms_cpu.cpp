@@ -20,6 +20,7 @@
 #include "../mms_host.h"
 #include "../rollout_lane.h"
 #include "../ppo_loss_lane.h"
+#include "../trpo_loss_lane.h"
 #include "../marl_loss_lane.h"
 #include "../q_lane.h"
 #include "../q_loss_lane.h"
@@ -1803,6 +1804,66 @@ MMS_API int mms_ppo_loss(int device, int64_t M, int32_t A, const float* mu, cons
     mms::ppo_finish_scalars(tot[0], tot[1], tot[2], entropy, M, value_coef, entropy_coef, out);
     if (grads)
         for (int j = 0; j < A; j++) dlog_std[j] = mms::ppo_finish_dlog_std(tot[3 + j], entropy_coef);
+    return 0;
+}
+
+// ---- the head of TRPO's policy step (include/mms.h: mms_trpo_heads) over ../trpo_loss_lane.h -----------------------------------------
+// Chunks and sums as mms_ppo_loss above: a row's logp and KL term in double over ascending columns, a chunk's two partials in double
+// over ascending rows, the chunks added in ascending order, one division by M and one rounding.  No workspace.
+MMS_API int mms_trpo_heads(int device, int64_t M, int32_t A, const float* mu, const float* log_std, const float* rmu, const int64_t* indices,
+                           const float* actions, const float* adv, const float* old_mu, const float* old_sigma, const float* old_logp,
+                           int32_t old_logp_dense, float* out, float* logp_out, float* gsur, float* gkl, float* gn, void* workspace, int64_t* ws_bytes,
+                           void*) {
+    if (cpu_only(device)) return 1;
+    if (refused(check_trpo_heads(M, A, mu, log_std, rmu, actions, adv, old_mu, old_sigma, old_logp, out, logp_out, gsur, gkl, gn, workspace, ws_bytes, 0)))
+        return 1;
+    if (!workspace) { *ws_bytes = 0; return 0; }                  // the size query
+    const bool sums = out != nullptr, want_lp = sums || logp_out || gsur, want_r = sums || gsur;
+    int64_t chunk = (M + 1023) / 1024;
+    chunk = chunk < 256 ? 256 : chunk;
+    const int64_t nchunks = (M + chunk - 1) / chunk;
+    const float inv_m = 1.0f / (float)M;
+    float einv[MMS_PPO_LOSS_MAX_A], den[MMS_PPO_LOSS_MAX_A], cden[MMS_PPO_LOSS_MAX_A];
+    for (int j = 0; j < A; j++) {
+        mms::ppo_col_consts(log_std[j], einv[j], den[j]);
+        cden[j] = mms::trpo_col_den(log_std[j], M);
+    }
+    std::vector<double> part((size_t)nchunks * 2, 0.0);
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < nchunks; c++) {
+        double* p = part.data() + c * 2;
+        const int64_t end = (c + 1) * chunk < M ? (c + 1) * chunk : M;
+        float z[MMS_PPO_LOSS_MAX_A];
+        for (int64_t row = c * chunk; row < end; row++) {
+            const int64_t src = indices ? indices[row] : row;
+            double logp = 0.0, kl = 0.0;
+            if (want_lp)
+                for (int j = 0; j < A; j++) logp += (double)mms::ppo_logp_term(actions[src * A + j], mu[row * A + j], log_std[j], einv[j], z[j]);
+            if (sums)
+                for (int j = 0; j < A; j++)
+                    kl += (double)mms::ppo_kl_term(log_std[j], old_sigma[src * A + j], old_mu[src * A + j], mu[row * A + j], den[j]);
+            float g = 0.f;
+            if (want_r) {
+                const mms::TrpoRow r = mms::trpo_row(logp, old_logp[old_logp_dense ? row : src], adv[src], inv_m);
+                g = r.g;
+                if (sums) p[0] += (double)r.term;
+            }
+            if (sums) p[1] += kl;
+            if (logp_out) logp_out[row] = (float)logp;
+            for (int j = 0; j < A; j++) {
+                if (gsur) gsur[row * A + j] = mms::trpo_gsur(g, z[j], einv[j]);
+                if (gkl) gkl[row * A + j] = mms::trpo_gkl(mu[row * A + j], old_mu[src * A + j], cden[j]);
+                if (gn) gn[row * A + j] = mms::trpo_gn(rmu[row * A + j], cden[j]);
+            }
+        }
+    }
+    if (sums) {
+        double tot[2] = {0.0, 0.0};
+        for (int64_t c = 0; c < nchunks; c++)
+            for (int q = 0; q < 2; q++) tot[q] += part[c * 2 + q];
+        out[0] = mms::trpo_finish_mean(tot[0], M);
+        out[1] = mms::trpo_finish_mean(tot[1], M);
+    }
     return 0;
 }
 

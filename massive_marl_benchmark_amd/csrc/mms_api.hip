@@ -37,6 +37,9 @@ hipError_t launch_q_heads_backup(int, int64_t, int, const float* const*, const f
 int64_t ppo_loss_ws_bytes(int64_t, int);
 hipError_t launch_ppo_loss(int64_t, int, const float*, const float*, const float*, const int64_t*, const float*, const float*, const float*, const float*,
                            const float*, const float*, const float*, float, float, float, int, float*, float*, float*, float*, void*, hipStream_t);
+int64_t trpo_heads_ws_bytes(int64_t, int);
+hipError_t launch_trpo_heads(int64_t, int, const float*, const float*, const float*, const int64_t*, const float*, const float*, const float*, const float*,
+                             const float*, int, float*, float*, float*, float*, float*, void*, hipStream_t);
 int64_t marl_loss_ws_bytes(int64_t, int);
 hipError_t launch_marl_ppo_loss(int64_t, int, const float*, const float*, const float*, const int64_t*, const mms_marl_loss_fields&, float, float, float,
                                 float, int, int, int, int, int, const float*, const float*, float*, float*, float*, float*, float*, void*, hipStream_t);
@@ -1052,6 +1055,24 @@ __attribute__((visibility("default"))) int mms_ppo_loss(int device, int64_t M, i
     if (!workspace) { *ws_bytes = need; return 0; }                // the size query
     MMS_FREE(mms::launch_ppo_loss(M, A, mu, log_std, value, indices, actions, old_logp, adv, returns, target_values, old_mu, old_sigma, clip, value_coef,
                                   entropy_coef, clipped_value, out, dmu, dlog_std, dvalue, workspace, (hipStream_t)s));
+    return 0;
+}
+
+// ---- the head of TRPO's policy step (trpo_loss_kernels.hip) -------------------------------------------------------------------------
+
+__attribute__((visibility("default"))) int mms_trpo_heads(int device, int64_t M, int32_t A, const float* mu, const float* log_std, const float* rmu,
+                                                          const int64_t* indices, const float* actions, const float* adv, const float* old_mu,
+                                                          const float* old_sigma, const float* old_logp, int32_t old_logp_dense, float* out,
+                                                          float* logp, float* gsur, float* gkl, float* gn, void* workspace, int64_t* ws_bytes,
+                                                          void* s) {
+    MMS_DEV(device)
+    const bool shapes = M >= 1 && M <= 0x7fffffff && A >= 1 && A <= MMS_PPO_LOSS_MAX_A;
+    const int64_t need = shapes ? mms::trpo_heads_ws_bytes(M, A) : 0;
+    if (refused(check_trpo_heads(M, A, mu, log_std, rmu, actions, adv, old_mu, old_sigma, old_logp, out, logp, gsur, gkl, gn, workspace, ws_bytes, need)))
+        return 1;
+    if (!workspace) { *ws_bytes = need; return 0; }                // the size query
+    MMS_FREE(mms::launch_trpo_heads(M, A, mu, log_std, rmu, indices, actions, adv, old_mu, old_sigma, old_logp, old_logp_dense != 0, out, logp, gsur, gkl,
+                                    gn, workspace, (hipStream_t)s));
     return 0;
 }
 

@@ -498,6 +498,28 @@ static inline std::string check_ppo_loss(int64_t M, int32_t A, const float* mu, 
     return {};
 }
 
+// mms_trpo_heads: check_ppo_loss's order; what is required follows from the outputs asked for (include/mms.h lists it).
+static inline std::string check_trpo_heads(int64_t M, int32_t A, const float* mu, const float* log_std, const float* rmu, const float* actions,
+                                           const float* adv, const float* old_mu, const float* old_sigma, const float* old_logp, const float* out,
+                                           const float* logp, const float* gsur, const float* gkl, const float* gn, const void* workspace,
+                                           const int64_t* ws_bytes, int64_t need) {
+    if (!ws_bytes) return "mms_trpo_heads: ws_bytes required";
+    if (M < 1 || M > 0x7fffffff) return "mms_trpo_heads: M must be in 1..2147483647";
+    if (A < 1 || A > MMS_PPO_LOSS_MAX_A) return "mms_trpo_heads: A must be in 1.." + std::to_string(MMS_PPO_LOSS_MAX_A);
+    if (!workspace) return {};
+    if (!out && !logp && !gsur && !gkl && !gn) return "mms_trpo_heads: no output (out, logp, gsur, gkl and gn all NULL)";
+    if (!log_std) return "mms_trpo_heads: null pointer (log_std is required)";
+    if (gn && !rmu) return "mms_trpo_heads: gn needs rmu";
+    if ((out || logp || gsur || gkl) && !mu) return "mms_trpo_heads: null pointer (out, logp, gsur and gkl need mu)";
+    if ((out || logp || gsur) && !actions) return "mms_trpo_heads: null pointer (out, logp and gsur need actions)";
+    if ((out || gsur) && (!old_logp || !adv)) return "mms_trpo_heads: null pointer (out and gsur need old_logp and adv)";
+    if ((out || gkl) && !old_mu) return "mms_trpo_heads: null pointer (out and gkl need old_mu)";
+    if (out && !old_sigma) return "mms_trpo_heads: null pointer (out needs old_sigma)";
+    if (*ws_bytes < need) return "mms_trpo_heads: workspace too small (" + std::to_string(*ws_bytes) + " bytes, needs " + std::to_string(need) + ")";
+    if (addr(workspace) & 255) return "mms_trpo_heads: workspace must be 256-byte aligned";
+    return {};
+}
+
 // mms_marl_ppo_loss: as check_ppo_loss, with the stored fields' pitches and what each flag requires.
 static inline std::string check_marl_ppo_loss(int64_t M, int32_t A, const float* mu, const float* std, const float* value, const mms_marl_loss_fields* f,
                                               int32_t policy_masks, int32_t value_masks, int32_t use_norm, const float* norm_mean,
